@@ -1,12 +1,21 @@
 #!/usr/bin/env python
 """Headline benchmark of the faststyle hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 without a torchrun environment: bench.py starts the N ranks itself -- it re-runs the same command as
   `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py ...`
   (one process per GPU, RCCL); launched that way by the caller it just joins.  `--launch` does the same for --gpus 1
   (RCCL all-reduce at world size 1); `--rendezvous-only` is a preflight of the launcher alone.  Rank 0 prints the ONE JSON
   line; `value` is the whole-job rate (max-over-ranks time), `per_rank_images_per_sec` every rank's own.
+
+A plain run is lean: set-up, W warm-up steps (at least 2 with the hipGraph), the K timed steps of the b32 leg, the
+outputs of the last timed step (with --dump-outputs) and the ONE JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config).  Everything else below -- the b4 leg, roofline / per-kernel / section passes, gram, stylize legs,
+cpu_baseline -- runs with --full only.
+
+  --dump-outputs DIR   after the timed steps, the arrays the timed step leaves to its caller, as float32 DIR/<name>.npy:
+                       losses (its return value), params (after the step's TF-Adam update), grads (the all-reduced
+                       gradients), adam_m, adam_v.  Inputs are seeded: the same arguments give the same inputs every run.
 
 A "step" is one full train.py loop body (reference train.py:245-275) on a synthetic 256x256 batch: content-target VGG
 pass, transform-net forward, VGG16 + Gram + losses, full backward, ONE RCCL all-reduce (SUM) of the 424,102 gradients
@@ -99,12 +108,17 @@ def same_build(profile_json):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps of the b32 leg (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch-per-gpu", type=int, default=32)
     ap.add_argument("--size", type=int, default=256)
-    ap.add_argument("--b4-steps", type=int, default=200, help="timed steps of the batch-4-per-GPU leg")
-    ap.add_argument("--profile-steps", type=int, default=5, help="eager steps of the per-kernel / per-section pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: idle gaps, eager section / per-kernel passes (roofline, gram), the "
+                         "batch-4 leg, the stylize legs and the CPU baseline (--no-b4 / --no-stylize / --no-cpu-baseline leave a leg out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as float32 DIR/<name>.npy")
+    ap.add_argument("--b4-steps", type=int, default=200, help="timed steps of the batch-4-per-GPU leg (--full)")
+    ap.add_argument("--profile-steps", type=int, default=5, help="eager steps of the per-kernel / per-section pass (--full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-quick", action="store_true", help="one warm-up + one timed run per CPU figure (contract test)")
     ap.add_argument("--no-stylize", action="store_true")
@@ -116,7 +130,10 @@ def parse():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="launcher preflight: every rank joins the process group (RCCL, or gloo when no GPU is visible), SUM-"
                          "all-reduces its rank, rank 0 prints one JSON line; no engine, no kernels")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def free_port():
@@ -362,8 +379,20 @@ def main():
             return [float(x) for x in t.tolist()]
         return [float(v)]
 
-    def train_leg(batch, steps, warmup, tr):
-        """Timed region + the eager per-section / per-kernel passes of one batch size."""
+    def dump_outputs(d, tr, losses):
+        """--dump-outputs: what the last timed step leaves to its caller, float32, rank 0 (params / moments are identical on
+        every rank after the SUM all-reduce); 4 x 424,102 values + 4 losses = 6.8 MB."""
+        if rank != 0:
+            return
+        os.makedirs(d, exist_ok=True)
+        arrs = {"losses": losses, "params": tr.params, "grads": tr.grads, "adam_m": tr.m, "adam_v": tr.v}
+        for name, t in arrs.items():
+            np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(tr.eng.mem.to_numpy(t), dtype=np.float32))
+        print("bench: wrote %s/{%s}.npy" % (d, ",".join(arrs)), file=sys.stderr, flush=True)
+
+    def train_leg(batch, steps, warmup, tr, full=True, dump_dir=None):
+        """Timed region (+ the outputs of its last step), and with full=True the idle-gap steps and the eager per-section /
+        per-kernel passes of one batch size."""
         pool = [torch.rand((batch, S, S, 3), device="cuda", generator=g) * 255.0 for _ in range(4)]
         n_warm = max(warmup, 2 if tr.use_graph else 1)             # (graph mode: first step captures, second replays)
         for i in range(n_warm):
@@ -378,6 +407,11 @@ def main():
         elapsed = max_over_ranks(mine)
         res = {"elapsed": elapsed, "graphed": graphed, "loss": float(losses[0].item()),
                "per_rank_images_per_sec": [round(steps * batch / t, 2) for t in all_ranks(mine)]}
+        if dump_dir:
+            dump_outputs(dump_dir, tr, losses)
+        if not full:
+            del pool
+            return res
         # ---- where the all-reduce + Adam (outside the hipGraph) and the host leave the GPU idle: 20 more steps of the timed
         # kind with an event before and after each; gap = end of step i -> start of step i+1 on the device time line
         Gs = 20
@@ -448,9 +482,9 @@ def main():
 
     # ------------------------------------------------------------------ the metric's configuration: batch 32 per GPU
     tr = trainer.Trainer(eng, params, vgg_w, style, learn_rate=1e-3, dist=ddist, use_graph=not args.no_graph)
-    main_leg = train_leg(B, args.steps, args.warmup, tr)
+    main_leg = train_leg(B, args.steps, args.warmup, tr, args.full, args.dump_outputs)
     b4_leg = None
-    if not args.no_b4 and B != 4:
+    if args.full and not args.no_b4 and B != 4:
         tr4 = trainer.Trainer(eng, params, None, style, learn_rate=1e-3, dist=ddist, use_graph=not args.no_graph)
         b4_leg = train_leg(4, args.b4_steps, args.warmup, tr4)
         del tr4
@@ -458,7 +492,7 @@ def main():
 
     # ------------------------------------------------------------------ configs[1] / configs[4]: forward only, independent frames
     fwd = {}
-    if not args.no_stylize:
+    if args.full and not args.no_stylize:
         from faststyle_amd import ckpt
         Wc = ckpt.load_checkpoint(os.path.join(ROOT, "models", "starry_final.ckpt"))
         flat = eng.mem.from_numpy(eng.flatten_params(Wc))
@@ -585,6 +619,30 @@ def main():
         fwd["stylize_1080p_b8_fp32"] = fwd_leg((8, 1080, 1920, 3), False, 2, 8, False)
 
     if rank == 0:
+        # the headline: every run reports it, from the timed region alone
+        value = args.steps * B * world / main_leg["elapsed"]
+        out = {
+            "metric": "images/sec train-step 256x256 b32 (+ Gram GFLOPs % MFMA peak); 720p stylize fps",
+            "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * main_leg["elapsed"] / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "per_rank_images_per_sec": main_leg["per_rank_images_per_sec"],
+            "data": "synthetic (uniform[0,255) images; %s VGG16 weights; random-init transform net)"
+                    % ("real" if real_vgg else "synthetic He-normal"),
+            "config": {"workload": "train.py step: %dx%d, batch %d per GPU (BASELINE metric 'b32' on one GPU; global batch %d), VGG16 "
+                                   "conv1_2/2_2/3_3/4_3 Gram style loss + conv3_3 content loss, resize-conv transform net, TF-Adam, "
+                                   "hipGraph-replayed; secondary line train_b4_per_gpu = the same step at batch 4 per GPU "
+                                   "(BASELINE configs[2]; configs[3] at N=8)" % (S, S, B, B * world),
+                       "global_batch": B * world, "batch_per_gpu": B, "image_size": [S, S], "parallelism": "dp%d" % world,
+                       "collective": ("one %s all-reduce(SUM) of 1,696,408 B per step (world size %d)%s" % (
+                           "RCCL" if backend == "nccl" else backend, world,
+                           "; TEST MODE: the ranks time-share one GPU" if share_gpu else "")) if launched else "none (single process)",
+                       "style_image": "starry_night_crop.jpg 640x938"},
+            "final_loss": main_leg["loss"], "hip_graph": main_leg["graphed"],
+        }
+        dg = {"b32_images_per_sec": out["value"], "b32_ms_per_step": out["ms_per_step"], "n_gpus": world}
+
+    if rank == 0 and args.full:
         def leg_report(leg, batch, steps):
             n_img = steps * batch * world
             value = n_img / leg["elapsed"]
@@ -677,23 +735,7 @@ def main():
                 traffic, traffic_src = k["traffic_bytes_per_launch"], os.path.relpath(tpath, ROOT)
             elif k and tj.get("batch_per_gpu") == B:
                 traffic_src = os.path.relpath(tpath, ROOT) + " (NOT quoted: collected from other kernel sources than the running build)"
-        out = {
-            "metric": "images/sec train-step 256x256 b32 (+ Gram GFLOPs % MFMA peak); 720p stylize fps",
-            "value": rep["images_per_sec"], "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": rep["ms_per_step"],
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "per_rank_images_per_sec": rep["per_rank_images_per_sec"],
-            "data": "synthetic (uniform[0,255) images; %s VGG16 weights; random-init transform net)"
-                    % ("real" if real_vgg else "synthetic He-normal"),
-            "config": {"workload": "train.py step: %dx%d, batch %d per GPU (BASELINE metric 'b32' on one GPU; global batch %d), VGG16 "
-                                   "conv1_2/2_2/3_3/4_3 Gram style loss + conv3_3 content loss, resize-conv transform net, TF-Adam, "
-                                   "hipGraph-replayed; secondary line train_b4_per_gpu = the same step at batch 4 per GPU "
-                                   "(BASELINE configs[2]; configs[3] at N=8)" % (S, S, B, B * world),
-                       "global_batch": B * world, "batch_per_gpu": B, "image_size": [S, S], "parallelism": "dp%d" % world,
-                       "collective": ("one %s all-reduce(SUM) of 1,696,408 B per step (world size %d)%s" % (
-                           "RCCL" if backend == "nccl" else backend, world,
-                           "; TEST MODE: the ranks time-share one GPU" if share_gpu else "")) if launched else "none (single process)",
-                       "style_image": "starry_night_crop.jpg 640x938"},
+        out.update({
             "roofline": {"bound": "mfma",
                          "kernel": names[di] + (": fp32 MFMA, Winograd F(4x4,3x3) 3x3 conv; achieved = FLOPs EXECUTED (36 products per "
                                                 "4x4 outputs instead of 144: a quarter of the direct form's, 0.5625 of F(2x2,3x3)'s)" if di in WINO_F4 else
@@ -720,10 +762,9 @@ def main():
             "step_gflop_executed": rep["step_gflop_executed"], "step_tflops_executed": rep["step_tflops_executed"],
             "step_frac_executed": rep["step_frac_executed"], "all_mfma_kernels_tflops": rep["all_mfma_kernels_tflops"],
             "mfma_kernel_ms_per_step": rep["mfma_kernel_ms_per_step"], "sections_ms_eager": rep["sections_ms_eager"],
-            "final_loss": rep["final_loss"], "hip_graph": rep["hip_graph"],
             "step_device_ms": rep["step_device_ms"], "inter_step_gap_us": rep["inter_step_gap_us"], "allreduce_us": rep["allreduce_us"],
             "host_gap_frac_of_step": rep["host_gap_frac_of_step"],
-        }
+        })
         if b4_leg is not None:
             r4, d4, pk4 = leg_report(b4_leg, 4, args.b4_steps)
             r4["dominant_kernel"] = names[d4]
@@ -739,10 +780,8 @@ def main():
             out["stylize_1080p_b8_fp32_fps"] = fwd["stylize_1080p_b8_fp32"]["fps"]
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(S)
-        # the headline figures once more as the LAST key of the line (and as the last stderr line): what a log tail shows
-        dg = {"b32_images_per_sec": out["value"], "b32_ms_per_step": out["ms_per_step"], "n_gpus": world,
-              "roofline_frac": out["roofline"]["frac"], "roofline_kernel": names[di].split(" (")[0],
-              "vgg_gram_frac_executed": out["vgg_gram_substep"]["frac_executed"], "step_frac_executed": out["step_frac_executed"]}
+        dg.update({"roofline_frac": out["roofline"]["frac"], "roofline_kernel": names[di].split(" (")[0],
+                   "vgg_gram_frac_executed": out["vgg_gram_substep"]["frac_executed"], "step_frac_executed": out["step_frac_executed"]})
         if b4_leg is not None:
             dg["b4_per_gpu_images_per_sec"] = out["train_b4_per_gpu"]["images_per_sec"]
             dg["b4_ms_per_step"] = out["train_b4_per_gpu"]["ms_per_step"]
@@ -756,6 +795,8 @@ def main():
             dg["stylize_1080p_b8_fp32_fps"] = out["stylize_1080p_b8_fp32_fps"]
         if "cpu_baseline" in out:
             dg["cpu_baseline_images_per_sec"] = out["cpu_baseline"].get("value")
+    if rank == 0:
+        # the headline figures once more as the LAST key of the line (and as the last stderr line): what a log tail shows
         out["digest"] = dg
         print(json.dumps(out))
         sys.stdout.flush()

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full",
                           "--b4-steps", "5", "--profile-steps", "2", "--cpu-quick"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -52,6 +53,47 @@ def test_bench_json_contract():
     assert c["torch_cpu"]["value"] > 0 and c["one_core"]["cores"] == 1 and c["stylize_720p"]["torch_cpu_fps"] > 0
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line holds the headline alone (no extra legs or passes); --dump-outputs writes the last timed
+    step's outputs as float32 .npy files."""
+    d = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                          "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str)):
+        assert isinstance(r[k], t), (k, r[k])
+    assert r["steps"] == 3 and r["warmup"] == 2 and r["unit"] == "images/sec" and r["dtype"] == "f32" and r["higher_is_better"] is True
+    assert abs(r["value"] - 32 * 3 / (r["ms_per_step"] * 3e-3)) / r["value"] < 1e-2
+    assert not set(r) & {"roofline", "gram", "train_b4_per_gpu", "stylize_720p", "cpu_baseline"}
+    n = 424102
+    shapes = {"losses": (4,), "params": (n,), "grads": (n,), "adam_m": (n,), "adam_v": (n,)}
+    assert sorted(os.listdir(str(d))) == sorted(k + ".npy" for k in shapes)
+    total = 0
+    for k, shp in shapes.items():
+        a = np.load(str(d / (k + ".npy")))
+        assert a.dtype == np.float32 and a.shape == shp and np.isfinite(a).all(), k
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert abs(float(np.load(str(d / "losses.npy"))[0]) - r["final_loss"]) <= 1e-6 * abs(r["final_loss"])
+
+
+def test_bench_options_plain_by_default(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "1"])
+    a = bench.parse()
+    assert a.steps == 7 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "o"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "o"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_launch_command_is_the_drivers_form():
     import bench
     cmd = bench.launch_cmd(8, ["--gpus", "8", "--steps", "5", "--launch"], 29511)
@@ -79,7 +121,7 @@ def test_bench_self_launch_world1_rccl():
     """The self-launch path on the one GPU a test box has: `bench.py --gpus 1 --launch` -> torch.distributed.run with one
     rank -> RCCL process group, the all-reduce inside the step, per-rank values in the line."""
     env = dict((k, v) for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"))
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--launch", "--steps", "3", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--launch", "--steps", "3", "--warmup", "2", "--full",
                           "--no-cpu-baseline", "--no-stylize", "--b4-steps", "4", "--profile-steps", "1"], cwd=ROOT,
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -25,7 +25,7 @@ def _env():
 
 @pytest.mark.gpu
 def test_bench_full_path_two_ranks_sharing_the_gpu():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full",
                           "--b4-steps", "4", "--profile-steps", "1", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True,
                          timeout=1500, env=_env())
     assert out.returncode == 0, out.stderr[-4000:]

@@ -62,7 +62,7 @@ def test_bench_under_torchrun_one_process():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-           "--no-cpu-baseline", "--no-stylize", "--b4-steps", "4", "--profile-steps", "1"]
+           "--full", "--no-cpu-baseline", "--no-stylize", "--b4-steps", "4", "--profile-steps", "1"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

@@ -24,7 +24,7 @@ O=$R/gpurun_out/ab
 rm -rf "$O" && mkdir -p "$O"
 for L in new base new2 base2; do
   if [ "${L:0:4}" = base ]; then export FASTSTYLE_HIP_LIB=$R/exp/libbase.so; else unset FASTSTYLE_HIP_LIB; fi
-  timeout 400 python "$R/bench.py" --no-cpu-baseline --steps 30 --b4-steps 100 > "$O/bench_$L.json" 2> "$O/bench_$L.err"
+  timeout 400 python "$R/bench.py" --full --no-cpu-baseline --steps 30 --b4-steps 100 > "$O/bench_$L.json" 2> "$O/bench_$L.err"
 done
 python - "$O" <<'PY'
 import json, sys

@@ -18,9 +18,9 @@ PY
 }
 for W in "$@"; do
   case $W in
-    b32) timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats_b32 --output-format csv -- python $R/bench.py --no-cpu-baseline --no-stylize --no-b4 --steps 30 > $O/bench_b32_under_rocprofv3.json 2> $O/bench_b32_stderr.txt
+    b32) timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats_b32 --output-format csv -- python $R/bench.py --full --no-cpu-baseline --no-stylize --no-b4 --steps 30 > $O/bench_b32_under_rocprofv3.json 2> $O/bench_b32_stderr.txt
          stats_table $O/stats_b32 $O/kernel_stats_b32.txt; rm -rf $O/stats_b32;;
-    b4)  timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats_b4 --output-format csv -- python $R/bench.py --no-cpu-baseline --no-stylize --no-b4 --batch-per-gpu 4 --steps 100 > $O/bench_b4_under_rocprofv3.json 2> $O/bench_b4_stderr.txt
+    b4)  timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats_b4 --output-format csv -- python $R/bench.py --full --no-cpu-baseline --no-stylize --no-b4 --batch-per-gpu 4 --steps 100 > $O/bench_b4_under_rocprofv3.json 2> $O/bench_b4_stderr.txt
          stats_table $O/stats_b4 $O/kernel_stats_b4.txt; rm -rf $O/stats_b4;;
     720p) timeout 200 rocprofv3 --kernel-trace --stats -d $O/stats_720p --output-format csv -- python $R/tools/fwd720.py 720 1280 1 fp32 > $O/fwd_720p.log 2>&1
          stats_table $O/stats_720p $O/kernel_stats_720p_b1_fp32.txt; rm -rf $O/stats_720p;;
