@@ -80,6 +80,8 @@ PROTOTYPES = {
     "fs_ctx_set_stream": (c_int, [c_void_p, c_void_p]),
     "fs_last_error": (c_char_p, []),
     "fs_version": (c_char_p, []),
+    "fs_debug_reload_env": (None, []),            # tests / tuning scripts only
+    "fs_debug_knob": (c_int, [c_int, POINTER(c_char_p), POINTER(c_int), POINTER(c_int)]),
     "fs_profile_begin": (c_int, [c_void_p]),
     "fs_profile_family_name": (c_char_p, [c_int]),
     "fs_profile_end": (c_int, [c_void_p, POINTER(ctypes.c_double * (3 * FS_PROFILE_FAMILIES))]),
@@ -169,8 +171,6 @@ def bind(cdll):
         fn.argtypes = args
     if missing:
         raise FaststyleError("shared library lacks C-ABI symbols: %s" % ", ".join(missing))
-    cdll.fs_debug_reload_env.restype = None       # tests / tuning scripts only (not declared in include/*.h)
-    cdll.fs_debug_reload_env.argtypes = []
     return cdll
 
 

@@ -7,7 +7,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
-#include <mutex>
 
 #include "fs_bf16.h"
 #include "fs_tnet.h"
@@ -57,33 +56,31 @@ static int fail(int code, const char* fmt, ...) {
 
 namespace fs {
 namespace {
-struct TuneEntry {
-    char name[48];
-    bool present;
-    int val;
+// the knob table of fs_knobs.h as arrays, and one slot per row
+#define FS_KNOB_NAME_ROW(id, dflt, doc) FS_KNOB_NAME(id),
+#define FS_KNOB_DEFAULT_ROW(id, dflt, doc) (dflt),
+const char* const kKnobName[K_COUNT] = {FS_KNOBS(FS_KNOB_NAME_ROW)};
+const int kKnobDefault[K_COUNT] = {FS_KNOBS(FS_KNOB_DEFAULT_ROW)};
+#undef FS_KNOB_NAME_ROW
+#undef FS_KNOB_DEFAULT_ROW
+struct KnobSlot {
+    std::atomic<bool> read{false};
+    std::atomic<int> val{0};
 };
-TuneEntry g_tune[64];
-int g_ntune = 0;
-std::mutex g_tune_mu;
+KnobSlot g_knob[K_COUNT];
 }  // namespace
-int tune_int(const char* name, int unset) {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    for (int i = 0; i < g_ntune; ++i)
-        if (!strcmp(g_tune[i].name, name)) return g_tune[i].present ? g_tune[i].val : unset;
-    const char* v = getenv(name);
-    if (g_ntune < 64) {
-        TuneEntry& e = g_tune[g_ntune++];
-        strncpy(e.name, name, sizeof(e.name) - 1);
-        e.name[sizeof(e.name) - 1] = 0;
-        e.present = v != nullptr;
-        e.val = v ? (int)strtol(v, nullptr, 0) : 0;
-    }
-    return v ? (int)strtol(v, nullptr, 0) : unset;
+int knob(Knob k) {
+    KnobSlot& e = g_knob[k];
+    if (e.read.load(std::memory_order_acquire)) return e.val.load(std::memory_order_relaxed);
+    const char* v = getenv(kKnobName[k]);
+    const int x = v ? (int)strtol(v, nullptr, 0) : kKnobDefault[k];
+    e.val.store(x, std::memory_order_relaxed);
+    e.read.store(true, std::memory_order_release);
+    return x;
 }
 static std::atomic<unsigned> g_tune_epoch{1};
 void tune_reload() {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    g_ntune = 0;
+    for (KnobSlot& e : g_knob) e.read.store(false, std::memory_order_release);
     g_tune_epoch.fetch_add(1);
 }
 unsigned tune_epoch() { return g_tune_epoch.load(); }
@@ -124,6 +121,13 @@ int fs_f32_to_u8(fs_ctx* ctx, const float* src, size_t npix, int swap_rb, unsign
 
 // tests / tuning scripts: re-read the FS_* knobs after changing the environment (not part of the product ABI)
 void fs_debug_reload_env(void) { fs::tune_reload(); }
+int fs_debug_knob(int i, const char** name, int* dflt, int* value) {
+    if (i < 0 || i >= fs::K_COUNT) return -1;
+    if (name) *name = fs::kKnobName[i];
+    if (dflt) *dflt = fs::kKnobDefault[i];
+    if (value) *value = fs::knob((fs::Knob)i);
+    return 0;
+}
 const char* fs_last_error(void) { return g_err; }
 const char* fs_version(void) { return "faststyle_hip 0.1 (gfx950, fp32 + split-bf16 MFMA)"; }
 
@@ -136,7 +140,7 @@ int fs_ctx_create(int device, void* hip_stream, fs_ctx** out) {
     c->tnet_valid = false;
     c->btnet = nullptr;
     c->have_side = false;
-    if (!fs::tune_int("FS_NO_SIDE_STREAM", 0) && hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) == hipSuccess) {
+    if (!fs::knob(fs::K_NO_SIDE_STREAM) && hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) == hipSuccess) {
         c->have_side = true;
         for (int i = 0; i < 34; ++i)
             if (hipEventCreateWithFlags(&c->ev[i], hipEventDisableTiming) != hipSuccess) c->have_side = false;
@@ -245,7 +249,7 @@ int fs_tnet_forward(fs_ctx* ctx, const float* params, const float* x, int N, int
     if (ws_bytes < L->total_floats * sizeof(float))
         return fail(-3, "fs_tnet_forward: workspace too small (%zu < %zu bytes)", ws_bytes, L->total_floats * sizeof(float));
     const bool reuse = (flags & FS_FLAG_PARAMS_FROZEN) && ctx->fwd_params == params && ctx->fwd_ws == ws && ctx->fwd_serial == ctx->tnet_serial;
-    const bool with_bwd = (flags & FS_FLAG_SAVE_FOR_BWD) && !reuse && fs::tune_int("FS_TNET_BWD_FILTERS_IN_FWD", 1);
+    const bool with_bwd = (flags & FS_FLAG_SAVE_FOR_BWD) && !reuse && fs::knob(fs::K_TNET_BWD_FILTERS_IN_FWD);
     const int rc = fs::tnet_forward(*L, params, x, y, (float*)ws, ctx->stream, reuse, with_bwd);
     if (rc) {
         ctx->fwd_params = nullptr;

@@ -560,14 +560,14 @@ const BsInst kBs[7] = {{32, 16, 3, 3, 2, 1}, {64, 32, 3, 3, 2, 1}, {64, 64, 3, 3
 }  // namespace
 
 int bstream_instance(const ConvBArgs& a) {
-    if (!tune_int("FS_BSTREAM", 1) || a.y_f32) return 0;
+    if (!knob(K_BSTREAM) || a.y_f32) return 0;
     const bool image = a.Cin == 3;
     if (image ? (!a.x_f32 || (a.src_mode != SRC_REFLECT && a.src_mode != SRC_PLAIN) || a.Cout > 32) : (a.x_f32 || a.src_mode != SRC_PLAIN)) return 0;
     const int dil = a.dil_x > 0 ? a.dil_x : 1;
     const int bn = a.Cout > 32 ? 64 : 32;
     for (int i = 0; i < 7; ++i)
         if (a.Cin == kBs[i].Cin && a.KH == kBs[i].KH && a.KW == kBs[i].KW && a.stride == kBs[i].stride && dil == kBs[i].dil && bn == kBs[i].BN) {
-            if (!((tune_int("FS_BSTREAM_MASK", 127) >> i) & 1)) return 0;
+            if (!((knob(K_BSTREAM_MASK) >> i) & 1)) return 0;
             if (a.Cout % 8 || (a.shuffle && ((a.Cout >> 2) % 8 || a.Cout % 4))) return 0;   // 16-byte output granules
             if (a.in_a && !a.in_b) return 0;
             return i + 1;
@@ -612,7 +612,7 @@ int bstream_launch(const ConvBArgs& a_in, hipStream_t s) {
     const ConvBPlan& p = a.p;
     if (p.lds_bytes > 160 * 1024) return -2;
     const long total = (long)a.N * p.tiles_y * p.tiles_x;
-    const int wgs = p.BN == 32 ? tune_int("FS_BSTREAM_WGS", 512) : tune_int("FS_BSTREAM_WGS64", 256);
+    const int wgs = p.BN == 32 ? knob(K_BSTREAM_WGS) : knob(K_BSTREAM_WGS64);
     const int ny = p.cout_pad / p.BN;
     long gx = wgs / ny;   // persistent workgroups over both grid dimensions: two per CU where 256 registers allow it, else two rounds of one
     if (gx < 1) gx = 1;

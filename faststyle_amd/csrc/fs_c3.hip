@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void conv3x3_to3_kernel(const float* __restric
 bool conv3x3_to3_eligible(const ConvArgs& a) {
     return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad_t == 1 && a.pad_l == 1 && a.Cout == 3 && a.Cin == 64 && a.Ho == a.H &&
            a.Wo == a.W && a.src_mode == SRC_PLAIN && !a.in_a && !a.bias && !a.out_relu && !a.shuffle && !a.stats && !a.add_src &&
-           !a.mask_src && a.w_nstride == 0 && (a.dil_x <= 1) && tune_int("FS_C3_VALU", 1) != 0;
+           !a.mask_src && a.w_nstride == 0 && (a.dil_x <= 1) && knob(K_C3_VALU) != 0;
 }
 
 int conv3x3_to3_launch(const ConvArgs& a, hipStream_t s) {

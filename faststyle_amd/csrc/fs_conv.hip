@@ -857,8 +857,6 @@ Profiler::~Profiler() {
     free(recs);
 }
 
-static int env_int(const char* name, int dflt) { return tune_int(name, dflt); }
-
 void plan_tile(int Ho, int Wo, int KH, int KW, int stride, int max_px, int* TH, int* TW) {
     double best = -1;
     int bth = 1, btw = 1;
@@ -895,7 +893,7 @@ static void plan_variant(const ConvArgs& a, int variant, ConvPlan* out) {
     p.BN = kVarMT[variant] * kVarWN[variant];
     const int max_px = 4 * kVarWM[variant] * kVarMT[variant];
     const int kstep = kVarMT[variant] == 16 ? 4 : 2;
-    const int budget = env_int("FS_CONV_LDS_KB", 36) * 1024;  // per pipeline stage (two stages + affine table)
+    const int budget = knob(K_CONV_LDS_KB) * 1024;  // per pipeline stage (two stages + affine table)
     for (int px = max_px; px >= 16; px >>= 1) {  // shrink the pixel tile until a channel chunk fits
         plan_tile(a.Ho, a.Wo, a.KH, a.KW, a.stride, px, &p.TH, &p.TW);
         p.tiles_y = cdiv(a.Ho, p.TH);
@@ -911,7 +909,7 @@ static void plan_variant(const ConvArgs& a, int variant, ConvPlan* out) {
             break;
         }
         const int G = a.KH * a.KW;
-        const int forced = env_int("FS_CONV_CC", 0);
+        const int forced = knob(K_CONV_CC);
         int chosen = 0, chosen_bytes = 0;
         for (int cc = 32; cc >= 4; cc >>= 1) {
             if (a.Cin % cc) continue;
@@ -933,8 +931,8 @@ static void plan_variant(const ConvArgs& a, int variant, ConvPlan* out) {
     }
     if (p.lds_bytes < 4 * 9 * p.BN) p.lds_bytes = 4 * 9 * p.BN;  // stats scratch
     p.ksplit = 1;
-    p.xcd_swizzle = env_int("FS_CONV_XCD", 1);
-    p.skew = env_int("FS_CONV_SKEW", 0);
+    p.xcd_swizzle = knob(K_CONV_XCD);
+    p.skew = knob(K_CONV_SKEW);
     *out = p;
 }
 
@@ -960,7 +958,7 @@ ConvPlan conv_plan(const ConvArgs& a) {
     {   // the specialised families, in the table's order (first taker wins)
         int nf = 0;
         const ConvFamily* fam = conv_families(&nf);
-        const bool wino_on = env_int("FS_CONV_WINO", 1) != 0;
+        const bool wino_on = knob(K_CONV_WINO) != 0;
         for (int i = 0; i < nf; ++i)
             if ((wino_on || !fam[i].winograd) && fam[i].eligible(a)) {
                 fam[i].plan(a, &p);
@@ -973,8 +971,8 @@ ConvPlan conv_plan(const ConvArgs& a) {
     }
     // widest tile first; halve the workgroup tile while the launch cannot fill the chip
     // (256 CUs x >= 2 workgroups), e.g. VGG conv4_x at batch 4 or the 64-channel residual convs
-    const int min_wgs = env_int("FS_CONV_MIN_WGS", 512);
-    const int forced_variant = env_int("FS_CONV_VARIANT", -1);  // tuning aid (tools/micro_conv.py)
+    const int min_wgs = knob(K_CONV_MIN_WGS);
+    const int forced_variant = knob(K_CONV_VARIANT);  // tuning aid (tools/micro_conv.py)
     if (forced_variant >= 0 && forced_variant <= 4 && forced_variant != 2) {
         plan_variant(a, forced_variant, &p);
         return p;
@@ -983,9 +981,9 @@ ConvPlan conv_plan(const ConvArgs& a) {
     // the chip with wide tiles; the narrow tiles that do fill it move twice the bytes per FLOP through LDS.
     // With scratch available, keep the wide tile and split the input-channel chunks over blockIdx.z instead;
     // a streaming epilogue kernel sums the partials and applies bias / ReLU / tap-add / mask.
-    const int max_split = env_int("FS_CONV_KSPLIT", 4);
+    const int max_split = knob(K_CONV_KSPLIT);
     if (a.split_ws && max_split > 1 && a.Cout > 32 && !a.stats && !a.shuffle && !a.add_pad && a.w_nstride == 0) {
-        const int force = env_int("FS_CONV_FORCE_KSPLIT", 0);  // test hook: split regardless of the grid size
+        const int force = knob(K_CONV_FORCE_KSPLIT);  // test hook: split regardless of the grid size
         if (force > 1) {
             plan_variant(a, 0, &p);
             const int nchunks = p.CC > 0 ? a.Cin / p.CC : 0;
@@ -1002,7 +1000,7 @@ ConvPlan conv_plan(const ConvArgs& a) {
             const long wgs = (long)a.N * p.tiles_y * p.tiles_x * cdiv(a.Cout, p.BN);
             const int nchunks = a.Cin / p.CC;
             int ks = (int)((min_wgs + wgs - 1) / wgs);
-            if (i == 0 && wgs * env_int("FS_CONV_KSPLIT_FILL", 4) > min_wgs) break;  // the plain variants already come close: not worth the extra pass
+            if (i == 0 && wgs * knob(K_CONV_KSPLIT_FILL) > min_wgs) break;  // the plain variants already come close: not worth the extra pass
             if (ks > max_split) ks = max_split;
             while (ks > 1 && (nchunks / ks) * p.CC * a.KH * a.KW < 1024) --ks;  // keep >= 1024 of K per split
             if (ks > 1 && wgs * ks >= min_wgs && (size_t)ks * a.N * a.Ho * a.Wo * a.Cout <= a.split_ws_floats) {
@@ -1083,7 +1081,7 @@ bool conv_route_ok(const ConvArgs& a) {
 
 int conv_launch(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
-    if (env_int("FS_CONV_DEBUG", 0))  // tuning aid: one line per launch with the chosen plan
+    if (knob(K_CONV_DEBUG))  // tuning aid: one line per launch with the chosen plan
         fprintf(stderr, "conv N%d %dx%dx%d -> %dx%dx%d k%dx%d s%d src%d: variant %d tile %dx%d (patch %dx%d) CC %d ksplit %d rem %d/%d lds %d wgs %d\n",
                 a.N, a.H, a.W, a.Cin, a.Ho, a.Wo, a.Cout, a.KH, a.KW, a.stride, a.src_mode, a.p.variant, a.p.TH, a.p.TW, a.p.PH,
                 a.p.PW, a.p.CC, a.p.ksplit, a.p.rem_full, a.p.rem_ks, a.p.lds_bytes, a.N * a.p.tiles_y * a.p.tiles_x * cdiv(a.Cout, a.p.BN));

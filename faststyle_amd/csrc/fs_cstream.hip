@@ -1160,16 +1160,16 @@ static int cstream_instance(const ConvArgs& a) {
 }
 
 // FS_CSTREAM_SPLIT (default 1): instances 1-4 on the bf16 matrix cores as six exact bf16-piece products (the X6 form of the kernel); 0: fp32 matrix instructions
-static bool cstream_split_on() { return tune_int("FS_CSTREAM_SPLIT", 1) != 0; }
+static bool cstream_split_on() { return knob(K_CSTREAM_SPLIT) != 0; }
 
 bool cstream_eligible(const ConvArgs& a) {
     const int inst = cstream_instance(a);
-    if (!tune_int("FS_CSTREAM", 1) || !inst) return false;
+    if (!knob(K_CSTREAM) || !inst) return false;
     // bit i enables instance i+1.  Instance 5 (residual convs on small grids) is OFF by default: measured +1 % at batch 4
     // (20 launches 0.68 -> 0.63 ms) for 509 registers, and it would make the kernel choice of the residual convs depend on the
     // batch size (the data-parallel identity grads(batch) = sum grads(sample) then only holds to rounding-order noise)
-    const bool r64x = inst == 5 && (a.res_x6 || tune_int("FS_CSTREAM_R64X_ALL", 0)) && cstream_split_on() && !a.add_src && !a.fin.counter && !a.shuffle;   // the forward residual convs, split-bf16 direct form (conv_r64x_kernel)
-    if (!r64x && !((tune_int("FS_CSTREAM_MASK", 15) >> (inst - 1)) & 1)) return false;
+    const bool r64x = inst == 5 && (a.res_x6 || knob(K_CSTREAM_R64X_ALL)) && cstream_split_on() && !a.add_src && !a.fin.counter && !a.shuffle;   // the forward residual convs, split-bf16 direct form (conv_r64x_kernel)
+    if (!r64x && !((knob(K_CSTREAM_MASK) >> (inst - 1)) & 1)) return false;
     const bool plain = a.src_mode == SRC_PLAIN && a.dil_x <= 1 && !a.bias && !a.out_relu && !a.mask_src && !a.route_src &&
                        !a.pool_out && a.w_nstride == 0 && !a.w_wino && !a.w_wino2;
     if (!plain) return false;
@@ -1180,7 +1180,7 @@ bool cstream_eligible(const ConvArgs& a) {
     // measured at batch 4 (256x256: 100-500 tiles, at most two per workgroup): still ahead of the one-tile kernel -- the
     // resident filter and the cheap addresses count even without a second tile to prefetch; tiny launches stay with it
     const long tiles = (long)a.N * cdiv(a.Ho, kInst[inst - 1].TH) * cdiv(a.Wo, kTW);
-    return tiles >= tune_int("FS_CSTREAM_MIN_TILES", 64);
+    return tiles >= knob(K_CSTREAM_MIN_TILES);
 }
 
 void cstream_plan(const ConvArgs& a, ConvPlan* out) {
@@ -1199,11 +1199,11 @@ void cstream_plan(const ConvArgs& a, ConvPlan* out) {
     p.S = a.Cin + 1;
     p.ksplit = 1;
     int patch_floats = (p.PH * p.PW * p.S + 4 + 3) & ~3;
-    if (inst == 5 && (a.res_x6 || tune_int("FS_CSTREAM_R64X_ALL", 0)) && cstream_split_on() && !a.add_src && !a.fin.counter && !a.shuffle) {   // conv_r64x_kernel: eight 8-channel planes of (pixels + 1) x 48 bytes, each rounded up to 256
+    if (inst == 5 && (a.res_x6 || knob(K_CSTREAM_R64X_ALL)) && cstream_split_on() && !a.add_src && !a.fin.counter && !a.shuffle) {   // conv_r64x_kernel: eight 8-channel planes of (pixels + 1) x 48 bytes, each rounded up to 256
         p.S = 48;
         patch_floats = 8 * ((((p.PH * p.PW + 1) * 48) + 255) & ~255) / 4;
         p.flat = 1;
-        if (a.pad_t == 0 && a.pad_l == 0 && tune_int("FS_R64X_PIPE", 1)) {   // VALID: conv_r64p_kernel, the next tile's staging threaded into the sweep over a second patch buffer
+        if (a.pad_t == 0 && a.pad_l == 0 && knob(K_R64X_PIPE)) {   // VALID: conv_r64p_kernel, the next tile's staging threaded into the sweep over a second patch buffer
             p.S = 49;
             patch_floats *= 2;
         }
@@ -1228,7 +1228,7 @@ static void cs_launch(const ConvArgs& a, unsigned grid, hipStream_t s) {
 int cstream_launch(const ConvArgs& a, hipStream_t s) {
     const ConvPlan& p = a.p;
     const long total = (long)a.N * p.tiles_y * p.tiles_x;
-    const int wgs = tune_int("FS_CSTREAM_WGS", 256);
+    const int wgs = knob(K_CSTREAM_WGS);
     const unsigned grid = (unsigned)(total < wgs ? total : wgs);
     if (p.flat) {   // the split-bf16 form
         switch (cstream_instance(a)) {

@@ -151,7 +151,7 @@ int in_finalize(const float* stats, int N, int T, int C, int groups, const float
                 float* mean, float* rstd, float* a, float* b, hipStream_t s, float* scratch) {
     const int Cv = C * groups;
     // (tests lower FS_FINALIZE_MIN_T so small images take the two-level path)
-    const int min_t = tune_int("FS_FINALIZE_MIN_T", 16 * kFinalizeSplit);  // 1024 tiles: 720p and up; training sizes stay single-level
+    const int min_t = knob(K_FINALIZE_MIN_T);  // 1024 tiles: 720p and up; training sizes stay single-level
     if (scratch && T * groups > min_t && T > kFinalizeSplit && Cv <= 256) {  // scratch: N * kFinalizeSplit * Cv * 3 floats
         hipLaunchKernelGGL(in_prereduce_kernel, dim3(kFinalizeSplit, N), dim3(256), 0, s, stats, T, Cv, kFinalizeSplit, scratch);
         stats = scratch;
@@ -861,7 +861,7 @@ static int in_bwd_chunk_px(int N, int HW) {
     // twice the partial records for the final reduction)
     int chunk_px = cdiv(HW * N, 2048);
     if (chunk_px < 128) chunk_px = 128;
-    const int v = tune_int("FS_INBWD_CHUNK", 0);   // tuning aid: pixels per partial-sum block (multiples of 64 only: the scratch is sized for 64)
+    const int v = knob(K_INBWD_CHUNK);   // tuning aid: pixels per partial-sum block (multiples of 64 only: the scratch is sized for 64)
     if (v >= 64) chunk_px = v;
     return chunk_px;
 }
@@ -871,15 +871,15 @@ static int in_bwd_chunk_px(int N, int HW) {
 // come from in_bwd_params over S_out.
 int in_bwd_rec(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
                float* dz, const float* rec, int T, float* S_out, float* scratch, int N, int HW, int C, hipStream_t s) {
-    if (C > 256 || C % 4 || (size_t)HW * C >= ((size_t)1 << 31) || !tune_int("FS_INBWD_REC", 1)) return 1;
+    if (C > 256 || C % 4 || (size_t)HW * C >= ((size_t)1 << 31) || !knob(K_INBWD_REC)) return 1;
     if (!rec) {
         // a coarser chunking than in_bwd's where needed (the prologue of every apply workgroup reads ALL of its sample's records): <= max_t
         // chunks per sample
-        const int max_t = tune_int("FS_INBWD_REC_MAXT", 192);   // (96 / 192 / 384 measured: 225 / 217 / 217 us on the largest unit at batch 32, tools/micro_inbwd.py)
+        const int max_t = knob(K_INBWD_REC_MAXT);   // (96 / 192 / 384 measured: 225 / 217 / 217 us on the largest unit at batch 32, tools/micro_inbwd.py)
         int chunk_px = in_bwd_chunk_px(N, HW);
         if (cdiv(HW, chunk_px) > max_t) chunk_px = cdiv(cdiv(HW, max_t), 64) * 64;
         const int chunks = cdiv(HW, chunk_px);
-        if (tune_int("FS_INBWD_PUNR", 8) >= 8)   // (16 loads of 16 bytes in flight per thread: the pass is latency-bound per workgroup)
+        if (knob(K_INBWD_PUNR) >= 8)   // (16 loads of 16 bytes in flight per thread: the pass is latency-bound per workgroup)
             hipLaunchKernelGGL(in_bwd_partial4_kernel<8>, dim3(chunks, N), dim3(256), 0, s, gin, z, mean, rstd, a, b, mode, scratch, HW, C, chunk_px);
         else
             hipLaunchKernelGGL(in_bwd_partial4_kernel<4>, dim3(chunks, N), dim3(256), 0, s, gin, z, mean, rstd, a, b, mode, scratch, HW, C, chunk_px);
@@ -888,7 +888,7 @@ int in_bwd_rec(const float* gin, const float* z, const float* mean, const float*
     }
     const int per4 = (HW * C) >> 2;
     // ~1024 workgroups per launch (four per CU, all resident): each walks per4 / (1024 / N) float4 of its sample in pipelined batches of 1024
-    int bps = tune_int("FS_INBWD_APPLY_WGS", 1024) / N;
+    int bps = knob(K_INBWD_APPLY_WGS) / N;
     if (bps < 1) bps = 1;
     int span4 = cdiv(cdiv(per4, bps), 1024) * 1024;
     if (span4 < 1024) span4 = 1024;

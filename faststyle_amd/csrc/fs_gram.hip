@@ -908,8 +908,8 @@ static bool gram2_shape(int N, int HW, int C, GramArgs* out) {
     a.pairs = a.groups * (a.groups + 1) / 2;
     // pixel ranges: enough items for ~3 waves of workgroups over the chip, at least ~4 staged tiles each
     int splits = 1;
-    const int target = tune_int("FS_GRAM2_ITEMS", 768);
-    const int min_px = tune_int("FS_GRAM2_MIN_TILES", 4) * (a.CG == 64 ? 256 : 64);   // (tests lower it: several ranges on small maps)
+    const int target = knob(K_GRAM2_ITEMS);
+    const int min_px = knob(K_GRAM2_MIN_TILES) * (a.CG == 64 ? 256 : 64);   // (tests lower it: several ranges on small maps)
     while ((long)N * a.pairs * splits < target && HW / (splits * 2) >= (min_px > 1 ? min_px : 1)) splits *= 2;
     a.splits = splits;
     *out = a;
@@ -918,7 +918,7 @@ static bool gram2_shape(int N, int HW, int C, GramArgs* out) {
 
 bool gram2_eligible(int N, int HW, int C) {
     GramArgs a;
-    return tune_int("FS_GRAM2", 1) != 0 && gram2_shape(N, HW, C, &a);
+    return knob(K_GRAM2) != 0 && gram2_shape(N, HW, C, &a);
 }
 
 size_t gram2_slab_floats(int N, int HW, int C) {
@@ -986,7 +986,7 @@ static int gram2_stream_impl(const GramArgs& a, int N, int HW, hipStream_t s) {
         static BigLds lds_attr;
         lds_attr.ensure(reinterpret_cast<const void*>(gram_stream_kernel<64>));
         hipLaunchKernelGGL(gram_stream_kernel<64>, dim3((unsigned)(N * a.pairs * a.splits)), dim3(256), lds, s, a);
-    } else if (tune_int("FS_GRAM_SPLIT", 1)) {   // six exact bf16-piece products (gram_streamx_kernel): two operands x three piece planes of 128 channels x 80 bytes
+    } else if (knob(K_GRAM_SPLIT)) {   // six exact bf16-piece products (gram_streamx_kernel): two operands x three piece planes of 128 channels x 80 bytes
         hipLaunchKernelGGL(gram_streamx_kernel, dim3((unsigned)(N * a.pairs * a.splits)), dim3(256), (size_t)(2 * 3 * 128 * 80), s, a);
     } else {
         static BigLds lds_attr;
@@ -999,7 +999,7 @@ static int gram2_stream_impl(const GramArgs& a, int N, int HW, hipStream_t s) {
 
 
 bool gram_bwd2_eligible(int N, int HW, int C) {
-    if (!tune_int("FS_GRAM_BWD2", 1) || N < 1 || HW < 1) return false;
+    if (!knob(K_GRAM_BWD2) || N < 1 || HW < 1) return false;
     if (!(C == 64 || C == 128 || C == 256)) return false;
     return (size_t)HW * C * 4 < 0x7F000000ull;   // 32-bit byte offsets inside one sample, with room for a tile of overshoot
 }
@@ -1022,7 +1022,7 @@ int gram_symmetrize(const float* dG, float* S, int N, int C, float scale, hipStr
 
 // the routed form (gram_bwd_kernel<.., RT = true>): whole tiles of two rows x TPX/2 columns
 bool gram_bwd2_route_eligible(int N, int H, int W, int C) {
-    if (!tune_int("FS_GRAM_ROUTE_FUSED", 1) || H < 2 || W < 2 || !gram_bwd2_eligible(N, H * W, C)) return false;
+    if (!knob(K_GRAM_ROUTE_FUSED) || H < 2 || W < 2 || !gram_bwd2_eligible(N, H * W, C)) return false;
     const int TW = C == 64 ? 128 : C == 128 ? 64 : 32;
     return !(H & 1) && W % TW == 0;
 }
@@ -1031,7 +1031,7 @@ bool gram_bwd2_route_eligible(int N, int H, int W, int C) {
 int gram_bwd2_route_grid(int N, int H, int W, int C) {
     const int NH = C > 128 ? C / 128 : 1, TPX = C == 64 ? 256 : C == 128 ? 128 : 64;
     const int tiles = (H / 2) * (W / (TPX / 2));
-    int wpg = tune_int("FS_GRAM_BWD2_WGS", 256) / (N * NH);
+    int wpg = knob(K_GRAM_BWD2_WGS) / (N * NH);
     if (wpg < 1) wpg = 1;
     if (wpg > tiles) wpg = tiles;
     return N * NH * wpg;
@@ -1059,13 +1059,13 @@ int gram_bwd2_launch(const float* F, const float* S, const float* add, float* dF
     a.C = C;
     const int NH = C > 128 ? C / 128 : 1, TPX = above ? (C == 64 ? 256 : C == 128 ? 128 : 64) : (C == 256 ? 128 : 256);   // (routed: half the pixels for C >= 128 -- the plain tile sizes spill with the routing pass's registers)
     const int tiles = above ? (HW / W / 2) * (W / (TPX / 2)) : cdiv(HW, TPX);
-    int wpg = tune_int("FS_GRAM_BWD2_WGS", 256) / (N * NH);
+    int wpg = knob(K_GRAM_BWD2_WGS) / (N * NH);
     if (wpg < 1) wpg = 1;
     if (wpg > tiles) wpg = tiles;
     a.wpg = wpg;
     const unsigned grid = (unsigned)(N * NH * wpg);
     const size_t lds = (size_t)TPX * (C + 1) * sizeof(float);
-    if (tune_int("FS_CONV_DEBUG", 0))
+    if (knob(K_CONV_DEBUG))
         fprintf(stderr, "gram_bwd2: N %d HW %d (W %d) C %d tile %d px%s%s, %d tiles / sample, %u workgroups\n", N, HW, W, C, TPX, above ? " + pool routing + mask" : "",
                 content ? " + content term" : (add ? " + addend" : ""), tiles, grid);
     Profiler* prof = Profiler::current();

@@ -8,6 +8,8 @@
 #include <mutex>
 #include <type_traits>
 
+#include "fs_knobs.h"
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int fs_u32x4 __attribute__((ext_vector_type(4)));   // payload type of raw_buffer_store_b128
@@ -588,12 +590,8 @@ bool wino_eligible(const ConvArgs& a);
 void wino_plan(const ConvArgs& a, ConvPlan* out);
 int wino_launch(const ConvArgs& a, hipStream_t s);
 void plan_tile(int Ho, int Wo, int KH, int KW, int stride, int max_px, int* TH, int* TW);
-// Tuning / debugging knobs come from the environment ONCE: the first lookup of a name reads and caches it,
-// so no launch or planning path calls getenv() afterwards.  fs_debug_reload_env() (tests) drops the cache.  `unset` is
-// returned when the variable is absent.  (fs_api.hip)
-int tune_int(const char* name, int unset);
-void tune_reload();
-unsigned tune_epoch();   // bumped by tune_reload: cached plans made under older knob values are stale
+// Tuning / debugging knobs: fs_knobs.h holds the one table of names and defaults and declares knob(), which reads the environment
+// once per knob, tune_reload() (fs_debug_reload_env: tests) and tune_epoch().
 // The Winograd generations are selected by ONE knob with ONE default, read through this accessor only (FS_WINO_V):
 //   1  fs_wino.hip    F(2x2), first kernel          2  + fs_wino2.hip / fs_wino2h.hip  F(2x2), second generation (Cin <= 128, half items)
 //   4  + fs_wino4.hip F(4x4), filter through LDS    5  + fs_wino4t.hip F(4x4), filter in registers (the fp32 default of every 3x3 stride-1 launch)
@@ -607,7 +605,7 @@ struct WinoGen {
     bool f4_reg() const { return v >= 5; }
     bool split_bf16() const { return v >= 6; }
 };
-inline WinoGen wino_gen() { return WinoGen{tune_int("FS_WINO_V", 6)}; }
+inline WinoGen wino_gen() { return WinoGen{knob(K_WINO_V)}; }
 // One row per specialised conv kernel family: conv_plan takes the first row whose eligible() accepts the launch, conv_launch finds the row of the
 // plan's variant again (and re-checks eligibility: a plan made for other arguments is refused with -7).  fs_conv.hip holds the table.
 struct ConvFamily {
@@ -629,7 +627,7 @@ inline bool fused_finalize_ok(int N, int C, int T, int groups) {
     // loads and no fence still +27 us (batch 4: transform-net forward 0.60 -> 0.98 ms; 720p 908 -> 708 fps) against the
     // 4.5 us in_finalize launch.  Kept behind the knob as a recorded experiment (tests/test_path_parity.py runs it on the
     // emulator so that it does not rot).
-    return tune_int("FS_FUSED_FINALIZE", 0) && (long)N * C * T * groups <= (long)tune_int("FS_FUSED_FINALIZE_MAX", 24576);
+    return knob(K_FUSED_FINALIZE) && (long)N * C * T * groups <= (long)knob(K_FUSED_FINALIZE_MAX);
 }
 
 // thread-local message behind fs_last_error(); returns `code` (fs_api.hip)

@@ -1005,11 +1005,11 @@ __global__ __launch_bounds__(256, 2) void conv_s16c3x_kernel(ConvArgs a) {
 
 // ------------------------------------------------------------------------------------------------------------ host
 // FS_S16_SPLIT (default 1): the folded output layer on the bf16 matrix cores as six exact bf16-piece products (conv_s16x_kernel); 0: fp32 matrix instructions
-static bool s16_split_on() { return tune_int("FS_S16_SPLIT", 1) != 0; }
+static bool s16_split_on() { return knob(K_S16_SPLIT) != 0; }
 static int s16_instance(const ConvArgs& a) {
     if (a.stride != 1) return 0;
     if (a.Cout == 64) {   // VGG16 conv1_1: 3 -> 64, 3x3 (mean on load, bias + ReLU)
-        return (a.Cin == 3 && a.KH == 3 && a.KW == 3 && a.dil_x <= 1 && a.src_mode == SRC_PLAIN && !a.in_relu && !a.stats && tune_int("FS_S16_VGG", 1)) ? 3 : 0;
+        return (a.Cin == 3 && a.KH == 3 && a.KW == 3 && a.dil_x <= 1 && a.src_mode == SRC_PLAIN && !a.in_relu && !a.stats && knob(K_S16_VGG)) ? 3 : 0;
     }
     if (a.Cout != 16 || a.bias || a.out_relu) return 0;
     if (a.Cin == 3 && a.KH == 9 && a.KW == 9 && a.dil_x <= 1 && (a.src_mode == SRC_PLAIN || a.src_mode == SRC_REFLECT) && !a.in_relu) return 1;
@@ -1019,13 +1019,13 @@ static int s16_instance(const ConvArgs& a) {
 
 bool s16_eligible(const ConvArgs& a) {
     const int inst = s16_instance(a);
-    if (!tune_int("FS_S16", 1) || !inst) return false;
+    if (!knob(K_S16) || !inst) return false;
     if (a.mask_src || a.route_src || a.pool_out || a.w_nstride || a.w_wino || a.w_wino2 || a.shuffle || a.add_src || a.fin.counter) return false;
     if (a.in_a && !a.in_b) return false;
     if (a.in_relu && !a.in_a) return false;
     if (a.pad_t < 0 || a.pad_l < 0) return false;
     const long tiles = (long)a.N * cdiv(a.Ho, kT) * cdiv(a.Wo, kT);
-    return tiles >= tune_int("FS_S16_MIN_TILES", 64);
+    return tiles >= knob(K_S16_MIN_TILES);
 }
 
 void s16_plan(const ConvArgs& a, ConvPlan* out) {
@@ -1059,7 +1059,7 @@ void s16_plan(const ConvArgs& a, ConvPlan* out) {
 int s16_launch(const ConvArgs& a, hipStream_t s) {
     const ConvPlan& p = a.p;
     const long total = (long)a.N * p.tiles_y * p.tiles_x;
-    const int wgs = tune_int("FS_S16_WGS", 512);
+    const int wgs = knob(K_S16_WGS);
     const unsigned grid = (unsigned)(total < wgs ? total : wgs);
     switch (s16_instance(a)) {
         case 1:

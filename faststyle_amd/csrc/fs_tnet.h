@@ -12,6 +12,19 @@ struct ParamInfo {
 };
 const ParamInfo* param_table();  // 48 entries, checkpoint key order
 
+// The kernel a residual conv (3x3 VALID, 64 -> 64: units 3..12) or its input gradient (the 3x3 'full' conv of dz) runs on; res_kernel() in
+// fs_tnet.hip decides it, once per layout.
+enum ResKernel : int {
+    RES_DIRECT = 0,  // conv_plan's pick among the direct kernels
+    RES_F2_V1,       // wino_conv_kernel: F(2x2), first generation (FS_WINO_V=1), 64-tile items
+    RES_F2,          // wino2_conv_kernel: F(2x2), second generation, 64-tile items (grids that fill the chip: 720p / 1080p frames)
+    RES_F2_HALF,     // wino2h_conv_kernel: half items (smaller grids)
+    RES_F4T,         // wino4t_conv_kernel: F(4x4,3x3), 16-tile items
+    RES_X6,          // conv_r64x_kernel: direct, split-bf16 (round 6), where the launch has few Winograd items
+};
+inline bool res_winograd(ResKernel k) { return k != RES_DIRECT && k != RES_X6; }
+inline size_t res_filter_floats(ResKernel k) { return (size_t)(k == RES_F4T ? 36 : 16) * 64 * 64; }   // its transformed filter
+
 // One conv + instance-norm unit of the net.
 struct Unit {
     int kind;  // 0: conv, 1: phase-collapsed resize-conv (2x2 taps, pixel-shuffle store),
@@ -30,10 +43,8 @@ struct Unit {
     int w_off, g_off, b_off;  // offsets into the flat parameter buffer
     size_t z, stats, mean, rstd, a, b;  // workspace offsets (floats)
     int tiles;
-    int wino;        // forward through a Winograd kernel: 1 wino(2)_conv_kernel (3x3 VALID residual convs on grids that fill the
-                     // chip with 64-tile items), 2 wino2h_conv_kernel (half items: smaller grids, batch 4 per GPU), 3 wino4t_conv_kernel (F(4x4,3x3))
-    int x6;          // forward through the split-bf16 direct kernel (conv_r64x_kernel, round 6): the residual convs wherever the launch has enough 8 x 16-pixel tiles
-    size_t wino_u;   // its transformed filter ([16][Cin][Cout]; 36 * Cin * Cout floats for 3) in the workspace
+    ResKernel res;   // the kernel of the forward (RES_DIRECT for every unit that is no residual conv)
+    size_t wino_u;   // the transformed filter of a Winograd one in the workspace (res_filter_floats)
     ConvPlan plan;
     WgradPlan wplan;
 };
@@ -52,8 +63,8 @@ struct TnetLayout {
     size_t wTu[16];   // per-unit input-gradient filters (flip+transpose / collapsed), all built by one wt_batch launch
     size_t dweff2;    // the collapsed filter gradient of the SECOND resize-conv unit (both units' reductions are pending at once since round 5)
     size_t g[3], dz[2], wT, dweff, inbwd, slabs;  // backward scratch (dz double-buffered: filter gradients run on a side stream)
-    size_t wino_d[10]; // Winograd-transformed input-gradient filters of the residual convs (0: direct kernel)
-    int wino_dh[10];   // ... 1: through the half-item kernel, 2: through the 16-tile F(4x4) kernel (fs_wino4t.hip)
+    ResKernel res_d[10]; // the kernel of each residual conv's input gradient
+    size_t wino_d[10];   // ... and its Winograd-transformed filter (0: direct kernel)
     size_t inb_rec;   // instance-norm-backward partial-sum records [N][items][64][2] written by the epilogue of a residual input-gradient launch
                       // (fs_wino4t_kernel.h EPI 5 / 6) for the unit below it; one buffer, consumed by that unit's in_bwd_rec right after
     size_t inb_S[16]; // per unit: the per-sample sums [N][Cout][2] in_bwd_rec leaves for in_bwd_params (dgamma / dbeta of all units in one launch)

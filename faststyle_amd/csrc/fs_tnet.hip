@@ -106,14 +106,84 @@ static ConvArgs unit_args(const Unit& u, int N) {
     a.shuffle = u.kind == 1;
     a.prof_tag = 1;
     a.tnet_plan = 1;
-    a.res_x6 = u.x6;
+    a.res_x6 = u.res == RES_X6;
     return a;
 }
 
 constexpr int kRemUnits = 256;   // at most one persistent grid of split units
 
 int tnet_wino_mode() {
-    return tune_int("FS_TNET_WINO", 1);
+    return knob(K_TNET_WINO);
+}
+
+// the input gradient of residual conv u: a 3x3 'full' conv of dz (the layout's probes and unit_dgrad's launch)
+static ConvArgs res_dgrad_args(const Unit& u, int N) {
+    ConvArgs a{};
+    a.prof_tag = 1;
+    a.tnet_plan = 1;   // (the planner keeps 16-tile F(4x4) items for the transform net)
+    a.N = N;
+    a.H = u.Hout;
+    a.W = u.Wout;
+    a.Cin = a.Cout = 64;
+    a.Ho = u.Hin;
+    a.Wo = u.Win;
+    a.KH = a.KW = 3;
+    a.stride = 1;
+    a.pad_t = a.pad_l = 2;
+    a.src_mode = SRC_PLAIN;
+    return a;
+}
+
+// the filter operand of a residual launch: U is the transformed filter of kernel k (unused by the direct kernels)
+static void res_set_filter(ConvArgs* a, ResKernel k, const float* U) {
+    a->w_wino = k == RES_F2_V1 ? U : nullptr;
+    a->w_wino2 = (k == RES_F2 || k == RES_F2_HALF) ? U : nullptr;
+    a->w_wino4t = k == RES_F4T ? U : nullptr;
+    a->half_items = k == RES_F2_HALF;
+}
+
+// THE policy: the kernel a residual conv (fwd; `shape` = unit_args) or its input gradient (`shape` = res_dgrad_args) runs on.  mode: FS_TNET_WINO
+// (0 no Winograd kernel, 2 forces one: tests).  Rule 1 ends the choice; of rules 2-4 a later one overrides an earlier one.
+//   1. FORWARD ONLY: the direct split-bf16 kernel where the fp32 Winograd kernel's 16 x 16-pixel items leave most of the chip idle -- batch 4 per GPU:
+//      100 items on 256 CUs against 200 tiles of 8 x 16 pixels; measured (same lease, profiles/r06_ab_r64x_residual_forward.txt) batch 4 3.22 -> 3.20 ms
+//      per step.  Where the items fill the chip the Winograd kernel is ahead (batch 32: ten forward launches 0.75 against 0.88 ms; 720p 1215 against
+//      1112 fps): per 8 x 16 tile the direct kernel's sweep is 15.7 k cycles at the full bf16 matrix rate, and issue + commit + epilogue add 10 k that
+//      one wave per SIMD cannot overlap (tools/r64x_trace.py).  FS_TNET_RES_X6: 0 never, 1 below FS_TNET_RES_X6_MAX_ITEMS items (129: less than half of
+//      the chip; a 720p frame has 240), 2 wherever the kernel takes the launch.
+//   2. F(2x2) with 64-tile items when the 16 x 16-pixel blocks fill the chip (>= 200: 720p / 1080p frames have 240-290 per image; at 256 x 256 batch 4
+//      they are 100 for 256 CUs), or mode 2.  The forward asks the kernels' eligibility and also takes the FIRST-GENERATION kernel (FS_WINO_V=1: forward
+//      only); the input gradient needs the second generation and does not ask.
+//   3. F(2x2) with half items (<= 32 tiles per item: twice the items) when rule 2 left the direct kernel and the launch has FS_WINO2H_MIN_ITEMS of
+//      them -- batch 4 per GPU: 100..144 items of 16 x 16 pixels, 180..252 half items.  Forced mode 2 skips it.
+//   4. the 16-tile F(4x4,3x3) kernel (fs_wino4t.hip: 36 products per 4 x 4 outputs instead of 64, filter operand global -> registers) wherever its items
+//      occupy a fair part of the chip (FS_WINO4T_MIN_ITEMS), or FS_TNET_WINO4=2: it overrides both F(2x2) forms.
+// (ADVICE.md finding 1 -- these probes are not the argument set of the launch, e.g. under FS_FUSED_FINALIZE=1 -- is to be fixed HERE.)
+static ResKernel res_kernel(const ConvArgs& shape, int mode, bool fwd) {
+    const float* const some = reinterpret_cast<const float*>(16);   // eligibility looks at the shapes only
+    const bool second = wino_gen().f2_second();
+    const long blocks = (long)shape.N * cdiv(shape.Ho, 16) * cdiv(shape.Wo, 16);   // = 64-tile F(2x2) items (Cout = 64)
+    ConvArgs a = shape;
+    if (fwd) a.stats = reinterpret_cast<float*>(16);   // a forward launch also leaves the instance-norm records
+    if (const int x6 = fwd ? knob(K_TNET_RES_X6) : 0) {
+        ConvArgs x = a;
+        x.res_x6 = 1;
+        if ((x6 == 2 || blocks < (long)knob(K_TNET_RES_X6_MAX_ITEMS)) && cstream_eligible(x)) return RES_X6;
+    }
+    ResKernel k = RES_DIRECT;
+    ConvArgs f2 = a;
+    f2.w_wino2 = some;
+    if (fwd) f2.w_wino = some;
+    if (mode && (mode == 2 || blocks >= 200) && (fwd ? wino_eligible(f2) || wino2_eligible(f2) : second)) k = second ? RES_F2 : RES_F2_V1;
+    if (k == RES_DIRECT && mode && mode != 2 && second && knob(K_TNET_WINO_HALF)) {
+        f2.half_items = 1;
+        if (wino2h_eligible(f2) && wino2h_items(f2) >= knob(K_WINO2H_MIN_ITEMS)) k = RES_F2_HALF;
+    }
+    if (const int w4 = mode ? knob(K_TNET_WINO4) : 0) {
+        ConvArgs t = a;
+        t.w_wino4t = some;
+        if (wino4t_eligible(t) && (w4 == 2 || wino4t_items(t) >= knob(K_WINO4T_MIN_ITEMS))) k = RES_F4T;
+    }
+    return k;
 }
 
 void tnet_layout(int N, int H, int W, int deconv, TnetLayout* L) {
@@ -243,59 +313,17 @@ void tnet_layout(int N, int H, int W, int deconv, TnetLayout* L) {
     for (int i = 0; i < 16; ++i) {
         Unit& u = L->u[i];
         ConvArgs a = unit_args(u, N);
-        // Residual convs (3x3 VALID, 64 -> 64) go through the Winograd kernel when its 16x16-pixel blocks fill the
-        // chip (720p / 1080p frames: 240-290 blocks per image); at 256x256 batch 4 they are 100 blocks for 256 CUs and
-        // the direct kernel stays.  FS_TNET_WINO=0 disables, =2 forces (tests).
-        u.wino = 0;
-        u.x6 = 0;
-        // (round 6) the residual convs as a direct convolution in six exact bf16-piece products (fs_cstream.hip: conv_r64x_kernel) where the fp32 Winograd
-        // kernel's 16 x 16-pixel items leave most of the chip idle -- batch 4 per GPU: 100 items on 256 CUs against 200 tiles of 8 x 16 pixels; measured
-        // (same lease, profiles/r06_ab_r64x_residual_forward.txt): batch 4 3.22 -> 3.20 ms per step.  Where the items fill the chip the Winograd kernel is
-        // ahead (batch 32: ten forward launches 0.75 against 0.88 ms; 720p 1215 against 1112 fps): per 8 x 16 tile the direct kernel's sweep is 15.7 k
-        // cycles at the full bf16 matrix rate, and issue + commit + epilogue add 10 k that one wave per SIMD cannot overlap (tools/r64x_trace.py).
-        // FS_TNET_RES_X6: 0 never, 1 (default) below FS_TNET_RES_X6_MAX_ITEMS Winograd items (129: less than half of the chip; a 720p frame has 240), 2 wherever the kernel takes the launch.
-        if (u.kind == 0 && i >= 3 && i <= 12 && tune_int("FS_TNET_RES_X6", 1)) {
-            const long w_items = (long)N * cdiv(u.Hc, 16) * cdiv(u.Wc, 16);
-            if (tune_int("FS_TNET_RES_X6", 1) == 2 || w_items < (long)tune_int("FS_TNET_RES_X6_MAX_ITEMS", 129)) {
-                a.res_x6 = 1;
-                a.stats = reinterpret_cast<float*>(16);
-                u.x6 = cstream_eligible(a) ? 1 : 0;
-                a.stats = nullptr;
-                a.res_x6 = u.x6;
-            }
+        if (i >= 3 && i <= 12) {
+            u.res = res_kernel(a, L->wino_mode, true);
+            a.res_x6 = u.res == RES_X6;
         }
-        if (!u.x6) {
-            const int mode = L->wino_mode;
-            a.w_wino = reinterpret_cast<const float*>(16);   // eligibility looks at the shapes only
-            a.w_wino2 = a.w_wino;
-            a.stats = reinterpret_cast<float*>(16);
-            const long blocks = (long)N * cdiv(u.Hc, 16) * cdiv(u.Wc, 16) * (u.Cc / 64 > 0 ? u.Cc / 64 : 1);
-            if (mode && u.kind == 0 && i >= 3 && i <= 12 && (wino_eligible(a) || wino2_eligible(a)) && (mode == 2 || blocks >= 200)) u.wino = 1;
-            // ... and through the half-item kernel (<= 32 tiles per item: twice the items) when 64-tile items leave most of
-            // the chip idle -- batch 4 per GPU: 100..144 items of 16x16 pixels, 180..252 half items
-            if (!u.wino && mode && mode != 2 && u.kind == 0 && i >= 3 && i <= 12 && wino_gen().f2_second() && tune_int("FS_TNET_WINO_HALF", 1)) {
-                ConvArgs h = a;
-                h.half_items = 1;
-                if (wino2h_eligible(h) && wino2h_items(h) >= tune_int("FS_WINO2H_MIN_ITEMS", 96)) u.wino = 2;
-            }
-            // ... and through the 16-tile Winograd F(4x4,3x3) kernel (fs_wino4t.hip: 36 products per 4x4 outputs instead of 64, filter
-            // operand global -> registers) wherever its items occupy a fair part of the chip.  FS_TNET_WINO4=0 disables, =2 forces.
-            const int w4 = tune_int("FS_TNET_WINO4", 1);
-            if (mode && w4 && u.kind == 0 && i >= 3 && i <= 12) {
-                ConvArgs t = a;
-                t.w_wino = t.w_wino2 = nullptr;
-                t.w_wino4t = reinterpret_cast<const float*>(16);
-                if (wino4t_eligible(t) && (w4 == 2 || wino4t_items(t) >= tune_int("FS_WINO4T_MIN_ITEMS", 64))) u.wino = 3;
-            }
-            if (!u.wino || u.wino == 3) a.w_wino = a.w_wino2 = nullptr;
-            if (u.wino == 3) a.w_wino4t = reinterpret_cast<const float*>(16);
-            a.stats = nullptr;
-        }
-        a.half_items = u.wino == 2;
-        a.rem_ws = reinterpret_cast<float*>(16);   // (planning looks at the capacity only)
+        const float* const some = reinterpret_cast<const float*>(16);   // (planning looks at which operands exist, and at the capacity below, only)
+        res_set_filter(&a, u.res, some);
+        if (a.w_wino || a.w_wino2) a.w_wino = a.w_wino2 = some;   // (the plan of an F(2x2) unit has always been made with both layouts present)
+        a.rem_ws = reinterpret_cast<float*>(16);
         a.rem_ws_floats = (size_t)kRemUnits * 16384;
         u.plan = conv_plan(a);
-        u.wino_u = u.wino ? b.take((size_t)(u.wino == 3 ? 36 : 16) * u.Cin * u.Cc) : 0;
+        u.wino_u = res_winograd(u.res) ? b.take(res_filter_floats(u.res)) : 0;
         u.tiles = u.kind == 2 ? cdiv(u.Hout * u.Wout, 256) : u.plan.tiles_y * u.plan.tiles_x;
         const size_t act = (size_t)N * u.Hout * u.Wout * u.Cout;
         u.z = b.take(act);
@@ -332,46 +360,9 @@ void tnet_layout(int N, int H, int W, int deconv, TnetLayout* L) {
                                                L->u[i].Cin * L->u[i].Cout);
     L->dweff = b.take(4 * 64 * 128);
     L->dweff2 = b.take(4 * 64 * 128);
-    for (int i = 3; i <= 12; ++i) {   // residual input gradients (3x3 'full' convs of dz) through the Winograd kernel when its blocks fill the chip
-        const Unit& u = L->u[i];
-        const long blocks = (long)N * cdiv(u.Hin, 16) * cdiv(u.Win, 16);
-        bool on = L->wino_mode && wino_gen().f2_second() && (L->wino_mode == 2 || blocks >= 200);
-        L->wino_dh[i - 3] = 0;
-        if (!on && L->wino_mode && L->wino_mode != 2 && wino_gen().f2_second() && tune_int("FS_TNET_WINO_HALF", 1)) {
-            ConvArgs h{};   // the 3x3 'full' conv of dz that unit_dgrad launches
-            h.N = N;
-            h.H = u.Hout;
-            h.W = u.Wout;
-            h.Cin = h.Cout = 64;
-            h.Ho = u.Hin;
-            h.Wo = u.Win;
-            h.KH = h.KW = 3;
-            h.stride = 1;
-            h.pad_t = h.pad_l = 2;
-            h.w_wino2 = reinterpret_cast<const float*>(16);
-            h.half_items = 1;
-            if (wino2h_eligible(h) && wino2h_items(h) >= tune_int("FS_WINO2H_MIN_ITEMS", 96)) on = L->wino_dh[i - 3] = 1;
-        }
-        if (const int w4 = L->wino_mode ? tune_int("FS_TNET_WINO4", 1) : 0) {   // the 16-tile F(4x4) kernel (see the forward units)
-            ConvArgs h{};   // the 3x3 'full' conv of dz that unit_dgrad launches
-            h.N = N;
-            h.H = u.Hout;
-            h.W = u.Wout;
-            h.Cin = h.Cout = 64;
-            h.Ho = u.Hin;
-            h.Wo = u.Win;
-            h.KH = h.KW = 3;
-            h.stride = 1;
-            h.pad_t = h.pad_l = 2;
-            h.prof_tag = 1;
-            h.tnet_plan = 1;   // (as unit_dgrad sets it: the planner keeps 16-tile items for the transform net)
-            h.w_wino4t = reinterpret_cast<const float*>(16);
-            if (wino4t_eligible(h) && (w4 == 2 || wino4t_items(h) >= tune_int("FS_WINO4T_MIN_ITEMS", 64))) {
-                on = true;
-                L->wino_dh[i - 3] = 2;
-            }
-        }
-        L->wino_d[i - 3] = on ? b.take((size_t)(L->wino_dh[i - 3] == 2 ? 36 : 16) * 64 * 64) : 0;
+    for (int i = 3; i <= 12; ++i) {   // residual input gradients
+        const ResKernel k = L->res_d[i - 3] = res_kernel(res_dgrad_args(L->u[i], N), L->wino_mode, false);
+        L->wino_d[i - 3] = res_winograd(k) ? b.take(res_filter_floats(k)) : 0;
     }
     L->inbwd = b.take(max_inbwd);
     {
@@ -398,7 +389,7 @@ void tnet_layout(int N, int H, int W, int deconv, TnetLayout* L) {
         WgradArgs probs[10];
         for (int i = 3; i <= 12; ++i) probs[i - 3] = unit_wgrad_args(L->u[i], N);
         Wg2Args w2;
-        const size_t f2 = tune_int("FS_TNET_WGRAD_BATCH", 1) ? wgrad2_plan(probs, 10, &w2) : 0;
+        const size_t f2 = knob(K_TNET_WGRAD_BATCH) ? wgrad2_plan(probs, 10, &w2) : 0;
         L->res_batch = f2 > 0;
         if (f2 > max_slab) max_slab = f2;
         WgwArgs ww;   // the Winograd filter-gradient kernel (fs_wgw.hip) takes the batch when it is eligible: its slabs are larger
@@ -468,7 +459,7 @@ static void bwd_filter_jobs(const TnetLayout& L, const float* params, float* ws,
     }
     for (int i = 3; i <= 12; ++i)   // ... and the Winograd transforms of the residual ones ([3][3][Cout][Cin] as the kernel's HWIO)
         if (L.wino_d[i - 3]) {
-            WinoBatch& t = L.wino_dh[i - 3] == 2 ? *nb4 : *nb;
+            WinoBatch& t = L.res_d[i - 3] == RES_F4T ? *nb4 : *nb;
             t.w[t.n] = ws + L.wTu[i];
             t.U[t.n] = ws + L.wino_d[i - 3];
             ++t.n;
@@ -488,11 +479,11 @@ int tnet_forward(const TnetLayout& L, const float* params, const float* x, float
         wb.add(WT_UPFWD, params + L.u[14].w_off, ws + L.weff[1], 3, 3, 32, 16);
         wb.add(WT_FOLD5FWD, params + L.u[15].w_off, ws + L.wfold, 9, 9, 16, 3);
     }
-    if (!reuse_filters) {   // Winograd-transformed filters of the residual convs that use wino_conv_kernel (one launch)
-        WinoBatch nb{}, nb4{}, nbd{};
+    if (!reuse_filters) {   // Winograd-transformed filters of the residual convs, one launch per layout (an empty batch launches nothing)
+        WinoBatch nb1{}, nb{}, nb4{}, nbd{};
         for (int i = 3; i <= 12; ++i)
-            if (L.u[i].wino) {
-                WinoBatch& t = L.u[i].wino == 3 ? nb4 : nb;   // (3: the register layout of fs_wino4t.hip)
+            if (res_winograd(L.u[i].res)) {
+                WinoBatch& t = L.u[i].res == RES_F4T ? nb4 : (L.u[i].res == RES_F2_V1 ? nb1 : nb);
                 t.w[t.n] = params + L.u[i].w_off;
                 t.U[t.n] = ws + L.u[i].wino_u;
                 ++t.n;
@@ -500,7 +491,8 @@ int tnet_forward(const TnetLayout& L, const float* params, const float* x, float
         // a training step: the backward's input-gradient filters ride in the same launches (two launches less per step)
         if (with_bwd_filters) bwd_filter_jobs(L, params, ws, &wb, &nbd, &nb4);
         FS_TRY(wt_batch(wb, s));
-        FS_TRY(wino_gen().f2_second() ? wt_wino2_batch(nb, 64, 64, s) : wt_wino_batch(nb, 64, 64, s));
+        FS_TRY(wt_wino_batch(nb1, 64, 64, s));
+        FS_TRY(wt_wino2_batch(nb, 64, 64, s));
         if (with_bwd_filters) FS_TRY(wt_wino2_batch(nbd, 64, 64, s));
         FS_TRY(wt_wino4t_batch(nb4, 64, 64, s));
     }
@@ -528,10 +520,7 @@ int tnet_forward(const TnetLayout& L, const float* params, const float* x, float
         a.in_nstride = src_a ? u.Cin : 0;
         a.in_relu = src_a ? 1 : 0;
         a.w = (u.kind == 1 || (u.kind == 3 && i < 15)) ? ws + L.weff[i - 13] : ((u.kind == 2 || u.kind == 3) ? ws + L.wfold : params + u.w_off);
-        a.w_wino = (u.wino && u.wino != 3 && !wino_gen().f2_second()) ? ws + u.wino_u : nullptr;
-        a.w_wino2 = (u.wino && u.wino != 3 && wino_gen().f2_second()) ? ws + u.wino_u : nullptr;
-        a.w_wino4t = u.wino == 3 ? ws + u.wino_u : nullptr;
-        a.half_items = u.wino == 2;
+        res_set_filter(&a, u.res, ws + u.wino_u);
         a.y = u.kind == 2 ? ws + L.zfold : ws + u.z;
         a.stats = u.kind == 2 ? nullptr : ws + u.stats;
         a.rem_ws = ws + L.rem_ws;
@@ -588,27 +577,24 @@ static int unit_dgrad(const TnetLayout& L, const Unit& u, const float* params, c
                       const float* add_src, float* ws, hipStream_t s, const Unit* below = nullptr, int below_relu = 0, int* rec_tiles = nullptr) {
     const int N = L.N;
     if (rec_tiles) *rec_tiles = 0;
+    const int ui = (int)(&u - L.u);
+    const bool res = ui >= 3 && ui <= 12;
     ConvArgs a{};
+    if (res) {
+        a = res_dgrad_args(u, N);
+        res_set_filter(&a, L.res_d[ui - 3], ws + L.wino_d[ui - 3]);
+    }
     a.prof_tag = 1;
     a.tnet_plan = 1;
     a.N = N;
     a.x = dz;
     a.y = dst;
-    a.w = ws + L.wTu[&u - L.u];  // built at the start of tnet_backward
-    {
-        const int ui = (int)(&u - L.u);
-        if (ui >= 3 && ui <= 12 && L.wino_d[ui - 3]) {
-            if (L.wino_dh[ui - 3] == 2) {
-                a.w_wino4t = ws + L.wino_d[ui - 3];
-            } else {
-                a.w_wino2 = ws + L.wino_d[ui - 3];
-                a.half_items = L.wino_dh[ui - 3];
-            }
-        }
-    }
+    a.w = ws + L.wTu[ui];  // built at the start of tnet_backward
     a.add_src = add_src;
     a.add_pad = add_src ? 2 : 0;
-    if (u.kind == 3) {  // adjoint of conv2d_transpose = the plain strided conv with the stored filter
+    if (res) {
+        // (described by res_dgrad_args)
+    } else if (u.kind == 3) {  // adjoint of conv2d_transpose = the plain strided conv with the stored filter
         a.w = params + u.w_off;
         a.H = u.Hout;
         a.W = u.Wout;
@@ -667,7 +653,7 @@ static int unit_dgrad(const TnetLayout& L, const Unit& u, const float* params, c
     a.rem_ws_floats = (size_t)kRemUnits * 16384;
     a.p = conv_plan(a);
     if (below && rec_tiles && a.w_wino4t && a.p.variant == 11 && a.p.TW == 16 && a.p.ksplit <= 1 && a.Ho == below->Hout && a.Wo == below->Wout &&
-        a.Cout == below->Cout && tune_int("FS_INBWD_FUSED", 1)) {
+        a.Cout == below->Cout && knob(K_INBWD_FUSED)) {
         ConvArgs f = a;
         f.inb_z = ws + below->z;
         f.inb_mean = ws + below->mean;
@@ -754,7 +740,7 @@ int tnet_backward(const TnetLayout& L, const float* params, const float* x, cons
     // neighbour's time -- bench.py's per-kernel table wants every launch alone)
     // ... and no fork for small batches: at batch 4 the fork / join events cost more than the overlap returns (same lease, FS_NO_SIDE_STREAM = 0 / 1:
     // 1100 against 1133 images/s; at batch 32 the fork is worth 1.2 %).  FS_SIDE_MIN_PIXELS: smallest N * H * W that forks.
-    const bool fork = aux && aux->side && aux->nev >= 34 && !Profiler::current() && (long)N * L.H * L.W >= (long)tune_int("FS_SIDE_MIN_PIXELS", 1000000);
+    const bool fork = aux && aux->side && aux->nev >= 34 && !Profiler::current() && (long)N * L.H * L.W >= (long)knob(K_SIDE_MIN_PIXELS);
     hipStream_t ws_stream = fork ? aux->side : s;  // stream of the filter-gradient branch
     if (!filters_ready) {  // every input-gradient filter of the step in one launch (a forward with FS_FLAG_SAVE_FOR_BWD has built them already)
         WtBatch wb{};
@@ -766,7 +752,7 @@ int tnet_backward(const TnetLayout& L, const float* params, const float* x, cons
     }
     Wg2Reduce red{};               // the slab reductions of the non-residual units' filter gradients: ONE launch behind the last of them
     int fold_units[16], n_fold = 0;
-    const bool defer_on = tune_int("FS_WGRAD_DEFER", 1) != 0;
+    const bool defer_on = knob(K_WGRAD_DEFER) != 0;
     const float* g = dy;         // gradient wrt the current unit's output activation (or h_k)
     const float* res_g = nullptr;  // d h_k, kept alive until the block's first conv adds it to its dgrad
     int dz_reader[2] = {-1, -1};   // event (side stream) of the last filter gradient that read dz[0] / dz[1]

@@ -41,13 +41,13 @@ static inline int pool_index(int l) { return l == 1 ? 0 : (l == 3 ? 1 : 2); }
 // prepared under other knobs degrades to the direct kernels, never to a read of bytes that were not written.
 enum { PREP_F2 = 1, PREP_W4 = 2, PREP_W4T = 4, PREP_W6 = 8 };
 unsigned vgg_prep_mask() {
-    if (tune_int("FS_VGG_PREPARE_ALL", 0)) return PREP_F2 | PREP_W4 | PREP_W4T | PREP_W6;
+    if (knob(K_VGG_PREPARE_ALL)) return PREP_F2 | PREP_W4 | PREP_W4T | PREP_W6;
     const WinoGen g = wino_gen();
     return g.split_bf16() ? (PREP_W4T | PREP_W6) : g.f4_reg() ? PREP_W4T : g.f4_lds() ? PREP_W4 : PREP_F2;
 }
 static bool w6_layer_ok(int l, bool dgrad) {
     const int ci = dgrad ? kCout[l] : kCin[l], co = dgrad ? kCin[l] : kCout[l];
-    return l >= 1 && ci % 32 == 0 && co % 128 == 0 && (long)ci * co >= (long)tune_int("FS_WINO6_MINCC", 512 * 256);
+    return l >= 1 && ci % 32 == 0 && co % 128 == 0 && (long)ci * co >= (long)knob(K_WINO6_MINCC);
 }
 struct PrepLayout {
     unsigned mask;
@@ -89,7 +89,7 @@ static bool vgg_want_w6() { return wino_gen().split_bf16(); }
 // debugging aid: FS_VGG_WINO_MASK selects the layers that may take the Winograd kernel (bit l: forward of layer l,
 // bit 16+l: its input gradient); default all
 static bool wino_layer_on(int bit) {
-    return ((unsigned)tune_int("FS_VGG_WINO_MASK", -1) >> bit) & 1u;
+    return ((unsigned)knob(K_VGG_WINO_MASK) >> bit) & 1u;
 }
 
 int vgg_prepare(const float* const w[FS_VGG_NLAYERS], float* prepared, hipStream_t s) {
@@ -230,7 +230,7 @@ void vgg_layout(int N, int H, int W, const fs_loss_cfg& cfg, bool with_content, 
                 const size_t f = wino6_ws_floats(dir == 0 ? (l <= cmax ? L->NB : N) : N, L->Hl[l], L->Wl[l], dir == 0 ? kCin[l] : kCout[l], dir == 0 ? kCout[l] : kCin[l]);
                 if (f > need6) need6 = f;
             }
-    const size_t cap6 = (size_t)tune_int("FS_WINO6_WS_MB", 2048) * (1u << 18);   // floats
+    const size_t cap6 = (size_t)knob(K_WINO6_WS_MB) * (1u << 18);   // floats
     if (need6 > cap6) need6 = cap6;
     L->w6ws_floats = need6;
     L->w6ws = b.take(need6 ? need6 : 4);
@@ -244,11 +244,11 @@ void vgg_layout(int N, int H, int W, const fs_loss_cfg& cfg, bool with_content, 
 // next to a resident GEMM wave).  Measured on three conv4_2-shaped layers at batch 32: 355 -> 284 us per layer (tools/micro_wino6_overlap.py).  Off while the
 // per-kernel profiler runs (its event pairs would time overlapping launches), for odd N, and under FS_WINO6_CHAINS=0.
 static bool w6_chains_on(const StreamAux* aux, int N) {
-    return aux && aux->side && aux->nev >= 2 && !(N & 1) && !Profiler::current() && tune_int("FS_WINO6_OVERLAP", 1) == 1;
+    return aux && aux->side && aux->nev >= 2 && !(N & 1) && !Profiler::current() && knob(K_WINO6_OVERLAP) == 1;
 }
 // ... or every launch on its own as two tile chunks pipelined over the two streams (fs_wino6.hip; FS_WINO6_OVERLAP = 2; measured SLOWER than no overlap in the step -- two GEMM launches of 4.5 grid rounds each and three more graph edges per launch --, kept as a recorded experiment; 0: neither; 1, the default: the chains above)
 static void w6_pipe_args(ConvArgs* a, const StreamAux* aux) {
-    if (aux && aux->side && aux->nev >= 3 && !Profiler::current() && tune_int("FS_WINO6_OVERLAP", 1) == 2) {
+    if (aux && aux->side && aux->nev >= 3 && !Profiler::current() && knob(K_WINO6_OVERLAP) == 2) {
         a->w6_side = aux->side;
         a->w6_ev = aux->ev;
     }
@@ -256,7 +256,7 @@ static void w6_pipe_args(ConvArgs* a, const StreamAux* aux) {
 // (a half of at least FS_WINO6_CHAIN_MINTILES tiles, default 1024 = conv4_x at batch 32, where the chains were measured; below it -- batch 4 per GPU: 256 tiles
 // per launch -- ONE chain: 3.283 -> 3.239 ms per batch-4 step against the fp32 kernel's split-K launches, profiles/r06_ab_wino6_exact_waits.txt)
 static bool w6_chain_launch_ok(const ConvArgs& a) {
-    return a.p.variant == 12 && !(a.N & 1) && !a.y_keep_n && (long)(a.N / 2) * cdiv(a.Ho, 4) * cdiv(a.Wo, 4) >= (long)tune_int("FS_WINO6_CHAIN_MINTILES", 1024) &&
+    return a.p.variant == 12 && !(a.N & 1) && !a.y_keep_n && (long)(a.N / 2) * cdiv(a.Ho, 4) * cdiv(a.Wo, 4) >= (long)knob(K_WINO6_CHAIN_MINTILES) &&
            a.w6_ws_floats >= 2 * wino6_ws_floats(a.N / 2, a.Ho, a.Wo, a.Cin, a.Cout);
 }
 struct W6Chains {   // fork / join bookkeeping of one run
@@ -344,10 +344,10 @@ static int vgg_conv(const float* x, int N, int H, int W, int l, const float* w, 
     }
     a.p = conv_plan(a);
     if (pooled) *pooled = false;
-    if (pool && (a.p.variant == 5 || a.p.variant == 6 || a.p.variant == 10 || a.p.variant == 11 || a.p.variant == 12) && a.p.ksplit <= 1 && !(H & 1) && !(W & 1) && tune_int("FS_VGG_POOL_FUSED", 1)) {
+    if (pool && (a.p.variant == 5 || a.p.variant == 6 || a.p.variant == 10 || a.p.variant == 11 || a.p.variant == 12) && a.p.ksplit <= 1 && !(H & 1) && !(W & 1) && knob(K_VGG_POOL_FUSED)) {
         a.pool_out = pool;   // the Winograd epilogues hold whole 2x2 tiles: the pooled tensor comes for one extra store per tile
         if (pooled) *pooled = true;
-        if ((a.p.variant == 11 || a.p.variant == 12) && tune_int("FS_VGG_SKIP_CONTENT_Y", 1)) a.y_keep_n = y_keep_n;
+        if ((a.p.variant == 11 || a.p.variant == 12) && knob(K_VGG_SKIP_CONTENT_Y)) a.y_keep_n = y_keep_n;
     }
     if (chains) {   // (a run of split-bf16 launches goes out as two half-batch chains; anything else closes the run first)
         if (w6_chain_launch_ok(a)) return chains->launch(a);
@@ -542,7 +542,7 @@ int perceptual_loss(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], co
     {
         // Gram matrices: the matrix kernels layer by layer, then ONE launch that reduces the slabs of all layers, mirrors them, and leaves
         // S = 4w/(c^2 hwc) (G - Gt) (dF = F S, G symmetric) and the partial sums of (G - Gt)^2 (loss += w * sum / c^2, losses.py:61-64)
-        bool batch = cfg.n_style > 0 && tune_int("FS_GRAM_FINISH_BATCH", 1);
+        bool batch = cfg.n_style > 0 && knob(K_GRAM_FINISH_BATCH);
         for (int i = 0; i < cfg.n_style; ++i) {
             const int l = cfg.style_layer[i];
             batch = batch && gram2_eligible(N, L.Hl[l] * L.Wl[l], kCout[l]);
@@ -557,7 +557,7 @@ int perceptual_loss(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], co
                 GramFinishJob& j = jobs[i];
                 j.slabs = ws + L.gslab[i];
                 j.Gt = cfg.target_gram[i];
-                j.G = tune_int("FS_GRAM_FINISH_KEEP_G", 0) ? ws + L.gram[i] : nullptr;   // (nothing reads G after the finish: S and the loss's partial sums are its products)
+                j.G = knob(K_GRAM_FINISH_KEEP_G) ? ws + L.gram[i] : nullptr;   // (nothing reads G after the finish: S and the loss's partial sums are its products)
                 j.S = ws + L.sm[i];
                 j.HW = HW;
                 j.C = C;
@@ -599,7 +599,7 @@ int perceptual_loss(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], co
         const bool route_in_gram = fuse_dst && fuse_above && n_style_here == 1 && gram_bwd2_route_eligible(N, H, W, C);
         // (round 5) a layer that carries one content and one style term and takes the routed Gram-gradient launch below forms the content term THERE
         // (F is that kernel's operand): no sqdiff pass, no content-gradient tensor
-        const bool content_in_gram = route_in_gram && n_content_here == 1 && tune_int("FS_GRAM_CONTENT_FUSED", 1) && gram_bwd2_route_grid(N, H, W, C) <= 1024;
+        const bool content_in_gram = route_in_gram && n_content_here == 1 && knob(K_GRAM_CONTENT_FUSED) && gram_bwd2_route_grid(N, H, W, C) <= 1024;
         const float* fused_content = nullptr;
         float fused_cscale = 0.f;
         float* fused_cpartial = nullptr;
@@ -642,7 +642,7 @@ int perceptual_loss(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], co
                 // (measured at batch 32: the mask alone -- last layer, no pool behind it -- is free in the conv's epilogue; the pool
                 // routing costs the Gram-gradient conv +0.45 ms for 0.75 ms of vgg_bwd_route saved, one 4-byte load per lane
                 // against that kernel's 16-byte streams: 0.4 % of the step, so it stays a knob, FS_VGG_ROUTE_FUSED=1)
-                if (fuse_dst && n_terms == 1 && (!fuse_above || tune_int("FS_VGG_ROUTE_FUSED", 0))) {
+                if (fuse_dst && n_terms == 1 && (!fuse_above || knob(K_VGG_ROUTE_FUSED))) {
                     ConvArgs f = a;
                     f.mask_src = ws + L.act[l];
                     f.route_src = fuse_above;

@@ -542,8 +542,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
 #endif
 }
 
-static int env_int2(const char* name, int dflt) { return tune_int(name, dflt); }
-
 WgradPlan wgrad_plan(const WgradArgs& a) {
     WgradPlan p{};
     p.K = a.KH * a.KW * a.Cin;
@@ -571,7 +569,7 @@ WgradPlan wgrad_plan(const WgradArgs& a) {
     const int kblocks_w0 = cdiv(p.KB, p.KWV);
     const int waves_k0 = kblocks_w0 >= 3 ? 4 : (kblocks_w0 >= 2 ? 2 : 1);
     const int groups0 = cdiv(p.KB, waves_k0 * p.KWV) * cdiv(p.NB, NWV) * (a.per_sample ? a.N : 1);
-    const int start_px = env_int2("FS_WGRAD_MAXPX", 256);
+    const int start_px = knob(K_WGRAD_MAXPX);
     for (int max_px = start_px; max_px >= 32; max_px >>= 1) {
         int tw = a.Wo >= 16 ? 16 : ((a.Wo + 1) & ~1);
         tw = cdiv(cdiv(a.Wo, cdiv(a.Wo, tw)), 2) * 2;
@@ -593,9 +591,9 @@ WgradPlan wgrad_plan(const WgradArgs& a) {
         // CU balance: every workgroup gets the same number of tiles, but with n_wg between 256 and 512 some CUs run two
         // workgroups and the others one (e.g. 441 -> 86 % of the chip).  If halving the tile lands the workgroup count
         // just under a multiple of 256, take the smaller tile.
-        if (max_px > 64 && env_int2("FS_WGRAD_BALANCE", 1)) {
+        if (max_px > 64 && knob(K_WGRAD_BALANCE)) {
             auto eff = [&](long total_tiles) {
-                int want = env_int2("FS_WGRAD_WGS", 512) / groups0;
+                int want = knob(K_WGRAD_WGS) / groups0;
                 if (want < 1) want = 1;
                 const long t = total_tiles <= want ? 1 : cdiv((int)total_tiles, want);  // tiles per workgroup
                 const long nwg = total_tiles <= want ? total_tiles : cdiv((int)total_tiles, (int)t);
@@ -612,7 +610,7 @@ WgradPlan wgrad_plan(const WgradArgs& a) {
     p.waves_k = kblocks_w >= 3 ? 4 : (kblocks_w >= 2 ? 2 : 1);
     const int total = (a.per_sample ? 1 : a.N) * p.tiles_y * p.tiles_x;
     const int groups = cdiv(p.KB, p.waves_k * p.KWV) * cdiv(p.NB, NWV) * (a.per_sample ? a.N : 1);
-    int want = env_int2("FS_WGRAD_WGS", 512) / groups;  // aim for ~2 workgroups per CU in flight
+    int want = knob(K_WGRAD_WGS) / groups;  // aim for ~2 workgroups per CU in flight
     if (want < 1) want = 1;
     // equal number of tiles per workgroup (no straggler round)
     p.n_wg = total <= want ? total : cdiv(total, cdiv(total, want));
@@ -633,7 +631,7 @@ int wgrad_launch(const WgradArgs& a_in, hipStream_t s) {
     const WgradPlan& p = a.p;
     a.same_xy = a.per_sample && a.x == a.dy && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.Cin == a.Cout && a.Cin <= 128 &&
                 a.Cin % 32 == 0 && !a.in_a && !a.dy_a && !a.dy_unshuffle && a.src_mode == SRC_PLAIN && a.pad_t == 0 && a.pad_l == 0 &&
-                tune_int("FS_GRAM_SAME", 1);
+                knob(K_GRAM_SAME);
     if (a.Cin > 128 && a.Cin % 128) return -1;
     if (p.lds_bytes > 160 * 1024) return -2;
     const int NWV = p.NWV;

@@ -581,7 +581,7 @@ bool wgrad2_eligible(const WgradArgs& a) {
     // accumulator tile of one workgroup: 4 waves x (KM x KN) blocks
     if (NB > 8) return false;
     const int KM = NB > 4 ? 4 : (NB >= 2 ? 9 : 18);
-    return KB <= 4 * KM && tune_int("FS_WGRAD2", 1) != 0;
+    return KB <= 4 * KM && knob(K_WGRAD2) != 0;
 }
 
 static void w2_variant(int KB, int NB, int* KM, int* KN, int* waves_k) {
@@ -645,7 +645,7 @@ size_t wgrad2_plan(const WgradArgs* probs, int n, Wg2Args* out) {
     A.dy_nstride = with_dy ? with_dy->dy_nstride : 0;
     A.dy_relu = with_dy ? with_dy->dy_relu : 0;
     A.dy_unshuffle = g.dy_unshuffle;
-    A.debug = tune_int("FS_WGRAD2_DEBUG", 0);   // timing experiments only: 1 skips the sweeps, 2 stages only the first tile
+    A.debug = knob(K_WGRAD2_DEBUG);   // timing experiments only: 1 skips the sweeps, 2 stages only the first tile
     p.K = g.KH * g.KW * g.Cin;
     p.KB = cdiv(p.K, 16);
     p.NB = g.Cout / 16;
@@ -663,7 +663,7 @@ size_t wgrad2_plan(const WgradArgs* probs, int n, Wg2Args* out) {
         if (probs[i].Wo > maxWo) maxWo = probs[i].Wo;
         px_total += (long)probs[i].N * probs[i].Ho * probs[i].Wo;
     }
-    const int n_wg_max = tune_int("FS_WGRAD2_WGS", 256);
+    const int n_wg_max = knob(K_WGRAD2_WGS);
     const long want_px = px_total / ((long)n_wg_max * 8) > 32 ? px_total / ((long)n_wg_max * 8) : 32;   // pixels per tile for >= 8 tiles/workgroup
     double best = -1;
     for (int tw = 8; tw <= 32 && tw <= ((maxWo + 7) & ~7); tw += 8)
@@ -698,7 +698,7 @@ size_t wgrad2_plan(const WgradArgs* probs, int n, Wg2Args* out) {
         }
     if (best < 0) return 0;
     p.lds_bytes = 2 * p.stage_floats * 4;
-    p.combine = waves_p > 1 && tune_int("FS_WGRAD2_COMBINE", 1) != 0;
+    p.combine = waves_p > 1 && knob(K_WGRAD2_COMBINE) != 0;
     if (p.combine && p.lds_bytes < p.waves_k * p.KM * p.KN * 4 * 64 * 4) p.lds_bytes = p.waves_k * p.KM * p.KN * 4 * 64 * 4;   // the hand-over buffer of one group
     // deal workgroups to problems in proportion to their tile counts (same geometry: same cost per tile)
     long tiles_total = 0;
@@ -793,15 +793,15 @@ int wgrad2_run(const Wg2Args& planned, float* slabs, float* const* dw, float sca
     const Wg2Plan& p = a.p;
     const int wvp = 4 / p.waves_k;
     auto geo = [&](int sa, int sd, int spr, int th, int pw, int wp) {
-        return tune_int("FS_WGRAD2_STATIC", 1) != 0 && a.stride * p.S == sa && p.DP == sd && p.TW == 4 * spr && p.TH == th && p.PW == pw && wvp == wp;
+        return knob(K_WGRAD2_STATIC) != 0 && a.stride * p.S == sa && p.DP == sd && p.TW == 4 * spr && p.TH == th && p.PW == pw && wvp == wp;
     };
-    if (tune_int("FS_CONV_DEBUG", 0))
+    if (knob(K_CONV_DEBUG))
         fprintf(stderr, "wgrad2: KM %d KN %d Cin %d Cout %d K %d stride %d S %d DP %d tile %dx%d PW %d waves_p %d wgs %d nprob %d\n", p.KM, p.KN, a.Cin,
                 a.Cout, p.K, a.stride, p.S, p.DP, p.TH, p.TW, p.PW, wvp, a.n_wg, a.nprob);
     // (geometry: stride * S, DP, tile width / 4, tile rows, patch width, waves over the pixel rows)
 #define FS_W2_GEO(KM, KN, XV, SA, SD, SPR, TH, PW, WP) \
     if (geo(SA, SD, SPR, TH, PW, WP)) {                                                        \
-        if (tune_int("FS_CONV_DEBUG", 0)) fprintf(stderr, "wgrad2: static instance %d %d | %d %d %d %d %d %d\n", KM, KN, SA, SD, SPR, TH, PW, WP); \
+        if (knob(K_CONV_DEBUG)) fprintf(stderr, "wgrad2: static instance %d %d | %d %d %d %d %d %d\n", KM, KN, SA, SD, SPR, TH, PW, WP); \
         w2_launch<KM, KN, XV, SA, SD, SPR, TH, PW, WP>(a, s);                                  \
     } else
     if (a.Cin == 3) {

@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void wgw_reduce_kernel(WgwReduce r) {
 }
 
 bool wgw_eligible(const WgradArgs& a) {
-    return tune_int("FS_WGW", 1) && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.Cin == kC && a.Cout == kC && a.pad_t == 0 && a.pad_l == 0 &&
+    return knob(K_WGW) && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.Cin == kC && a.Cout == kC && a.pad_t == 0 && a.pad_l == 0 &&
            a.Ho == a.H - 2 && a.Wo == a.W - 2 && a.src_mode == SRC_PLAIN && !a.per_sample && !a.dy_unshuffle && !a.dy_a && a.dil_x <= 1 &&
            (double)a.N * a.H * a.W * kC * 4.0 < 2147483648.0;
 }
@@ -309,7 +309,7 @@ size_t wgw_plan(const WgradArgs* probs, int n, WgwArgs* out) {
             w.in_nstride = probs[i].in_nstride;
             w.in_relu = probs[i].in_relu;
         }
-    const int wgs_total = tune_int("FS_WGW_WGS", 256);
+    const int wgs_total = knob(K_WGW_WGS);
     const int per_lo = wgs_total / n < 1 ? 1 : wgs_total / n, extra = wgs_total >= n ? wgs_total - per_lo * n : 0;   // the first `extra` problems get one more
     long total_steps = 0;
     int wg = 0;
@@ -339,7 +339,7 @@ size_t wgw_plan(const WgradArgs* probs, int n, WgwArgs* out) {
         off += (size_t)p.wg_count * (16 * kC * kC);
         total_steps += p.steps;
     }
-    if (total_steps < (long)tune_int("FS_WGW_MIN_STEPS", 64) * n) return 0;   // tiny problems: the slab traffic outweighs the matrix work
+    if (total_steps < (long)knob(K_WGW_MIN_STEPS) * n) return 0;   // tiny problems: the slab traffic outweighs the matrix work
     w.n_wg = wg;
     *out = w;
     return off;

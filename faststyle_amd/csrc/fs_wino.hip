@@ -532,7 +532,7 @@ void wino_plan(const ConvArgs& a, ConvPlan* out) {
     p.ksplit = 1;
     const long wgs = (long)a.N * p.tiles_y * p.tiles_x * (a.Cout / kBN);
     const int nchunks = a.Cin / kCC;
-    const int max_ks = tune_int("FS_WINO_KSPLIT", 4);  // tuning / debugging aid
+    const int max_ks = knob(K_WINO_KSPLIT);  // tuning / debugging aid
     if (a.split_ws && !a.stats) {
         int ks = 1;
         while (ks < max_ks && wgs * ks < 256 && nchunks / (ks * 2) >= 8 &&

@@ -799,7 +799,7 @@ bool wino2_eligible(const ConvArgs& a) {
     const bool pad_ok = a.pad_t == a.pad_l && a.pad_t >= 0 && a.pad_t <= 2 && a.Ho == a.H + 2 * a.pad_t - 2 && a.Wo == a.W + 2 * a.pad_l - 2;
     // (measured: ahead of the first-generation kernel on the 64-channel layers -- 8 chunks per block, where the fixed cost of
     // a block weighs most --, level at 128 input channels, behind it beyond: FS_WINO2_MAXCIN)
-    return a.w_wino2 && wino_gen().f2_second() && a.Cin <= tune_int("FS_WINO2_MAXCIN", 128) && a.KH == 3 && a.KW == 3 && a.stride == 1 && pad_ok && a.src_mode == SRC_PLAIN && a.Cin % kCC == 0 &&
+    return a.w_wino2 && wino_gen().f2_second() && a.Cin <= knob(K_WINO2_MAXCIN) && a.KH == 3 && a.KW == 3 && a.stride == 1 && pad_ok && a.src_mode == SRC_PLAIN && a.Cin % kCC == 0 &&
            a.Cout % kBN == 0 && !a.shuffle && (!a.in_a || a.pad_t == 0) && a.w_nstride == 0 && (a.dil_x <= 1) &&
            (!a.add_src || !a.stats);
 }
@@ -816,7 +816,7 @@ void wino2_plan(const ConvArgs& a, ConvPlan* out) {
     p.ksplit = 1;
     const long items = (long)a.N * p.tiles_y * p.tiles_x * (a.Cout / kBN);
     const int nchunks = a.Cin / kCC;
-    const int max_ks = tune_int("FS_WINO_KSPLIT", 4);
+    const int max_ks = knob(K_WINO_KSPLIT);
     if (a.split_ws && !a.stats && !a.add_src) {
         int ks = 1;
         while (ks < max_ks && items * ks < 256 && nchunks / (ks * 2) >= 8 &&
@@ -826,8 +826,8 @@ void wino2_plan(const ConvArgs& a, ConvPlan* out) {
     }
     // remainder split (transform-net launches; see wino2_conv_kernel<true>): whole rounds of whole items, the last partial
     // round split over the input-channel chunks so that it occupies the whole chip for a fraction of a round
-    if (a.rem_ws && a.tnet_plan && p.ksplit == 1 && !a.bias && !a.out_relu && !a.mask_src && !a.pool_out && !a.fin.counter && tune_int("FS_WINO2_REM", 1)) {
-        const long G = tune_int("FS_WINO2_WGS", 256);
+    if (a.rem_ws && a.tnet_plan && p.ksplit == 1 && !a.bias && !a.out_relu && !a.mask_src && !a.pool_out && !a.fin.counter && knob(K_WINO2_REM)) {
+        const long G = knob(K_WINO2_WGS);
         if (items > G) {
             const long full = items / G * G, rem = items - full;
             int rks = 1;
@@ -844,7 +844,7 @@ void wino2_plan(const ConvArgs& a, ConvPlan* out) {
 int wino2_launch(const ConvArgs& a, hipStream_t s) {
     const ConvPlan& p = a.p;
     const long items = (long)a.N * p.tiles_y * p.tiles_x * (a.Cout / kBN) * (p.ksplit > 1 ? p.ksplit : 1);
-    const int wgs = tune_int("FS_WINO2_WGS", 256);
+    const int wgs = knob(K_WINO2_WGS);
     if (p.rem_ks > 0) {   // whole items of the full rounds + units of the split remainder, then the remainder's epilogue
         static BigLds lds_attr_rem;
         lds_attr_rem.ensure(reinterpret_cast<const void*>(wino2_conv_kernel<true>));

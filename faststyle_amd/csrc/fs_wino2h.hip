@@ -556,7 +556,7 @@ bool wino2h_eligible(const ConvArgs& a) {
 static void wino2h_shape(int Ho, int Wo, int* bh, int* bw) {
     static const int shapes[4][2] = {{4, 8}, {5, 6}, {6, 5}, {8, 4}};
     long best = -1;
-    const int forced = tune_int("FS_WINO2H_SHAPE", -1);
+    const int forced = knob(K_WINO2H_SHAPE);
     for (int s = 0; s < 4; ++s) {
         if (forced >= 0 && forced != s) continue;
         const long n = (long)cdiv(Ho, 2 * shapes[s][0]) * cdiv(Wo, 2 * shapes[s][1]);
@@ -597,7 +597,7 @@ int wino2h_launch(const ConvArgs& a, hipStream_t s) {
     static BigLds lds_attr;
     lds_attr.ensure(reinterpret_cast<const void*>(wino2h_conv_kernel));
     const long items = (long)a.N * p.tiles_y * p.tiles_x * (a.Cout / kBN);
-    const int wgs = tune_int("FS_WINO2_WGS", 256);
+    const int wgs = knob(K_WINO2_WGS);
     const long grid = items < wgs ? items : wgs;
     hipLaunchKernelGGL(wino2h_conv_kernel, dim3((unsigned)grid), dim3(256), (size_t)p.lds_bytes, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;

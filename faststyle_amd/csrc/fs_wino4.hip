@@ -631,13 +631,13 @@ void wino4_plan(const ConvArgs& a, ConvPlan* out) {
     p.tiles_x = cdiv(a.Wo, kBW);
     p.lds_bytes = 4 * 2 * kStageF;
     p.ksplit = 1;
-    p.skew = tune_int("FS_WINO4_STAGGER", 0);
+    p.skew = knob(K_WINO4_STAGGER);
     const long items = (long)a.N * p.tiles_y * p.tiles_x * (a.Cout / kBN);
     const int nchunks = a.Cin / kCC;
-    const int max_ks = tune_int("FS_WINO_KSPLIT", 4);
+    const int max_ks = knob(K_WINO_KSPLIT);
     if (a.split_ws && !a.pool_out) {
         int ks = 1;
-        const int min_steps = tune_int("FS_WINO4_KSPLIT_MINSTEPS", 16);   // chunks (steps) a split item must keep
+        const int min_steps = knob(K_WINO4_KSPLIT_MINSTEPS);   // chunks (steps) a split item must keep
         while (ks < max_ks && items * ks < 256 && nchunks / (ks * 2) >= min_steps && (size_t)(ks * 2) * a.N * a.Ho * a.Wo * a.Cout <= a.split_ws_floats) ks *= 2;
         p.ksplit = ks;
     }
@@ -647,7 +647,7 @@ void wino4_plan(const ConvArgs& a, ConvPlan* out) {
 int wino4_launch(const ConvArgs& a, hipStream_t s) {
     const ConvPlan& p = a.p;
     const long items = (long)a.N * p.tiles_y * p.tiles_x * (a.Cout / kBN) * (p.ksplit > 1 ? p.ksplit : 1);
-    const int wgs = tune_int("FS_WINO4_WGS", 256);
+    const int wgs = knob(K_WINO4_WGS);
     const long grid = items < wgs ? items : wgs;
     static BigLds lds_attr[3];
     const int epi = p.ksplit > 1 ? 0 : (a.mask_src ? 2 : ((a.bias || a.out_relu || a.pool_out) ? 1 : 0));

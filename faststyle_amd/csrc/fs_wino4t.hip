@@ -120,10 +120,10 @@ static long wino4t_items_tb(const ConvArgs& a, int tb) { return (long)a.N * cdiv
 // tile blocks per item: 32-tile items amortise the filter loads over twice the products (a step costs ~1.8x that of a 16-tile item), 16-tile
 // items fill small grids.  FS_WINO4T_TB = 1 | 2 pins it.
 static int wino4t_pick_tb(const ConvArgs& a) {
-    const int forced = tune_int("FS_WINO4T_TB", 0);
+    const int forced = knob(K_WINO4T_TB);
     if (forced == 1 || forced == 2) return forced;
     if (a.tnet_plan == 1) return 1;   // the transform net's 8-step items: measured level at batch 32 (800 16-tile / 480 32-tile items), 16-tile items ahead everywhere else
-    const int wgs = tune_int("FS_WINO4T_WGS", 256);
+    const int wgs = knob(K_WINO4T_WGS);
     const double c1 = (double)cdiv((int)wino4t_items_tb(a, 1), wgs), c2 = 1.8 * (double)cdiv((int)wino4t_items_tb(a, 2), wgs);
     return c2 <= c1 ? 2 : 1;
 }
@@ -135,7 +135,7 @@ long wino4t_items(const ConvArgs& a) { return wino4t_items_tb(a, wino4t_pick_tb(
 // FS_WINO4T_CB = 1 disables it.
 static bool wino4t_use_cb2(const ConvArgs& a) {
     const int e = wino4t_epi(a, 1);
-    return a.w_wino4u && a.Cout % (2 * kBN) == 0 && !a.in_a && (e == 0 || e == 3 || e == 4) && tune_int("FS_WINO4T_CB", 2) >= 2 && wino4t_pick_tb(a) == 2;
+    return a.w_wino4u && a.Cout % (2 * kBN) == 0 && !a.in_a && (e == 0 || e == 3 || e == 4) && knob(K_WINO4T_CB) >= 2 && wino4t_pick_tb(a) == 2;
 }
 
 // The flattened form (M = 4 of the kernel, round 5): 16 consecutive tiles of the sample's row-major tile list per item -- ceil(tiles / 16) items per
@@ -143,12 +143,12 @@ static bool wino4t_use_cb2(const ConvArgs& a) {
 // of the persistent grid (batch 32 at 256 x 256: 736 against 800 items = three rounds instead of four); the transform net's launches only (its
 // epilogue forms).  FS_WINO4T_FLAT = 0 never, 2 always (tests).
 static bool wino4t_use_flat(const ConvArgs& a, int tb, bool cb2) {
-    const int mode = tune_int("FS_WINO4T_FLAT", 1);
+    const int mode = knob(K_WINO4T_FLAT);
     const int e = wino4t_epi(a, 1);
     if (!mode || tb != 1 || cb2 || !(e == 0 || e == 1 || e == 2 || e == 5 || e == 6) || a.split_ws) return false;
     if (mode == 2) return true;
     if (!a.tnet_plan) return false;
-    const int wgs = tune_int("FS_WINO4T_WGS", 256);
+    const int wgs = knob(K_WINO4T_WGS);
     const long ncob = a.Cout / kBN;
     const long rect = (long)a.N * cdiv(a.Ho, kBH) * cdiv(a.Wo, 16) * ncob, flat = (long)a.N * cdiv(cdiv(a.Ho, 4) * cdiv(a.Wo, 4), 16) * ncob;
     return cdiv((int)flat, wgs) < cdiv((int)rect, wgs);
@@ -175,10 +175,10 @@ void wino4t_plan(const ConvArgs& a, ConvPlan* out) {
     p.ksplit = 1;
     const long items = (long)a.N * p.tiles_y * p.tiles_x * (a.Cout / p.BN);
     const int nchunks = a.Cin / kCC;
-    const int max_ks = tune_int("FS_WINO_KSPLIT", 4);
+    const int max_ks = knob(K_WINO_KSPLIT);
     if (a.split_ws && !a.pool_out && !a.stats && !a.in_a && !a.inb_rec && !p.flat_tiles) {   // split-K where the launch cannot fill the chip (the rule of fs_wino4.hip; a step here is 8 channels)
         int ks = 1;
-        const int min_steps = tune_int("FS_WINO4_KSPLIT_MINSTEPS", 16) / 2;
+        const int min_steps = knob(K_WINO4_KSPLIT_MINSTEPS) / 2;
         while (ks < max_ks && items * ks < 256 && nchunks / (ks * 2) >= min_steps && (size_t)(ks * 2) * a.N * a.Ho * a.Wo * a.Cout <= a.split_ws_floats) ks *= 2;
         p.ksplit = ks;
     }
@@ -201,7 +201,7 @@ int wino4t_launch(const ConvArgs& a, hipStream_t s) {
     const int epi = wino4t_epi(a, ks);
     if (epi < 0 || (tb != 1 && tb != 2) || (a.in_a && epi > 1)) return -7;
     const long items = (long)a.N * p.tiles_y * p.tiles_x * (a.Cout / p.BN) * ks;
-    const int wgs = tune_int("FS_WINO4T_WGS", 256);
+    const int wgs = knob(K_WINO4T_WGS);
     const long grid = items < wgs ? items : wgs;
     if (p.flat_tiles) {
         if (tb != 1 || p.BN != kBN || ks != 1) return -7;

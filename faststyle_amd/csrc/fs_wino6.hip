@@ -459,7 +459,7 @@ bool wino6_eligible(const ConvArgs& a) {
     const long T = (long)a.N * cdiv(a.Ho, 4) * cdiv(a.Wo, 4);
     return a.KH == 3 && a.KW == 3 && a.stride == 1 && pad_ok && a.src_mode == SRC_PLAIN && a.Cin % kW6K == 0 && a.Cout % kW6TN == 0 && !a.shuffle && wino6_epi(a) >= 0 &&
            !a.route_src && a.w_nstride == 0 && a.dil_x <= 1 && !a.fin.counter && a.Ho > 0 && a.Wo > 0 && (!a.pool_out || (!(a.Ho & 1) && !(a.Wo & 1))) &&
-           (long)a.Cin * a.Cout >= (long)tune_int("FS_WINO6_MINCC", 512 * 256) && T >= tune_int("FS_WINO6_MINTILES", 256) && T < (1L << 24) && 36.0 * (double)((T + 127) & ~127L) * (a.Cin > a.Cout ? a.Cin : a.Cout) * 4.0 < 4294967296.0 &&
+           (long)a.Cin * a.Cout >= (long)knob(K_WINO6_MINCC) && T >= knob(K_WINO6_MINTILES) && T < (1L << 24) && 36.0 * (double)((T + 127) & ~127L) * (a.Cin > a.Cout ? a.Cin : a.Cout) * 4.0 < 4294967296.0 &&
            a.w6_ws_floats >= (size_t)36 * 128 * ((size_t)a.Cin + a.Cout);
 }
 
@@ -501,10 +501,10 @@ int wino6_launch(const ConvArgs& a, hipStream_t s) {
     const long Tall = (long)a.N * w.th * w.tw;
     // tiles per pass: what the workspace holds (multiples of 128), optionally capped (FS_WINO6_CHUNK: a chunk whose V and M stay in the 256 MB Infinity Cache)
     long cap = (long)(a.w6_ws_floats / ((size_t)36 * ((size_t)a.Cin + a.Cout))) & ~127L;
-    const int knob = tune_int("FS_WINO6_CHUNK", 0);
-    if (knob >= 128 && (knob & ~127) < cap) cap = knob & ~127;
+    const int chunk_cap = knob(K_WINO6_CHUNK);
+    if (chunk_cap >= 128 && (chunk_cap & ~127) < cap) cap = chunk_cap & ~127;
     if (cap < 128) return -7;
-    const int nw = tune_int("FS_WINO6_WAVES", 4) == 8 ? 8 : 4;   // 8 measured level or slower (profiles/r06_ab_split_bf16_pipeline.txt): kept as an experiment
+    const int nw = knob(K_WINO6_WAVES) == 8 ? 8 : 4;   // 8 measured level or slower (profiles/r06_ab_split_bf16_pipeline.txt): kept as an experiment
     static BigLds lds_attr4, lds_attr8;
     if (nw == 4) lds_attr4.ensure(reinterpret_cast<const void*>(wino6_gemm_kernel<4>));
     else lds_attr8.ensure(reinterpret_cast<const void*>(wino6_gemm_kernel<8>));
@@ -537,7 +537,7 @@ int wino6_launch(const ConvArgs& a, hipStream_t s) {
     // their waves fit on a SIMD beside a GEMM wave --   s:    K1a | K2a        | K2b        | K3b
     //                                                   side:      | K1b        | K3a        |          (joined before returning)
     const long Ta = ((Tall / 2) + 127) & ~127L;
-    if (a.w6_side && a.w6_ev && !Profiler::current() && tune_int("FS_WINO6_PIPE", 1) && Tall - Ta >= 128 && cap >= Ta + (((Tall - Ta) + 127) & ~127L)) {
+    if (a.w6_side && a.w6_ev && !Profiler::current() && knob(K_WINO6_PIPE) && Tall - Ta >= 128 && cap >= Ta + (((Tall - Ta) + 127) & ~127L)) {
         const W6Args ca = chunk(0, Ta, a.w6_ws);
         const W6Args cb = chunk(Ta, Tall - Ta, a.w6_ws + (size_t)36 * ca.Tpad * ((size_t)a.Cin + a.Cout));
         hipStream_t t = a.w6_side;

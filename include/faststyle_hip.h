@@ -31,6 +31,12 @@ int fs_ctx_set_stream(fs_ctx* ctx, void* hip_stream);
 const char* fs_last_error(void);
 const char* fs_version(void);
 
+/* ---- tests and tuning scripts only (not part of the product ABI): the FS_* environment knobs are read once each;
+ * fs_debug_reload_env re-reads them after the environment changed.  fs_debug_knob describes row i of the knob table -- its environment
+ * name, default and current value (null pointers are skipped) -- and returns -1 past the last row. */
+void fs_debug_reload_env(void);
+int fs_debug_knob(int i, const char** name, int* dflt, int* value);
+
 /* ---- measurement hook (bench.py): HIP events around every MFMA-kernel launch on the ctx stream.
  * out[f*3+{0,1,2}] = {launches, FLOPs executed, milliseconds} of row f; fs_profile_family_name(f) is the kernel symbol the
  * row belongs to (one row per symbol, so a row can be re-derived from a `rocprofv3 --kernel-trace --stats` summary; the
