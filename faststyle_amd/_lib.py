@@ -149,6 +149,9 @@ PROTOTYPES = {
     "fs_example_int64": (c_int, [c_void_p, c_size_t, c_char_p, POINTER(c_longlong)]),
     "fs_resize_bicubic_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     "fs_resize_bicubic_u8x": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int]),
+    "fs_resize_bicubic_u8x_many": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
+    "fs_queue_take": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "fs_synth_uniform": (c_int, [c_void_p, c_void_p, c_size_t, c_uint64, c_uint32, c_uint64]),
     "fs_u8_to_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "fs_f32_to_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
 }
@@ -156,6 +159,18 @@ PROTOTYPES = {
 
 class FaststyleError(RuntimeError):
     pass
+
+
+def knob(lib, name):
+    """Current value of one row of the library's knob table (csrc/fs_knobs.h), e.g. knob(lib, "FS_FEED_DEPTH"): read from the environment by
+    the library, once per fs_debug_reload_env."""
+    i = 0
+    row, value = c_char_p(), c_int()
+    while lib.fs_debug_knob(i, ctypes.byref(row), None, ctypes.byref(value)) == 0:
+        if row.value.decode() == name:
+            return value.value
+        i += 1
+    raise FaststyleError("the library has no knob %s" % name)
 
 
 def bind(cdll):

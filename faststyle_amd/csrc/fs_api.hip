@@ -109,6 +109,46 @@ int fs_resize_bicubic_u8x(fs_ctx* ctx, const unsigned char* src, int H, int W, i
     return rc ? fail(rc, "fs_resize_bicubic_u8x: launch failed (%d)", rc) : 0;
 }
 
+int fs_resize_bicubic_u8x_many(fs_ctx* ctx, const unsigned char* base, size_t base_bytes, const fs_resize_item* items_host,
+                               const fs_resize_item* items_dev, int K, float* store, int capacity, int Ho, int Wo) {
+    if (!ctx || !base || !items_host || !items_dev || !store) return fail(-1, "fs_resize_bicubic_u8x_many: null argument");
+    if (K < 1) return fail(-1, "fs_resize_bicubic_u8x_many: K must be positive, got %d", K);
+    if (Ho < 1 || Wo < 1 || capacity < 1) return fail(-1, "fs_resize_bicubic_u8x_many: bad store shape [%d,%d,%d,3]", capacity, Ho, Wo);
+    if ((uintptr_t)items_dev & 7) return fail(-5, "fs_resize_bicubic_u8x_many: the descriptor table must be 8-byte aligned");
+    for (int k = 0; k < K; ++k) {
+        const fs_resize_item& it = items_host[k];
+        if (it.pixel_bytes != 3 && it.pixel_bytes != 4)
+            return fail(-2, "fs_resize_bicubic_u8x_many: image %d: pixel_bytes must be 3 (RGB) or 4 (RGBX), got %d", k, it.pixel_bytes);
+        if (it.H < 1 || it.W < 1) return fail(-1, "fs_resize_bicubic_u8x_many: image %d: bad shape %dx%d", k, it.H, it.W);
+        if (it.dst_row < 0 || it.dst_row >= capacity)
+            return fail(-4, "fs_resize_bicubic_u8x_many: image %d: dst_row %d outside the store's %d rows", k, it.dst_row, capacity);
+        const uint64_t bytes = (uint64_t)it.H * (uint64_t)it.W * (uint64_t)it.pixel_bytes;
+        if (it.src_offset > base_bytes || bytes > base_bytes - it.src_offset)
+            return fail(-1, "fs_resize_bicubic_u8x_many: image %d (%dx%dx%d at byte %llu) does not fit the staged %zu bytes", k, it.H, it.W,
+                        it.pixel_bytes, (unsigned long long)it.src_offset, base_bytes);
+    }
+    const int rc = fs::resize_bicubic_u8_many(base, items_dev, K, store, capacity, Ho, Wo, ctx->stream);
+    return rc ? fail(rc, "fs_resize_bicubic_u8x_many: launch failed (%d)", rc) : 0;
+}
+int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
+                  const int32_t* move_dst, int M, float* batch_out) {
+    if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");
+    if (B < 1 || M < 0 || M > B || capacity < 1) return fail(-1, "fs_queue_take: bad counts (B %d, M %d, capacity %d): need 0 <= M <= B, B >= 1", B, M, capacity);
+    if (M > 0 && (!move_src || !move_dst)) return fail(-1, "fs_queue_take: null move table with M = %d", M);
+    if (row_floats == 0 || (row_floats & 3) || row_floats / 4 > 0x7fffffffu) return fail(-2, "fs_queue_take: row_floats must be a positive multiple of 4, got %zu", row_floats);
+    if (((uintptr_t)store & 15) || ((uintptr_t)batch_out & 15) || ((uintptr_t)take_idx & 3) || ((uintptr_t)move_src & 3) || ((uintptr_t)move_dst & 3))
+        return fail(-5, "fs_queue_take: store and batch_out must be 16-byte, the index tables 4-byte aligned");
+    const int rc = fs::queue_take(store, capacity, row_floats, take_idx, B, move_src, move_dst, M, batch_out, ctx->stream);
+    return rc ? fail(rc, "fs_queue_take: launch failed (%d)", rc) : 0;
+}
+int fs_synth_uniform(fs_ctx* ctx, float* out, size_t n, uint64_t seed, uint32_t rank, uint64_t batch_index) {
+    if (!ctx || !out) return fail(-1, "fs_synth_uniform: null argument");
+    if (n == 0 || n > ((size_t)1 << 34)) return fail(-1, "fs_synth_uniform: n must be in [1, 2^34], got %zu", n);
+    if ((uintptr_t)out & 15) return fail(-5, "fs_synth_uniform: out must be 16-byte aligned");
+    const int rc = fs::synth_uniform(out, n, seed, rank, batch_index, ctx->stream);
+    return rc ? fail(rc, "fs_synth_uniform: launch failed (%d)", rc) : 0;
+}
+
 int fs_u8_to_f32(fs_ctx* ctx, const unsigned char* src, size_t n, float* dst) {
     if (!ctx || !src || !dst) return fail(-1, "fs_u8_to_f32: null argument");
     if (((uintptr_t)src & 3) || ((uintptr_t)dst & 15)) return fail(-1, "fs_u8_to_f32: src must be 4-byte, dst 16-byte aligned");

@@ -14,6 +14,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int fs_u32x4 __attribute__((ext_vector_type(4)));   // payload type of raw_buffer_store_b128
 
+struct fs_resize_item;   // include/faststyle_io.h
+
 namespace fs {
 
 // How a conv reads its (virtual) input image.  Padding outside the virtual image is zero.
@@ -635,6 +637,11 @@ int set_error(int code, const char* fmt, ...);
 // tf.image.resize_images(method=2) of TF 1.0 on device u8 [H,W,3] -> f32 [Ho,Wo,3] (fs_io.hip)
 int resize_bicubic_u8(const unsigned char* src, int H, int W, float* dst, int Ho, int Wo, hipStream_t s, int pixel_bytes = 3);
 int u8_to_f32(const unsigned char* src, float* dst, size_t n, hipStream_t s);
+// the device-fed input path (fs_feed.hip; argument checks are in fs_api.hip)
+int resize_bicubic_u8_many(const unsigned char* base, const ::fs_resize_item* items, int K, float* store, int capacity, int Ho, int Wo, hipStream_t s);
+int queue_take(float* store, int capacity, size_t row_floats, const int* take_idx, int B, const int* move_src, const int* move_dst, int M,
+               float* batch_out, hipStream_t s);
+int synth_uniform(float* out, size_t n, unsigned long long seed, unsigned rank, unsigned long long batch_index, hipStream_t s);
 int f32_to_u8(const float* src, unsigned char* dst, size_t npix, int swap_rb, hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);

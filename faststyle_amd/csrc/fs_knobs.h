@@ -53,6 +53,7 @@ namespace fs {
     /* streams */                                                                                                                        \
     X(NO_SIDE_STREAM, 0, "1: a context creates no second stream (no filter-gradient branch, no overlapped chains)")                      \
     X(SIDE_MIN_PIXELS, 1000000, "smallest N * H * W whose fs_tnet_backward forks the filter gradients onto the second stream")           \
+    X(FEED_DEPTH, 2, "train.py: device batches the input path keeps in its ring, produced ahead of the step on a stream of its own; 0: the synchronous path") \
     /* instance norm */                                                                                                                  \
     X(INBWD_REC, 1, "0: instance-norm backward in its three-launch form everywhere")                                                     \
     X(INBWD_FUSED, 1, "0: no partial-sum records from the residual input-gradient epilogues (a pass of its own instead)")                \

@@ -11,6 +11,13 @@ Where each stage runs:
     resident in HBM (4000 x 256x256 images = 3.1 GB of the 288 GB); a batch is a device-side gather.
 
 Data-parallel: rank r reads shards ``files[r::world]`` (no exchange; SURVEY.md §8e).
+
+Two ways from the decoded pixels to a batch:
+  * ``batcher(...)`` (``prefetch=0``): ShuffleQueue -- one upload and one resize launch per image, a gather and up to batch_size row copies
+    per batch, all on the caller's stream;
+  * ``batcher(..., prefetch=D)``: the device-fed path (DeviceRing + FedQueue, kernels in csrc/fs_feed.hip) -- the same batches, bit for bit
+    and in the same order, but every image enqueued since the last take crosses in ONE pinned copy with ONE resize launch, the take is ONE
+    launch, and all of it runs on a side stream into a ring of D batches, ahead of the step.
 """
 import io
 import os
@@ -126,14 +133,271 @@ class ShuffleQueue(object):
         return batch
 
 
+class DeviceRing(object):
+    """``depth`` pre-allocated device batches that producers fill on a side stream while the consumer's stream works on earlier ones.
+
+    Per slot two events: ``ready`` (recorded on the side stream behind the producer's last launch; the consumer's stream waits on it before
+    it reads the batch) and ``free`` (recorded on the consumer's stream once the consumer has enqueued everything that reads the batch; the
+    side stream waits on it before the slot is written again).  The host never waits for either.  ONE host thread issues everything -- the
+    overlap is between streams on the device -- so nothing is launched concurrently with a hipGraph capture on the consumer's side and the
+    (not thread-safe) engine context is only ever used from its own thread.
+
+    A memory provider without streams (the emulator's host arrays) runs the same producers synchronously."""
+
+    def __init__(self, engine, shape, depth):
+        self.eng = engine
+        mem = self.mem = engine.mem
+        self.depth = max(1, int(depth))
+        self.slots = [mem.empty(shape) for _ in range(self.depth)]
+        self.side = None
+        if all(getattr(mem, n, None) is not None for n in ("new_stream", "new_event", "on_stream", "current_stream")):
+            self.side = mem.new_stream()
+            self.side.wait_stream(mem.current_stream())        # (the slots, and whatever the caller allocated before, exist for the side stream)
+            self.ready = [mem.new_event() for _ in range(self.depth)]
+            self.free = [mem.new_event() for _ in range(self.depth)]
+        self._free_recorded = [False] * self.depth
+        self._next = 0
+
+    def run(self, fn):
+        """fn() with the side stream current (no slot involved: e.g. a resize launch between two takes)."""
+        if self.side is None:
+            return fn()
+        with self.mem.on_stream(self.side):
+            return fn()
+
+    def produce(self, fn):
+        """Enqueue fn(slot tensor) on the side stream for the next slot of the ring; returns the slot number."""
+        s = self._next
+        self._next = (s + 1) % self.depth
+        if self.side is None:
+            fn(self.slots[s])
+            return s
+        with self.mem.on_stream(self.side):
+            if self._free_recorded[s]:
+                self.side.wait_event(self.free[s])
+            fn(self.slots[s])
+            self.ready[s].record(self.side)
+        return s
+
+    def hand_over(self, s):
+        if self.side is not None:
+            self.mem.current_stream().wait_event(self.ready[s])
+        return self.slots[s]
+
+    def release(self, s):
+        if self.side is not None:
+            self.free[s].record(self.mem.current_stream())
+            self._free_recorded[s] = True
+
+    def close(self):
+        """Drain: nothing of this ring is queued or running afterwards."""
+        if self.side is not None:
+            self.side.synchronize()
+
+    def feed(self, producers):
+        """Generator of device batches: producers yields callables fn(out) that fill ``out``.  Up to depth - 1 batches are produced ahead of
+        the one the consumer holds; a batch is the consumer's until it asks for the next one."""
+        pending = deque()
+        try:
+            for fn in producers:
+                pending.append(self.produce(fn))
+                if len(pending) == self.depth:
+                    s = pending.popleft()
+                    yield self.hand_over(s)
+                    self.release(s)
+            while pending:
+                s = pending.popleft()
+                yield self.hand_over(s)
+                self.release(s)
+        finally:
+            try:
+                close = getattr(producers, "close", None)
+                if close is not None:
+                    close()
+            finally:
+                self.close()
+
+
+def _align16(n):
+    return (n + 15) & ~15
+
+
+class FedQueue(object):
+    """ShuffleQueue's logic with the device work regrouped: the host keeps the very sequence of ShuffleQueue (slot = size, size += 1 per image;
+    rng.choice + swap-remove, highest index first, per batch) on plain integers, and per batch issues one staging copy (descriptor table, index
+    tables and the pixels of every image enqueued since the last take), one fs_resize_bicubic_u8x_many launch and one fs_queue_take launch
+    through ``ring``.  The swap-remove is resolved on the host: each hole below the new size gets the ORIGINAL row that ends up in it (size 5,
+    remove {2,3}: row 4 -> 3 -> 2 becomes the one move 4 -> 2)."""
+
+    STAGE_CAP_BYTES = 64 << 20      # images waiting for a take are flushed (copy + resize, no take) beyond this: the fill phase stages in pieces
+
+    def __init__(self, engine, capacity, shape, rng, ring):
+        self.eng = engine
+        self.mem = engine.mem
+        self.ring = ring
+        self.capacity = int(capacity)
+        self.shape = tuple(int(s) for s in shape)
+        self.store = self.mem.empty((self.capacity,) + self.shape)
+        if ring.side is not None:
+            ring.side.wait_stream(self.mem.current_stream())
+        self.size = 0
+        self.rng = rng
+        self._pending = []          # [(image, row)]
+        self._pending_bytes = 0
+        self._pinned = getattr(self.mem, "staging_u8", None) is not None and getattr(self.mem, "upload_u8_pinned", None) is not None and ring.side is not None
+        self._n_stage = ring.depth + 1
+        self._stage_next = 0
+        self._stage_event = [None] * self._n_stage
+        self.copies = 0             # staging copies issued (tests: O(1) per batch)
+
+    def enqueue(self, img_u8):
+        assert self.size < self.capacity
+        img_u8 = np.ascontiguousarray(img_u8, dtype=np.uint8)
+        if self._pending and self._pending_bytes + img_u8.nbytes > self.STAGE_CAP_BYTES:
+            self.ring.run(lambda: self._issue(None, None))
+        self._pending.append((img_u8, self.size))
+        self._pending_bytes += _align16(img_u8.nbytes)
+        self.size += 1
+
+    def take(self, n):
+        """The host half of dequeue_many (rng draw, swap-remove on integers); returns fn(out) that issues the device half."""
+        idx = self.rng.choice(self.size, size=n, replace=False)
+        at = {}                      # position -> original row now standing there (positions that changed only)
+        size = self.size
+        for i in sorted((int(v) for v in idx), reverse=True):
+            last = size - 1
+            src = at.pop(last, last)
+            if i != last:
+                at[i] = src
+            size -= 1
+        self.size = size
+        dst = sorted(at)
+        tables = np.concatenate([np.asarray(idx, dtype=np.int32), np.asarray([at[d] for d in dst], dtype=np.int32),
+                                 np.asarray(dst, dtype=np.int32)]).astype(np.int32)
+        return lambda out: self._issue(tables, out)
+
+    def _staging(self, nbytes):
+        """(host array to fill, commit() -> device u8 buffer)."""
+        if not self._pinned:
+            host = np.empty(nbytes, dtype=np.uint8)
+            return host, lambda: self.mem.upload_u8(host)
+        k = self._stage_next
+        self._stage_next = (k + 1) % self._n_stage
+        if self._stage_event[k] is not None:
+            self._stage_event[k].synchronize()         # the copy that last read this pinned buffer: depth + 1 batches back, long done
+        host, pinned, dev = self.mem.staging_u8(k, nbytes)
+
+        def commit():
+            self.mem.upload_u8_pinned(dev, pinned, nbytes)
+            if self._stage_event[k] is None:
+                self._stage_event[k] = self.mem.new_event()
+            self._stage_event[k].record(self.mem.current_stream())
+            return dev
+        return host, commit
+
+    def _issue(self, tables, out):
+        """One staging copy; the resize of the pending images; the take when ``tables`` is given.  Runs with the ring's side stream current."""
+        pending, self._pending, self._pending_bytes = self._pending, [], 0
+        K = len(pending)
+        n_tab = 0 if tables is None else int(tables.size)
+        tab_off = _align16(K * self.eng.RESIZE_ITEM.itemsize)
+        off = _align16(tab_off + 4 * n_tab)
+        items = np.zeros(K, dtype=self.eng.RESIZE_ITEM)
+        for k, (img, row) in enumerate(pending):
+            items[k] = (off, img.shape[0], img.shape[1], img.shape[2], row)
+            off += _align16(img.nbytes)
+        host, commit = self._staging(off)
+        host[:K * items.itemsize] = items.view(np.uint8)
+        if n_tab:
+            host[tab_off:tab_off + 4 * n_tab] = tables.view(np.uint8)
+        for it, (img, _) in zip(items, pending):
+            o = int(it["src_offset"])
+            host[o:o + img.nbytes] = img.reshape(-1)
+        dev = commit()
+        self.copies += 1
+        if K:
+            self.eng.resize_bicubic_u8_many(dev, items, self.store, items_dev=(dev, 0))
+        if tables is not None:
+            B = int(out.shape[0])
+            M = (n_tab - B) // 2
+            self.eng.queue_take(self.store, tables[:B], tables[B:B + M], tables[B + M:], out, tables_dev=(dev, tab_off))
+
+
+def _fed_producers(queue, decoded, batch_size, min_after_dequeue, max_batches):
+    """batcher's loop with the device work handed out as callables (DeviceRing.feed runs them, up to depth - 1 batches ahead)."""
+    produced = 0
+    try:
+        for img in decoded:
+            queue.enqueue(img)
+            while queue.size - batch_size >= min_after_dequeue:
+                yield queue.take(batch_size)
+                produced += 1
+                if max_batches is not None and produced >= max_batches:
+                    return
+        while queue.size >= batch_size:
+            yield queue.take(batch_size)
+            produced += 1
+            if max_batches is not None and produced >= max_batches:
+                return
+    finally:
+        decoded.close()
+
+
+def synthetic_device_batches(engine, batch_size, resize_shape, seed, rank, first, count, depth):
+    """``count`` batches [batch_size,H,W,3] of uniform [0,255) images generated on the device (fs_synth_uniform), batch indices first,
+    first + 1, ...: batch k is a function of (seed, rank, k) alone, so a resumed run continues the stream at its step."""
+    H, W = (int(v) for v in resize_shape)
+    ring = DeviceRing(engine, (batch_size, H, W, 3), depth)
+    return ring.feed((lambda out, k=k: engine.synth_uniform(out, seed, rank, k)) for k in range(first, first + count))
+
+
+def host_batches(engine, arrays, depth):
+    """Host float32 batches (all of one shape) -> device batches through pinned staging and the ring: the copy of batch k + 1 is asynchronous
+    and runs on the side stream under step k.  The values are the host's, untouched."""
+    arrays = iter(arrays)
+    try:
+        head = next(arrays)
+    except StopIteration:
+        return iter(())
+    mem = engine.mem
+    ring = DeviceRing(engine, head.shape, depth)
+    pinned_ok = ring.side is not None and getattr(mem, "staging_u8", None) is not None
+    events = [None] * (ring.depth + 1)
+    state = {"k": 0}
+
+    def producer(a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+
+        def fn(out):
+            if not pinned_ok:
+                out[...] = mem.from_numpy(a)
+                return
+            k = state["k"]
+            state["k"] = (k + 1) % len(events)
+            if events[k] is not None:
+                events[k].synchronize()
+            host, pinned, _ = mem.staging_u8(("host_batches", k), a.nbytes)
+            host[:a.nbytes] = a.reshape(-1).view(np.uint8)
+            mem.upload_u8_pinned(mem.as_u8(out), pinned, a.nbytes)
+            if events[k] is None:
+                events[k] = mem.new_event()
+            events[k].record(mem.current_stream())
+        return fn
+    import itertools
+    return ring.feed(producer(a) for a in itertools.chain([head], arrays))
+
+
 def batcher(filenames, batch_size, resize_shape=None, num_epochs=None, min_after_dequeue=4000, engine=None,
-            seed=0, rank=0, world=1, num_threads=None, max_batches=None):
+            seed=0, rank=0, world=1, num_threads=None, max_batches=None, prefetch=0):
     """Generator of device tensors [batch_size,H,W,3] float32 (RGB 0..255, TF1-bicubic resized).
 
     Same arguments as the reference's ``batcher`` (datapipe.py:55-78) plus the engine that owns the
     device, the shard partition and a seed.  Like tf.train.shuffle_batch it fills the queue to
     ``min_after_dequeue`` before the first batch (capacity = min_after_dequeue + 3*batch_size), and when the
     epochs are exhausted it drains the queue and drops the last partial batch.
+
+    prefetch=D > 0: the device-fed path -- the same batches, produced on a side stream into a ring of D device batches (DeviceRing, FedQueue).
+    A yielded batch is the caller's until it asks for the next one; closing the generator drains the side stream.
     """
     if engine is None:
         raise L.FaststyleError("datapipe.batcher needs the Engine that owns the device (no CPU resize path)")
@@ -147,9 +411,19 @@ def batcher(filenames, batch_size, resize_shape=None, num_epochs=None, min_after
     H, W = (int(v) for v in resize_shape)
     rng = np.random.default_rng(seed + 7919 * rank)
     capacity = min_after_dequeue + 3 * batch_size                      # datapipe.py:73
-    queue = ShuffleQueue(engine, capacity, (H, W, 3), rng)
     threads = num_threads or min(32, max(4, (os.cpu_count() or 8) // max(1, world)))
     decoded = _prefetch_map(lambda d: decode_jpeg(d, packed=False), _examples(files, num_epochs, rng), threads, window=4 * threads)
+    if prefetch and prefetch > 0:
+        ring = DeviceRing(engine, (batch_size, H, W, 3), prefetch)
+        queue = FedQueue(engine, capacity, (H, W, 3), rng, ring)
+        fed = ring.feed(_fed_producers(queue, decoded, batch_size, min_after_dequeue, max_batches))
+        try:
+            for batch in fed:
+                yield batch
+        finally:
+            fed.close()          # (also when the caller stops early: drains the side stream)
+        return
+    queue = ShuffleQueue(engine, capacity, (H, W, 3), rng)
     produced = 0
     for img in decoded:
         queue.enqueue_resized(img)

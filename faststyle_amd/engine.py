@@ -68,6 +68,41 @@ class TorchMem(object):
     def copy_row(self, store, src, dst):
         store[dst].copy_(store[src])
 
+    # ---- device-fed input path (datapipe.DeviceRing): a side stream, events, pinned staging
+    def new_stream(self):
+        return self.torch.cuda.Stream(self.device)
+
+    def new_event(self):
+        return self.torch.cuda.Event()
+
+    def current_stream(self):
+        return self.torch.cuda.current_stream(self.device)
+
+    def on_stream(self, stream):
+        return self.torch.cuda.stream(stream)
+
+    def staging_u8(self, slot, nbytes):
+        """Staging pair number ``slot``: (numpy view of a pinned host buffer, that buffer, a device buffer), each of at least nbytes bytes.  The
+        pair is kept and reused; it grows (by half again at least) when a request does not fit.  The caller owns the ordering: a pinned buffer
+        is refilled only after the event behind its last copy has completed."""
+        pool = self.__dict__.setdefault("_staging", {})
+        have = pool.get(slot)
+        if have is None or have[1].numel() < nbytes:
+            n = max(int(nbytes), (have[1].numel() * 3) // 2 if have else 0, 1 << 20)
+            pinned = self.torch.empty(n, dtype=self.torch.uint8, pin_memory=True)
+            have = pool[slot] = (pinned.numpy(), pinned, self.torch.empty(n, dtype=self.torch.uint8, device=self.device))
+        return have
+
+    def upload_u8_pinned(self, dst_device, pinned, nbytes):
+        """Asynchronous host-to-device copy on the current stream: pinned[:nbytes] -> dst_device[:nbytes] (both flat uint8).  The host does not
+        wait for the stream, unlike upload_u8 from pageable memory."""
+        dst_device[:nbytes].copy_(pinned[:nbytes], non_blocking=True)
+        return dst_device
+
+    def as_u8(self, t):
+        """Flat uint8 view of a contiguous device tensor (the destination of upload_u8_pinned for float data)."""
+        return t.view(-1).view(self.torch.uint8)
+
 
 def default_loss_cfg():
     """train.py:52-70 defaults: content conv3_3 x1.0; style conv1_2/2_2/3_3/4_3 x5.0."""
@@ -580,6 +615,55 @@ class Engine(object):
         else:
             L.check(self.lib, self.lib.fs_resize_bicubic_u8x(self.ctx, self.mem.ptr_u8(src), H, W, 4, self.mem.ptr(out), Ho, Wo),
                     "fs_resize_bicubic_u8x")
+        return out
+
+    # ------------------------------------------------------------------ device-fed input path (csrc/fs_feed.hip)
+    RESIZE_ITEM = np.dtype([("src_offset", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pixel_bytes", "<i4"), ("dst_row", "<i4")])   # fs_resize_item
+
+    def _table_ptr(self, table, dev):
+        """Device address of an integer table: ``dev`` = (device u8 buffer, byte offset) where the caller has staged it already, else it is
+        uploaded here.  Returns (address, keep-alive)."""
+        if dev is not None:
+            return self.mem.ptr_u8(dev[0]) + int(dev[1]), dev[0]
+        up = self.mem.upload_u8(np.ascontiguousarray(table).view(np.uint8).reshape(-1))
+        return self.mem.ptr_u8(up), up
+
+    def resize_bicubic_u8_many(self, staged, items, store, items_dev=None):
+        """K resize_bicubic_u8 calls in one launch (fs_resize_bicubic_u8x_many).  staged: device uint8 buffer holding the decoded images;
+        items: host array of RESIZE_ITEM rows (where each image lies, its shape, its row of ``store``); store: device float32
+        [capacity,Ho,Wo,3].  items_dev: (device u8 buffer, byte offset) of a copy of ``items`` already on the device."""
+        self._sync_stream()
+        items = np.ascontiguousarray(items, dtype=self.RESIZE_ITEM)
+        capacity, Ho, Wo, C = (int(s) for s in store.shape)
+        assert C == 3
+        ptr, keep = self._table_ptr(items, items_dev)
+        L.check(self.lib, self.lib.fs_resize_bicubic_u8x_many(self.ctx, self.mem.ptr_u8(staged), int(np.prod(staged.shape)), items.ctypes.data, ptr,
+                                                              int(items.shape[0]), self.mem.ptr(store), capacity, Ho, Wo),
+                "fs_resize_bicubic_u8x_many")
+        self._keep = [keep, items]
+        return store
+
+    def queue_take(self, store, take_idx, move_src, move_dst, out, tables_dev=None):
+        """tf.RandomShuffleQueue.dequeue_many in one launch (fs_queue_take): out[i] = store[take_idx[i]], then store[move_dst[j]] =
+        store[move_src[j]].  tables_dev: (device u8 buffer, byte offset) of the three int32 tables back to back, staged by the caller."""
+        self._sync_stream()
+        take_idx, move_src, move_dst = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (take_idx, move_src, move_dst))
+        B, M = int(take_idx.size), int(move_src.size)
+        assert int(move_dst.size) == M
+        capacity = int(store.shape[0])
+        row = int(np.prod(store.shape[1:]))
+        assert int(np.prod(out.shape)) == B * row
+        ptr, keep = self._table_ptr(np.concatenate([take_idx, move_src, move_dst]), tables_dev)
+        L.check(self.lib, self.lib.fs_queue_take(self.ctx, self.mem.ptr(store), capacity, row, ptr, B, ptr + 4 * B if M else None,
+                                                 ptr + 4 * (B + M) if M else None, M, self.mem.ptr(out)), "fs_queue_take")
+        self._keep = [keep]
+        return out
+
+    def synth_uniform(self, out, seed, rank, batch_index):
+        """Uniform [0,255) float32 values into ``out``: Philox4x32-10 keyed by seed, counter (element block, batch_index, rank) (fs_synth_uniform)."""
+        self._sync_stream()
+        L.check(self.lib, self.lib.fs_synth_uniform(self.ctx, self.mem.ptr(out), int(np.prod(out.shape)), int(seed) & (2 ** 64 - 1),
+                                                    int(rank) & 0xFFFFFFFF, int(batch_index) & (2 ** 64 - 1)), "fs_synth_uniform")
         return out
 
     def u8_to_f32(self, src_u8, dst):

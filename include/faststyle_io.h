@@ -62,6 +62,43 @@ int fs_resize_bicubic_u8x(fs_ctx* ctx, const unsigned char* src, int H, int W, i
 int fs_u8_to_f32(fs_ctx* ctx, const unsigned char* src, size_t n, float* dst);
 int fs_f32_to_u8(fs_ctx* ctx, const float* src, size_t npix, int swap_rb, unsigned char* dst);
 
+/* ---- Device-fed training input path (csrc/fs_feed.hip; faststyle_amd/datapipe.py runs these on a side stream, ahead of the step).
+ * All three are asynchronous on the ctx stream, allocate nothing and can be captured into a hipGraph. */
+
+/* One image of fs_resize_bicubic_u8x_many: H x W pixels of pixel_bytes (3 = RGB, 4 = RGBX) bytes each, starting src_offset bytes into the
+ * staged buffer, resized into row dst_row of the destination store.  24 bytes, 8-byte aligned. */
+typedef struct fs_resize_item {
+    uint64_t src_offset;
+    int32_t H, W;
+    int32_t pixel_bytes;
+    int32_t dst_row;
+} fs_resize_item;
+
+/* K fs_resize_bicubic_u8x calls in ONE launch: image k of the staged device buffer `base` (base_bytes long) goes to store[dst_row[k]] of the
+ * device store [capacity,Ho,Wo,3] float32, bit-identical to the single-image call.  The descriptor table is passed twice: items_host is read
+ * by this call (checks, nothing else -- it may be freed on return), items_dev is the copy the kernel reads (the same pointer where host memory
+ * is device-visible).  Errors: -1 null argument / K <= 0 / bad shape / an image outside base_bytes, -2 a pixel_bytes other than 3 or 4,
+ * -4 a dst_row outside [0, capacity), -5 items_dev not 8-byte aligned. */
+int fs_resize_bicubic_u8x_many(fs_ctx* ctx, const unsigned char* base, size_t base_bytes, const fs_resize_item* items_host,
+                               const fs_resize_item* items_dev, int K, float* store, int capacity, int Ho, int Wo);
+
+/* tf.RandomShuffleQueue.dequeue_many on the device store [capacity, row_floats] in ONE launch:
+ *   batch_out[i] = store[take_idx[i]]  (i < B)   and   store[move_dst[j]] = store[move_src[j]]  (j < M, 0 <= M <= B).
+ * take_idx, move_src, move_dst: device int32 tables.  The caller resolves the swap-remove: the move_dst rows are the holes (taken rows) below
+ * the new size, every move_src row lies at or above it, is not taken and is nobody's destination.  A hole is gathered before it is
+ * back-filled (by the same workgroup); an index outside [0, capacity) moves nothing.  row_floats: a multiple of 4; store and batch_out
+ * 16-byte aligned.  Errors: -1 null argument / B < 1 / M outside [0, B] / capacity < 1, -2 row_floats not a positive multiple of 4,
+ * -5 a misaligned pointer. */
+int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
+                  const int32_t* move_dst, int M, float* batch_out);
+
+/* Uniform [0, 255) float32 images on the device: element e of out[0, n) is word (e & 3) of the Philox4x32-10 block with counter
+ * (e >> 2, batch_index low, batch_index high, rank) and key (seed low, seed high), mapped by float(word >> 8) * 2^-24 * 255.0f (both products
+ * rounded separately; the largest value is 254.99998).  A pure function of its arguments: independent of the launch geometry, so a resumed
+ * run asks for batch `global_step` and continues the stream.  out: 16-byte aligned.  Errors: -1 null argument / n == 0 / n > 2^34,
+ * -5 misaligned out. */
+int fs_synth_uniform(fs_ctx* ctx, float* out, size_t n, uint64_t seed, uint32_t rank, uint64_t batch_index);
+
 #ifdef __cplusplus
 }
 #endif

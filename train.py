@@ -12,8 +12,15 @@ Differences from the reference that are forced by the environment and stated, no
     tfrecords_writer.py (read by faststyle_amd/datapipe.py: native record/Example reader, threaded
     JPEG decode, TF1-bicubic resize kernel, HBM-resident shuffle queue of ``--num_pipe_buffer``
     images).  Two conveniences on top: a directory of plain JPEG/PNG files (PIL decode + PIL
-    bicubic), and the literal ``synthetic`` (uniform [0,255) images, MS-COCO train2014 count
-    82,783 per epoch) for benchmarking without a dataset;
+    bicubic), and the literals ``synthetic`` (uniform [0,255) images drawn with numpy on the host,
+    MS-COCO train2014 count 82,783 per epoch) and ``synthetic:device`` (the same count, drawn on the
+    GPU by fs_synth_uniform as a function of (seed 1234, rank, step): with ``--resume_from`` the stream
+    continues at the restored step and the run does the REMAINING steps, so an interrupted and resumed
+    run ends with the parameters of an uninterrupted one) for benchmarking without a dataset;
+  * batches reach the step through a ring of FS_FEED_DEPTH (default 2) device batches that a side
+    stream fills ahead of the step (faststyle_amd/datapipe.py: DeviceRing; shards, ``synthetic`` and
+    ``synthetic:device``).  The batches are the same, bit for bit; FS_FEED_DEPTH=0 is the synchronous
+    path on the training stream;
   * next to the TensorBoard event file (``summaries/train/<run_name>/events.out.tfevents.*`` with the
     reference's four scalars ``summaries/{loss,style_loss,content_loss,tv_loss}`` at the same steps,
     train.py:185-189, 260-272; no graph definition in it) the same values go to ``scalars.jsonl``.
@@ -82,7 +89,7 @@ def batcher(train_dir, batch_size, resize, n_epochs, buffer_size, seed, rank, wo
 def main(args):
     import torch
     import torch.distributed as dist
-    from faststyle_amd import ckpt, datapipe, engine, im_transf_net, tbevents, trainer, utils, vgg16
+    from faststyle_amd import _lib, ckpt, datapipe, engine, im_transf_net, tbevents, trainer, utils, vgg16
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -135,13 +142,16 @@ def main(args):
         # full: saver = tf.train.Saver() -- all variables incl. Adam slots and global_step (train.py:224)
         ckpt.save_checkpoint(prefix, tr.state_tensors(full=full))
 
+    step0 = 0
     if args.resume_from:
         step0 = tr.load_state(ckpt.load_checkpoint(args.resume_from))
         if rank == 0:
             print('Resumed from %s at step %d.' % (args.resume_from, step0))
 
     # Input pipeline (train.py:192-196): TFRecord shards train-* when present
-    shards = sorted(glob.glob(os.path.join(args.train_dir, 'train-*'))) if args.train_dir != 'synthetic' else []
+    literal = args.train_dir in ('synthetic', 'synthetic:device')
+    shards = sorted(glob.glob(os.path.join(args.train_dir, 'train-*'))) if not literal else []
+    feed_depth = _lib.knob(eng.lib, "FS_FEED_DEPTH")       # ring depth of the device-fed input path; 0: the synchronous path
 
     def common_step_count(n_local):
         """Ranks read disjoint shards / files of unequal size: every rank must run the SAME number of steps, or the
@@ -160,14 +170,21 @@ def main(args):
         cap = common_step_count(datapipe.count_records(shards[rank::world]) * args.n_epochs // args.batch_size)
         batches = datapipe.batcher(shards, args.batch_size, args.preprocess_size, args.n_epochs,
                                    args.num_pipe_buffer, engine=eng, seed=1234, rank=rank, world=world,
-                                   max_batches=cap)
+                                   max_batches=cap, prefetch=max(0, feed_depth))
+    elif args.train_dir == 'synthetic:device':
+        total = COCO_TRAIN2014 * args.n_epochs // world // args.batch_size          # the step count of `synthetic`
+        batches = datapipe.synthetic_device_batches(eng, args.batch_size, args.preprocess_size, 1234, rank, step0,
+                                                    max(0, total - step0), max(1, feed_depth))
     else:
         gen = batcher(args.train_dir, args.batch_size, args.preprocess_size, args.n_epochs, args.num_pipe_buffer, 1234, rank, world)
         if args.train_dir != 'synthetic':   # a directory of image files, dealt files[rank::world]: counts differ by up to one image
             n_files = len([f for f in os.listdir(args.train_dir) if f.lower().endswith((".jpg", ".jpeg", ".png"))])
             n_mine = len(range(rank, n_files, world))
             gen = itertools.islice(gen, common_step_count(n_mine * args.n_epochs // args.batch_size))
-        batches = (eng.mem.from_numpy(b) for b in gen)
+        if args.train_dir == 'synthetic' and feed_depth > 0:      # the host's values, untouched; the upload is pinned and asynchronous
+            batches = datapipe.host_batches(eng, gen, feed_depth)
+        else:
+            batches = (eng.mem.from_numpy(b) for b in gen)
     if rank == 0:
         print('Starting training...')
     clean_exit = False        # the loop ended the same way on every rank (epochs exhausted / num_steps_break)
@@ -198,6 +215,12 @@ def main(args):
                 print('Done training.')
         clean_exit = True
     finally:
+        # the input path first: nothing of it stays queued on its side stream whichever way the loop ended
+        try:
+            batches.close()
+        except Exception:
+            import traceback
+            traceback.print_exc()
         # Save the model (the image transformation network) for later usage (train.py:283-286)
         try:
             if rank == 0:
