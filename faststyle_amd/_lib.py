@@ -60,6 +60,16 @@ class fs_conv_desc(Structure):
                 ("w_wino6", c_void_p), ("w6_ws", c_void_p), ("w6_ws_bytes", ctypes.c_size_t)]
 
 
+class fs_jpeg_info(Structure):
+    """include/faststyle_io.h: what fs_jpeg_parse reports of a handled JPEG."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32),
+                ("hs", ctypes.c_int32 * 3), ("vs", ctypes.c_int32 * 3), ("tq", ctypes.c_int32 * 3),
+                ("mcu_x", ctypes.c_int32), ("mcu_y", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
+                ("blocks_x", ctypes.c_int32 * 3), ("blocks_y", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32),
+                ("scan_offset", c_uint64), ("plane_offset", c_uint64 * 3), ("qt_offset", c_uint64), ("coef_count", c_uint64),
+                ("coef_bytes", c_uint64), ("rgb_bytes", c_uint64)]
+
+
 class fs_wgrad_desc(Structure):
     _fields_ = [("x", c_void_p), ("dy", c_void_p), ("dw", c_void_p),
                 ("N", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int),
@@ -152,6 +162,9 @@ PROTOTYPES = {
     "fs_resize_bicubic_u8x_many": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
     "fs_queue_take": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fs_synth_uniform": (c_int, [c_void_p, c_void_p, c_size_t, c_uint64, c_uint32, c_uint64]),
+    "fs_jpeg_parse": (c_int, [c_void_p, c_size_t, POINTER(fs_jpeg_info)]),
+    "fs_jpeg_decode": (c_int, [c_void_p, c_size_t, POINTER(fs_jpeg_info), c_void_p, c_size_t]),
+    "fs_jpeg_reconstruct_many": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     "fs_u8_to_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "fs_f32_to_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
 }

@@ -130,6 +130,31 @@ int fs_resize_bicubic_u8x_many(fs_ctx* ctx, const unsigned char* base, size_t ba
     const int rc = fs::resize_bicubic_u8_many(base, items_dev, K, store, capacity, Ho, Wo, ctx->stream);
     return rc ? fail(rc, "fs_resize_bicubic_u8x_many: launch failed (%d)", rc) : 0;
 }
+int fs_jpeg_reconstruct_many(fs_ctx* ctx, void* coef_base, size_t coef_bytes, const fs_jpeg_item* items_host, const fs_jpeg_item* items_dev, int K,
+                             void* rgb_base, size_t rgb_bytes) {
+    if (!ctx || !coef_base || !items_host || !items_dev || !rgb_base) return fail(-1, "fs_jpeg_reconstruct_many: null argument");
+    if (K < 1 || K > 65535) return fail(-1, "fs_jpeg_reconstruct_many: K must be in [1, 65535], got %d", K);
+    if ((uintptr_t)items_dev & 7) return fail(-5, "fs_jpeg_reconstruct_many: the descriptor table must be 8-byte aligned");
+    if (((uintptr_t)coef_base & 15) || ((uintptr_t)rgb_base & 3)) return fail(-5, "fs_jpeg_reconstruct_many: coef_base must be 16-byte, rgb_base 4-byte aligned");
+    unsigned long long max_blocks = 0, max_groups = 0;
+    for (int k = 0; k < K; ++k) {
+        const fs_jpeg_item& it = items_host[k];
+        const int rc = fs::jpeg_item_check(it, coef_bytes, rgb_bytes);
+        if (rc == -2) return fail(-2, "fs_jpeg_reconstruct_many: image %d: pixel_bytes must be 3 (RGB) or 4 (RGBX), got %d", k, it.pixel_bytes);
+        if (rc == -5)
+            return fail(-5, "fs_jpeg_reconstruct_many: image %d: coef_offset and qt_offset must be multiples of 16, dst_offset of 4 with 4-byte pixels", k);
+        if (rc)
+            return fail(rc, "fs_jpeg_reconstruct_many: image %d (%dx%d, %d components, %dx%d sampling) has a bad geometry or does not fit the %zu coefficient / %zu pixel bytes",
+                        k, it.width, it.height, it.ncomp, it.hs, it.vs, coef_bytes, rgb_bytes);
+        unsigned long long b, g;
+        fs::jpeg_item_extent(it, &b, &g);
+        max_blocks = b > max_blocks ? b : max_blocks;
+        max_groups = g > max_groups ? g : max_groups;
+    }
+    const int rc = fs::jpeg_reconstruct_many(static_cast<unsigned char*>(coef_base), coef_bytes, items_dev, K, max_blocks, max_groups,
+                                             static_cast<unsigned char*>(rgb_base), rgb_bytes, ctx->stream);
+    return rc ? fail(rc, "fs_jpeg_reconstruct_many: launch failed (%d)", rc) : 0;
+}
 int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
                   const int32_t* move_dst, int M, float* batch_out) {
     if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");

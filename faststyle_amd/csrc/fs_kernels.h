@@ -15,6 +15,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int fs_u32x4 __attribute__((ext_vector_type(4)));   // payload type of raw_buffer_store_b128
 
 struct fs_resize_item;   // include/faststyle_io.h
+struct fs_jpeg_item;
 
 namespace fs {
 
@@ -643,6 +644,12 @@ int queue_take(float* store, int capacity, size_t row_floats, const int* take_id
                float* batch_out, hipStream_t s);
 int synth_uniform(float* out, size_t n, unsigned long long seed, unsigned rank, unsigned long long batch_index, hipStream_t s);
 int f32_to_u8(const float* src, unsigned char* dst, size_t npix, int swap_rb, hipStream_t s);
+// the device half of the JPEG decoder (fs_jpeg.hip): the descriptor check shared by fs_jpeg_reconstruct_many and the kernels (0 or that call's
+// error code), one image's block and 8-pixel-group counts, and the two launches
+__host__ __device__ int jpeg_item_check(const ::fs_jpeg_item& it, unsigned long long coef_bytes, unsigned long long rgb_bytes);
+void jpeg_item_extent(const ::fs_jpeg_item& it, unsigned long long* blocks, unsigned long long* groups);
+int jpeg_reconstruct_many(unsigned char* coef_base, size_t coef_bytes, const ::fs_jpeg_item* items_dev, int K, unsigned long long max_blocks,
+                          unsigned long long max_groups, unsigned char* rgb_base, size_t rgb_bytes, hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);
 // ... with the per-sample sums taken from records [N][T][C][2] (rec == nullptr: computed here into `scratch`), reduced in the apply kernel's

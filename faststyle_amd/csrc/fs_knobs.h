@@ -54,6 +54,7 @@ namespace fs {
     X(NO_SIDE_STREAM, 0, "1: a context creates no second stream (no filter-gradient branch, no overlapped chains)")                      \
     X(SIDE_MIN_PIXELS, 1000000, "smallest N * H * W whose fs_tnet_backward forks the filter gradients onto the second stream")           \
     X(FEED_DEPTH, 2, "train.py: device batches the input path keeps in its ring, produced ahead of the step on a stream of its own; 0: the synchronous path") \
+    X(FEED_JPEG, 0, "train.py: 1: baseline JPEGs are decoded by the library on the device-fed path (fs_jpeg.hip: Huffman pass on the decode threads, reconstruction on the GPU); 0: PIL") \
     /* instance norm */                                                                                                                  \
     X(INBWD_REC, 1, "0: instance-norm backward in its three-launch form everywhere")                                                     \
     X(INBWD_FUSED, 1, "0: no partial-sum records from the residual input-gradient epilogues (a pass of its own instead)")                \

@@ -110,7 +110,27 @@ def default_loss_cfg():
                 style_layers=["conv1_2", "conv2_2", "conv3_3", "conv4_3"], style_weights=[5.0] * 4, beta=0.0)
 
 
-class Engine(object):
+class JpegHost(object):
+    """The two host calls of the JPEG decoder (csrc/fs_jpeg.hip).  They need the library and no device: the engine has them through this
+    class, and a tool that measures the host half alone makes a JpegHost of its own."""
+
+    def __init__(self, lib=None):
+        self.lib = lib if lib is not None else L.load()
+
+    def jpeg_parse(self, data):
+        """(answer, info) of fs_jpeg_parse for the bytes of a JPEG file: 0 handled (info: an fs_jpeg_info), 1 not taken by this decoder
+        (PIL's), negative malformed; info is None unless handled.  Host code: needs no device, may be called from any thread."""
+        info = L.fs_jpeg_info()
+        rc = self.lib.fs_jpeg_parse(data, len(data), ctypes.byref(info))
+        return rc, (info if rc == 0 else None)
+
+    def jpeg_decode(self, data, info, out_addr, out_bytes):
+        """fs_jpeg_decode: the Huffman pass of a handled JPEG into info.coef_bytes bytes at host address out_addr; returns its answer
+        (0, or what makes the caller decode the file with PIL).  Releases the interpreter lock; any number of threads at once."""
+        return self.lib.fs_jpeg_decode(data, len(data), ctypes.byref(info), ctypes.c_void_p(out_addr), out_bytes)
+
+
+class Engine(JpegHost):
     # Workspaces are cached per shape (a backward must find the workspace its forward filled; a captured hipGraph replays raw
     # pointers into its own).  The cache is bounded by BYTES, least recently used first: stylizing a directory of mixed
     # resolutions must not pile up one multi-GB workspace per size.  Entries a live hipGraph replays into are pinned by
@@ -658,6 +678,27 @@ class Engine(object):
                                                  ptr + 4 * (B + M) if M else None, M, self.mem.ptr(out)), "fs_queue_take")
         self._keep = [keep]
         return out
+
+    # ------------------------------------------------------------------ baseline JPEG decoding (csrc/fs_jpeg.hip)
+    JPEG_ITEM = np.dtype([("coef_offset", "<u8"), ("qt_offset", "<u8"), ("dst_offset", "<u8"), ("width", "<i4"), ("height", "<i4"),
+                          ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("pixel_bytes", "<i4")])      # fs_jpeg_item
+
+    @classmethod
+    def jpeg_item(cls, info, coef_offset, dst_offset, pixel_bytes):
+        """The JPEG_ITEM row of an image that fs_jpeg_decode wrote at byte coef_offset of the coefficient buffer."""
+        return (coef_offset, coef_offset + info.qt_offset, dst_offset, info.width, info.height, info.ncomp, info.hs[0], info.vs[0], pixel_bytes)
+
+    def jpeg_reconstruct_many(self, coef, items, rgb, items_dev=None):
+        """fs_jpeg_reconstruct_many: coef, rgb device uint8 buffers; items host JPEG_ITEM rows; the u8 pixels of every image are written into
+        ``rgb`` where its row says.  ``coef`` is working memory (its coefficients are consumed).  items_dev as for resize_bicubic_u8_many."""
+        self._sync_stream()
+        items = np.ascontiguousarray(items, dtype=self.JPEG_ITEM)
+        ptr, keep = self._table_ptr(items, items_dev)
+        L.check(self.lib, self.lib.fs_jpeg_reconstruct_many(self.ctx, self.mem.ptr_u8(coef), int(np.prod(coef.shape)), items.ctypes.data, ptr,
+                                                            int(items.shape[0]), self.mem.ptr_u8(rgb), int(np.prod(rgb.shape))),
+                "fs_jpeg_reconstruct_many")
+        self._keep = [keep, items]
+        return rgb
 
     def synth_uniform(self, out, seed, rank, batch_index):
         """Uniform [0,255) float32 values into ``out``: Philox4x32-10 keyed by seed, counter (element block, batch_index, rank) (fs_synth_uniform)."""

@@ -4,9 +4,12 @@
  *   datapipe.py:38-49   tf.TFRecordReader().read + tf.parse_single_example   -> fs_tfrecord_scan, fs_example_bytes/_int64
  *   datapipe.py:24      tf.image.resize_images(image, size, method=2)          -> fs_resize_bicubic_u8 (device kernel)
  *   tfrecords_writer.py:217-239  tf.python_io.TFRecordWriter.write             -> fs_tfrecord_frame
- * JPEG entropy decoding stays on the host (libjpeg through PIL, several threads); everything after
- * the decoded u8 pixels runs on the GPU: the image is uploaded as u8 (a quarter of the fp32 bytes over
- * PCIe), resized by the TF1 bicubic kernel straight into the HBM-resident shuffle buffer.
+ * JPEG decoding: by default libjpeg through PIL on several host threads, the decoded u8 pixels uploaded (a quarter of the fp32
+ * bytes over PCIe) and resized by the TF1 bicubic kernel straight into the HBM-resident shuffle buffer.  On the device-fed path the
+ * library can decode baseline JPEGs itself (FS_FEED_JPEG=1, the fs_jpeg_* calls below): only the serial part, marker parsing and Huffman
+ * decoding, stays on the host threads (fs_jpeg_parse / fs_jpeg_decode, no Python work around it); the int16 coefficients cross PCIe and
+ * dequantisation, inverse DCT, chroma upsampling and colour conversion run on the GPU (fs_jpeg_reconstruct_many), bit-identical to PIL's
+ * decode of the same bytes.  A JPEG outside the handled set is PIL's, as before.
  *
  * The host-side functions are pure C (no HIP calls) and work without a GPU.  All return 0 / a
  * non-negative count on success and a negative code on error (fs_last_error() has the text).
@@ -98,6 +101,76 @@ int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, co
  * run asks for batch `global_step` and continues the stream.  out: 16-byte aligned.  Errors: -1 null argument / n == 0 / n > 2^34,
  * -5 misaligned out. */
 int fs_synth_uniform(fs_ctx* ctx, float* out, size_t n, uint64_t seed, uint32_t rank, uint64_t batch_index);
+
+/* ---- Baseline JPEG decoding (csrc/fs_jpeg.hip): the host half works without a GPU, keeps no global state (any number of threads may
+ * decode at once) and allocates nothing. */
+
+/* What fs_jpeg_parse found in a handled JPEG, and where fs_jpeg_decode puts it.  The coefficient buffer of an image is coef_bytes long:
+ * component c's plane starts at plane_offset[c] and holds blocks_y[c] rows of blocks_x[c] blocks (the component padded to whole MCUs), a block
+ * being 64 int16 quantised coefficients in natural (de-zigzagged, row-major) order; coef_count int16 in all.  At qt_offset (a multiple of 16)
+ * follow three tables of 64 uint16, natural order: the quantisation table of component 0, 1, 2 (zeros beyond ncomp).  All sizes in bytes
+ * unless named otherwise.  No implicit padding: 22 int32, then uint64. */
+typedef struct fs_jpeg_info {
+    int32_t width, height;
+    int32_t ncomp;                     /* 1 (grayscale) or 3 (YCbCr) */
+    int32_t hs[3], vs[3];              /* sampling factors: component 0 is 1x1, 2x1 or 2x2, the chroma components 1x1 */
+    int32_t tq[3];                     /* quantisation table each component names */
+    int32_t mcu_x, mcu_y;              /* MCU grid */
+    int32_t restart_interval;          /* MCUs between RSTn markers; 0: none */
+    int32_t blocks_x[3], blocks_y[3];
+    int32_t reserved;
+    uint64_t scan_offset;              /* first byte of the entropy-coded data within the file */
+    uint64_t plane_offset[3];
+    uint64_t qt_offset;
+    uint64_t coef_count;
+    uint64_t coef_bytes;               /* what fs_jpeg_decode writes: qt_offset + 384 */
+    uint64_t rgb_bytes;                /* width * height * 3 */
+} fs_jpeg_info;
+
+/* Reads the markers of a JPEG file image up to its scan.  Returns
+ *    0  handled: *info is filled;
+ *    1  a JPEG this decoder does not take (not an error: the caller decodes it with PIL);
+ *  < 0  malformed (-1 not a JPEG / truncated / null argument, -2 a bad segment).
+ * Handled: SOF0, or SOF1 with 8-bit samples; Huffman coded; ONE scan with all components (interleaved, or the single component of a grayscale
+ * file); luma sampled 1x1, 2x1 or 2x2 against 1x1 chroma; YCbCr by the JFIF rule (a JFIF marker, or component ids 1, 2, 3) and no Adobe marker;
+ * restart intervals; any Huffman tables (up to four per class, several per segment); 8-bit quantisation tables.  Everything else answers 1:
+ * progressive, arithmetic, lossless, 12-bit, 16-bit quantisation tables, CMYK / Adobe files, 4:4:0 and other sampling factors, several scans,
+ * a height given by DNL, tables left for the decoder to supply. */
+int fs_jpeg_parse(const void* jpeg, size_t n, fs_jpeg_info* info);
+
+/* Huffman-decodes the scan of a handled JPEG (info: what fs_jpeg_parse filled from the same bytes) into out[0, info->coef_bytes), laid out as
+ * described at fs_jpeg_info.  Every read is checked against n, every code against its table; the call writes only inside out[0, coef_bytes).
+ * Stricter than a viewer: whatever is not a complete, well-formed scan followed by EOI is an error, and the caller decodes that file the way it
+ * did before.  Returns 0, 1 (as fs_jpeg_parse), or < 0: -1 / -2 as fs_jpeg_parse or an info / out_bytes that does not fit, -4 corrupt or
+ * truncated scan data, -5 out not 2-byte aligned. */
+int fs_jpeg_decode(const void* jpeg, size_t n, const fs_jpeg_info* info, void* out, size_t out_bytes);
+
+/* One image of fs_jpeg_reconstruct_many: its coefficient planes start coef_offset bytes into coef_base (laid out as fs_jpeg_decode writes them
+ * for this geometry) and its three quantisation tables qt_offset bytes into coef_base (for a buffer written by fs_jpeg_decode at byte o:
+ * coef_offset = o, qt_offset = o + info.qt_offset); both multiples of 16.  hs, vs: the luma sampling factors (info.hs[0], info.vs[0]).  The
+ * pixels go to rgb_base + dst_offset, height rows of width pixels of pixel_bytes bytes (3 = RGB, 4 = RGBX with dst_offset a multiple of 4), no
+ * row padding: what an fs_resize_item with the same offset, shape and pixel_bytes describes.  48 bytes, 8-byte aligned. */
+typedef struct fs_jpeg_item {
+    uint64_t coef_offset;
+    uint64_t qt_offset;
+    uint64_t dst_offset;
+    int32_t width, height;
+    int32_t ncomp;
+    int32_t hs, vs;
+    int32_t pixel_bytes;
+} fs_jpeg_item;
+
+/* Dequantisation, inverse DCT, chroma upsampling and colour conversion of K images in one launch sequence (two kernels), in the integer
+ * arithmetic of the IJG library's default decoder (accurate integer DCT, "fancy" triangle upsampling, 16-bit fixed-point YCbCr -> RGB): the
+ * pixels PIL gives for the same file, bit for bit.  coef_base is WORKING memory: each block's coefficients are replaced by its samples, so a
+ * region is reconstructed once.  The descriptor table is passed twice, as for fs_resize_bicubic_u8x_many (items_host is only checked).
+ * Asynchronous on the ctx stream, allocates nothing, can be captured into a hipGraph.  No value of the coefficient data reaches an address: a
+ * corrupt file that still decoded gives wrong pixels, nothing else; a descriptor the check refuses is skipped by the kernels too.
+ * Errors: -1 null argument / K outside [1, 65535] / a bad geometry / an image outside coef_bytes or rgb_bytes, -2 a pixel_bytes other than 3
+ * or 4, -5 items_dev not 8-byte aligned, coef_base or an image's coef_offset / qt_offset not 16-byte aligned, rgb_base or (4-byte pixels) a
+ * dst_offset not 4-byte aligned. */
+int fs_jpeg_reconstruct_many(fs_ctx* ctx, void* coef_base, size_t coef_bytes, const fs_jpeg_item* items_host, const fs_jpeg_item* items_dev,
+                             int K, void* rgb_base, size_t rgb_bytes);
 
 #ifdef __cplusplus
 }

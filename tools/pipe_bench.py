@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Throughput of the TFRecord input pipeline alone (decode threads + GPU resize + HBM shuffle queue) on
-synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host]
+synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native]
+"host_native": the host half of the native JPEG path (fs_jpeg_parse + fs_jpeg_decode: the Huffman pass, coefficients dropped) and then the PIL
+host half, at the same thread count, one after the other over the same shards.
 "host": the host half only -- record framing, Example parsing and the JPEG decode pool, decoded images dropped (no engine, no GPU): what a rank's
 cores sustain when eight pools run side by side on one box whose single GPU would otherwise be shared by all eight (tools/pipe_bench8.sh)."""
 import io
@@ -37,6 +39,27 @@ def main():
                                                  "image/channels": 3}))
         files.append(p)
     print("shards: %d images, %.1f KB/jpeg" % (n, np.mean([len(j) for j in jpegs]) / 1e3))
+    if len(sys.argv) > 3 and sys.argv[3] == "host_native":
+        th = threads or 24
+        host, arena = engine.JpegHost(), datapipe.CoefArena(None, False)
+        t0 = time.time()
+        k = fallback = 0
+        for r in datapipe._prefetch_map(lambda job: datapipe._native_decode(host, job),
+                                        datapipe._native_jobs(host, arena, datapipe._examples(files, 1, np.random.default_rng(0))), th, window=4 * th):
+            slot = r if isinstance(r, datapipe.CoefSlot) else r[1]
+            fallback += not isinstance(r, datapipe.CoefSlot)
+            if slot is not None:
+                slot.release()
+            k += 1
+        dt = time.time() - t0
+        print("pipeline: %.0f images/s host half only, native entropy decode (%d images, %d of them through PIL, in %.2f s, %d decode threads, %d host cores)"
+              % (k / dt, k, fallback, dt, th, os.cpu_count()))
+        it = datapipe._prefetch_map(lambda d: datapipe.decode_jpeg(d, packed=False), datapipe._examples(files, 1, np.random.default_rng(0)), th, window=4 * th)
+        t0 = time.time()
+        k = sum(1 for _ in it)
+        dt = time.time() - t0
+        print("pipeline: %.0f images/s host half only, PIL decode (%d images in %.2f s, %d decode threads, %d host cores)" % (k / dt, k, dt, th, os.cpu_count()))
+        return
     if len(sys.argv) > 3 and sys.argv[3] == "host":
         th = threads or 24
         it = datapipe._prefetch_map(datapipe.decode_jpeg, datapipe._examples(files, 1, np.random.default_rng(0)), th, window=4 * th)

@@ -8,7 +8,9 @@ nothing is started on the GPU after it):
   synth_host     train.main --train_dir synthetic (fewer steps: the host draws each batch with numpy)
   shards         train.main over generated TFRecord shards (640 x 480 JPEGs), FS_FEED_DEPTH at its default
   shards_sync    the same with FS_FEED_DEPTH=0
-plus ``decode`` (host only: the JPEG decode rate of the pool of threads that bounds the shard legs) and ``kernels`` (HIP-event time per launch
+  shards_jpeg    the same as shards with FS_FEED_JPEG=1: the library's JPEG decoder (Huffman pass on the decode threads, the rest on the GPU)
+plus ``decode`` (host only: the JPEG decode rate of the pool of threads that bounds the shard legs), ``decode_native`` (the same pool running the
+library's Huffman pass instead of PIL) and ``kernels`` (HIP-event time per launch
 of the three kernels of csrc/fs_feed.hip at the batch-32 training shapes).
 
 A train.main leg is timed from inside: Trainer.step is wrapped, the clock starts at a device synchronise before step ``warmup`` and stops at one
@@ -16,6 +18,7 @@ before step ``warmup + steps`` -- so the interval holds ``steps`` whole iteratio
 tenth step).  Rates on a shared machine are recorded, not gated.
 
     python tools/train_e2e.py --out profiles/train_e2e.json
+    python tools/train_e2e.py --only shards,shards_jpeg --out somewhere.json      (the pool leg and the named train.main legs only)
 """
 import argparse
 import io
@@ -119,18 +122,17 @@ def leg_train(kind, batch, steps, warmup, shard_dir):
     os.chdir(work)
     argv = ["--model_name", "e2e", "--style_img_path", STYLE, "--preprocess_size", str(SIZE), str(SIZE), "--batch_size", str(batch),
             "--num_steps_ckpt", "1000000"]
-    if kind in ("shards", "shards_sync"):
+    if kind in ("shards", "shards_sync", "shards_jpeg"):
         argv += ["--train_dir", shard_dir, "--n_epochs", "1000", "--num_pipe_buffer", "512"]
     else:
         argv += ["--train_dir", "synthetic:device" if kind == "synth_device" else "synthetic"]
     return timed_main(argv, warmup, steps, batch)
 
 
-def leg_decode(shard_dir, seconds=4.0):
+def leg_decode(shard_dir, threads, seconds=4.0):
     import glob
     from faststyle_amd import datapipe
     files = sorted(glob.glob(os.path.join(shard_dir, "train-*")))
-    threads = min(32, max(4, os.cpu_count() or 8))
     rng = np.random.default_rng(0)
     it = datapipe._prefetch_map(lambda d: datapipe.decode_jpeg(d, packed=False), datapipe._examples(files, None, rng), threads, window=4 * threads)
     for _ in range(2 * threads):
@@ -142,6 +144,40 @@ def leg_decode(shard_dir, seconds=4.0):
     dt = time.perf_counter() - t0
     it.close()
     return {"images_per_s": n / dt, "threads": threads, "note": "framing + Example lookup + PIL decode on the batcher's own thread pool, no GPU"}
+
+
+def leg_decode_native(shard_dir, threads, seconds=4.0):
+    """leg_decode with fs_jpeg_parse + fs_jpeg_decode in place of PIL: the host half of the native path, at the same thread count."""
+    import glob
+    from faststyle_amd import datapipe, engine
+    files = sorted(glob.glob(os.path.join(shard_dir, "train-*")))
+    rng = np.random.default_rng(0)
+    host = engine.JpegHost()
+    arena = datapipe.CoefArena(None, False)
+    state = {"handled": 0, "other": 0}
+
+    def results():
+        for r in datapipe._prefetch_map(lambda job: datapipe._native_decode(host, job),
+                                        datapipe._native_jobs(host, arena, datapipe._examples(files, None, rng)), threads, window=4 * threads):
+            if isinstance(r, datapipe.CoefSlot):
+                state["handled"] += 1
+                r.release()
+            else:
+                state["other"] += 1
+                if r[1] is not None:
+                    r[1].release()
+            yield r
+    it = results()
+    for _ in range(2 * threads):
+        next(it)
+    n, t0 = 0, time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        next(it)
+        n += 1
+    dt = time.perf_counter() - t0
+    it.close()
+    return {"images_per_s": n / dt, "threads": threads, "handled": state["handled"], "fallback": state["other"],
+            "note": "framing + Example lookup + fs_jpeg_parse + fs_jpeg_decode into arena chunks (pageable here) on the batcher's own thread pool, no GPU"}
 
 
 def leg_kernels(reps=20):
@@ -188,7 +224,9 @@ def child(args):
     if args.leg == "pool":
         r = leg_pool(args.batch, args.steps, args.warmup)
     elif args.leg == "decode":
-        r = leg_decode(args.shard_dir)
+        r = leg_decode(args.shard_dir, args.threads)
+    elif args.leg == "decode_native":
+        r = leg_decode_native(args.shard_dir, args.threads)
     elif args.leg == "kernels":
         r = leg_kernels()
     else:
@@ -201,14 +239,18 @@ def verdict(doc):
     out = {}
     decode = doc["legs"]["decode"]["images_per_s"]
     for batch, legs in ((4, doc["legs"].get("batch4", {})), (32, doc["legs"].get("batch32", {}))):
-        for leg in ("synth_device", "shards"):
+        for leg in ("synth_device", "shards", "shards_jpeg"):
             if leg not in legs:
                 continue
             r = legs[leg]["ratio_to_pool"]
             row = {"ratio_to_pool": round(r, 4), "target": 0.97 if (leg, batch) != ("shards", 32) else None}
             if row["target"] is not None:
                 row["met"] = bool(r >= row["target"])
-            if leg == "shards":
+            if leg == "shards_jpeg":
+                native = doc["legs"].get("decode_native", {}).get("images_per_s")
+                if native:
+                    row["decode_native_images_per_s"] = round(native, 1)
+            elif leg == "shards":
                 row["decode_images_per_s"] = round(decode, 1)
                 row["decode_over_pool_rate"] = round(decode / legs["pool"]["images_per_s"], 3)
                 row["bound"] = ("inferred from the legs, not isolated further -- the host: the training thread shares the interpreter lock and the CPUs with the decode pool (its Python halves), and copies "
@@ -230,9 +272,10 @@ def parent(args):
 
     def run(leg, batch, steps, limit, env=None):
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--batch", str(batch), "--steps", str(steps),
-               "--warmup", str(args.warmup), "--shard_dir", shard_dir]
+               "--warmup", str(args.warmup), "--shard_dir", shard_dir, "--threads", str(args.threads)]
         e = dict(os.environ)
         e.pop("FS_FEED_DEPTH", None)
+        e.pop("FS_FEED_JPEG", None)
         e.update(env or {})
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e)
         lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("TRAIN_E2E ")]
@@ -247,14 +290,20 @@ def parent(args):
             f.write("\n")
     doc["legs"]["decode"] = run("decode", 0, 0, 120)
     flush()
-    doc["legs"]["kernels"] = run("kernels", 0, 0, 180)
+    doc["legs"]["decode_native"] = run("decode_native", 0, 0, 120)
     flush()
+    only = [l for l in (args.only or "").split(",") if l]
+    if not only:
+        doc["legs"]["kernels"] = run("kernels", 0, 0, 180)
+        flush()
     for batch in (32, 4):
         legs = doc["legs"]["batch%d" % batch] = {}
         legs["pool"] = run("pool", batch, args.steps, 240)
         flush()
         for leg, steps, env in (("synth_device", args.steps, None), ("synth_host", max(20, args.steps // 5), None), ("shards", args.steps, None),
-                                ("shards_sync", args.steps, {"FS_FEED_DEPTH": "0"})):
+                                ("shards_sync", args.steps, {"FS_FEED_DEPTH": "0"}), ("shards_jpeg", args.steps, {"FS_FEED_JPEG": "1"})):
+            if only and leg not in only:
+                continue
             legs[leg] = run(leg, batch, steps, 420, env)
             legs[leg]["ratio_to_pool"] = legs[leg]["images_per_s"] / legs["pool"]["images_per_s"]
             flush()
@@ -269,6 +318,8 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--images", type=int, default=1024)
+    ap.add_argument("--threads", type=int, default=16, help="decode threads of the two host-only legs (a fixed count, not the machine's CPU count)")
+    ap.add_argument("--only", default=None, help="comma-separated train.main legs to run beside the pool leg (default: all)")
     ap.add_argument("--leg", default=None)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--shard_dir", default=None)

@@ -20,7 +20,9 @@ Differences from the reference that are forced by the environment and stated, no
   * batches reach the step through a ring of FS_FEED_DEPTH (default 2) device batches that a side
     stream fills ahead of the step (faststyle_amd/datapipe.py: DeviceRing; shards, ``synthetic`` and
     ``synthetic:device``).  The batches are the same, bit for bit; FS_FEED_DEPTH=0 is the synchronous
-    path on the training stream;
+    path on the training stream.  FS_FEED_JPEG=1 (default 0) has the library decode the shards' baseline JPEGs
+    itself on that path -- Huffman pass on the decode threads, reconstruction on the GPU, the same pixels as
+    PIL's, which keeps the files the library does not take; it needs the ring (refused with FS_FEED_DEPTH=0);
   * next to the TensorBoard event file (``summaries/train/<run_name>/events.out.tfevents.*`` with the
     reference's four scalars ``summaries/{loss,style_loss,content_loss,tv_loss}`` at the same steps,
     train.py:185-189, 260-272; no graph definition in it) the same values go to ``scalars.jsonl``.
@@ -152,6 +154,7 @@ def main(args):
     literal = args.train_dir in ('synthetic', 'synthetic:device')
     shards = sorted(glob.glob(os.path.join(args.train_dir, 'train-*'))) if not literal else []
     feed_depth = _lib.knob(eng.lib, "FS_FEED_DEPTH")       # ring depth of the device-fed input path; 0: the synchronous path
+    feed_jpeg = _lib.knob(eng.lib, "FS_FEED_JPEG")         # 1: shards' JPEGs through the library's decoder (device-fed path only)
 
     def common_step_count(n_local):
         """Ranks read disjoint shards / files of unequal size: every rank must run the SAME number of steps, or the
@@ -170,7 +173,7 @@ def main(args):
         cap = common_step_count(datapipe.count_records(shards[rank::world]) * args.n_epochs // args.batch_size)
         batches = datapipe.batcher(shards, args.batch_size, args.preprocess_size, args.n_epochs,
                                    args.num_pipe_buffer, engine=eng, seed=1234, rank=rank, world=world,
-                                   max_batches=cap, prefetch=max(0, feed_depth))
+                                   max_batches=cap, prefetch=max(0, feed_depth), jpeg="device" if feed_jpeg else None)
     elif args.train_dir == 'synthetic:device':
         total = COCO_TRAIN2014 * args.n_epochs // world // args.batch_size          # the step count of `synthetic`
         batches = datapipe.synthetic_device_batches(eng, args.batch_size, args.preprocess_size, 1234, rank, step0,
