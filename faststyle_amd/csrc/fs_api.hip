@@ -697,10 +697,11 @@ static int fill_conv(fs_conv_desc* d, fs::ConvArgs* a) {
         if (a->w_wino && !fs::wino_eligible(*a)) a->w_wino = nullptr;
     }
     a->p = fs::conv_plan(*a);
-    if (d->inb_rec && !(a->w_wino4t && a->p.variant == 11 && a->p.TW == 16 && a->p.ksplit <= 1))
+    if (d->inb_rec && !(a->w_wino4t && a->p.variant == fs::CV_WINO4T && a->p.TW == 16 && a->p.ksplit <= 1))
         return fail(-2, "fs_conv2d: inb_rec needs an eligible w_wino4t conv (3x3 stride 1, raw or add_src epilogue, inb_z / inb_mean / inb_rstd set)");
     if (d->pool_out) {   // only the Winograd epilogues hold whole pooling windows
-        if (!(a->p.variant == 5 || a->p.variant == 6 || a->p.variant == 10 || a->p.variant == 11 || a->p.variant == 12) || a->p.ksplit > 1 || (a->Ho & 1) || (a->Wo & 1))
+        const fs::ConvFamily* fam = fs::conv_family(a->p.variant);
+        if (!(fam && fam->pool_epilogue) || a->p.ksplit > 1 || (a->Ho & 1) || (a->Wo & 1))
             return fail(-2, "fs_conv2d: pool_out needs a Winograd-eligible conv with even Ho, Wo");
         a->pool_out = d->pool_out;
     }

@@ -940,17 +940,25 @@ static void plan_variant(const ConvArgs& a, int variant, ConvPlan* out) {
 // fits; what falls through runs on conv_igemm_kernel below).  Generations of the Winograd kernels: WinoGen in fs_kernels.h.
 const ConvFamily* conv_families(int* n) {
     static const ConvFamily kFamilies[] = {
-        {"wino6: split-bf16 F(4x4,3x3) pipeline (deep VGG16 layers)", 12, true, wino6_eligible, wino6_plan, wino6_launch},
-        {"wino4: F(4x4,3x3), filter through LDS (FS_WINO_V=4)", 10, true, wino4_eligible, wino4_plan, wino4_launch},
-        {"wino4t: F(4x4,3x3), filter in registers", 11, true, wino4t_eligible, wino4t_plan, wino4t_launch},
-        {"wino2h: F(2x2,3x3), half items (small grids)", 8, true, wino2h_eligible, wino2h_plan, wino2h_launch},
-        {"wino2: F(2x2,3x3), second generation", 6, true, wino2_eligible, wino2_plan, wino2_launch},
-        {"wino: F(2x2,3x3), first kernel", 5, true, wino_eligible, wino_plan, wino_launch},
-        {"cstream: narrow full-resolution layers, persistent streaming", 7, false, cstream_eligible, cstream_plan, cstream_launch},
-        {"s16: 16-output-channel blocks (9x9 image layer, folded output layer)", 9, false, s16_eligible, s16_plan, s16_launch},
+        // name                                                                            variant  tile  pool   keep_n  fin    profiler row, with prof_tag
+        {"wino6: split-bf16 F(4x4,3x3) pipeline (deep VGG16 layers)",                  CV_WINO6,   4, true,  true,  false, PF_WINO6, PF_WINO6, wino6_eligible, wino6_plan, wino6_launch},
+        {"wino4: F(4x4,3x3), filter through LDS (FS_WINO_V=4)",                        CV_WINO4,   4, true,  false, false, PF_WINO4, PF_WINO4, wino4_eligible, wino4_plan, wino4_launch},
+        {"wino4t: F(4x4,3x3), filter in registers",                                    CV_WINO4T,  4, true,  true,  false, PF_WINO4T_VGG, PF_WINO4T_TNET, wino4t_eligible, wino4t_plan, wino4t_launch},
+        {"wino2h: F(2x2,3x3), half items (small grids)",                               CV_WINO2H,  2, false, false, true,  PF_WINO2H_TNET, PF_WINO2H_TNET, wino2h_eligible, wino2h_plan, wino2h_launch},
+        {"wino2: F(2x2,3x3), second generation",                                       CV_WINO2,   2, true,  false, true,  PF_WINO2_VGG, PF_WINO2_TNET, wino2_eligible, wino2_plan, wino2_launch},
+        {"wino: F(2x2,3x3), first kernel",                                             CV_WINO,    2, true,  false, false, PF_WINO, PF_WINO, wino_eligible, wino_plan, wino_launch},
+        {"cstream: narrow full-resolution layers, persistent streaming",               CV_CSTREAM, 0, false, false, true,  PF_CSTREAM, PF_CSTREAM, cstream_eligible, cstream_plan, cstream_launch},
+        {"s16: 16-output-channel blocks (9x9 image layer, folded output layer)",       CV_S16,     0, false, false, false, PF_S16, PF_S16, s16_eligible, s16_plan, s16_launch},
     };
     *n = (int)(sizeof(kFamilies) / sizeof(kFamilies[0]));
     return kFamilies;
+}
+const ConvFamily* conv_family(int variant) {
+    int nf = 0;
+    const ConvFamily* fam = conv_families(&nf);
+    for (int i = 0; i < nf; ++i)
+        if (fam[i].variant == variant) return &fam[i];
+    return nullptr;
 }
 
 ConvPlan conv_plan(const ConvArgs& a) {
@@ -960,20 +968,20 @@ ConvPlan conv_plan(const ConvArgs& a) {
         const ConvFamily* fam = conv_families(&nf);
         const bool wino_on = knob(K_CONV_WINO) != 0;
         for (int i = 0; i < nf; ++i)
-            if ((wino_on || !fam[i].winograd) && fam[i].eligible(a)) {
+            if ((wino_on || !fam[i].wino_tile) && fam[i].eligible(a)) {
                 fam[i].plan(a, &p);
                 return p;
             }
     }
     if (a.Cout <= 16 || a.Cin == 3) {  // narrow outputs, and the flat Cin==3 path, have one variant each
-        plan_variant(a, a.Cout <= 16 ? 2 : 0, &p);
+        plan_variant(a, a.Cout <= 16 ? CV_IGEMM_16_4_1 : CV_IGEMM_32_2_2, &p);
         return p;
     }
     // widest tile first; halve the workgroup tile while the launch cannot fill the chip
     // (256 CUs x >= 2 workgroups), e.g. VGG conv4_x at batch 4 or the 64-channel residual convs
     const int min_wgs = knob(K_CONV_MIN_WGS);
     const int forced_variant = knob(K_CONV_VARIANT);  // tuning aid (tools/micro_conv.py)
-    if (forced_variant >= 0 && forced_variant <= 4 && forced_variant != 2) {
+    if (forced_variant >= CV_IGEMM_32_2_2 && forced_variant <= CV_IGEMM_32_1_1 && forced_variant != CV_IGEMM_16_4_1) {
         plan_variant(a, forced_variant, &p);
         return p;
     }
@@ -1076,7 +1084,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const float* __res
 // sum complete in one workgroup (the window partners are read from mask_src in global memory: no tile alignment needed)
 bool conv_route_ok(const ConvArgs& a) {
     const ConvPlan& p = a.p;
-    return a.mask_src && !a.add_src && !a.shuffle && !a.stats && p.ksplit <= 1 && p.variant < 5;
+    return a.mask_src && !a.add_src && !a.shuffle && !a.stats && p.ksplit <= 1 && !conv_family(p.variant);
 }
 
 int conv_launch(const ConvArgs& a_in, hipStream_t s) {
@@ -1099,25 +1107,21 @@ int conv_launch(const ConvArgs& a_in, hipStream_t s) {
         a.add_src = nullptr;
         a.mask_src = nullptr;
     }
+    const ConvFamily* special = conv_family(p.variant);
     Profiler* prof = Profiler::current();
     if (prof) {
         // algorithmic FLOPs: 2*M*K*N with the true extents; a zero-dilated dgrad only does 1/4 useful work
         double fl = 2.0 * a.N * a.Ho * a.Wo * (double)a.KH * a.KW * a.Cin * a.Cout;
         if (a.src_mode == SRC_DILATE2) fl *= 0.25;
         if (a.shuffle) fl *= 9.0 / 16.0;  // phase-collapsed resize-conv / stride-2 dgrad: 9 of the 16 tap-parity slots are non-zero
-        // Winograd F(2x2,3x3): 16 products per 2x2 output tile instead of 36 -- the FLOPs actually executed
-        if (p.variant == 5 || p.variant == 6 || p.variant == 8) fl = 2.0 * a.N * cdiv(a.Ho, 2) * cdiv(a.Wo, 2) * 16.0 * a.Cin * a.Cout;
-        if (p.variant == 10 || p.variant == 11 || p.variant == 12) fl = 2.0 * a.N * cdiv(a.Ho, 4) * cdiv(a.Wo, 4) * 36.0 * a.Cin * a.Cout;   // F(4x4,3x3): 36 products per 4x4 outputs
-        int fam = p.variant;   // conv_igemm_kernel<..> instances 0..4, wino_conv_kernel 5
-        if (a.w_nstride) fam = PF_GRAM_BWD_IGEMM;
-        else if (p.variant == 7) fam = PF_CSTREAM;
-        else if (p.variant == 9) fam = PF_S16;
-        else if (p.variant == 10) fam = PF_WINO4;
-        else if (p.variant == 12) fam = PF_WINO6;
-        else if (p.variant == 11) fam = a.prof_tag ? PF_WINO4T_TNET : PF_WINO4T_VGG;
-        else if (p.variant == 8) fam = PF_WINO2H_TNET;
-        else if (p.variant == 6) fam = a.prof_tag ? PF_WINO2_TNET : PF_WINO2_VGG;
-        prof->begin(fam, fl, s);
+        // Winograd F(m x m, 3x3): (m + 2)^2 products per m x m output tile instead of 9 m^2 -- the FLOPs actually executed
+        if (special && special->wino_tile) {
+            const int m = special->wino_tile;
+            fl = 2.0 * a.N * cdiv(a.Ho, m) * cdiv(a.Wo, m) * (double)((m + 2) * (m + 2)) * a.Cin * a.Cout;
+        }
+        // the row: per kernel symbol -- the conv_igemm_kernel<..> instance, or the family's
+        const int row = a.w_nstride ? (int)PF_GRAM_BWD_IGEMM : !special ? p.variant : a.prof_tag ? special->prof_row_tagged : special->prof_row;
+        prof->begin(row, fl, s);
     }
 #define FS_LAUNCH(MT_, WM_, WN_, FL_)                                                                              \
     do {                                                                                                           \
@@ -1125,13 +1129,6 @@ int conv_launch(const ConvArgs& a_in, hipStream_t s) {
         lds_attr.ensure(reinterpret_cast<const void*>(conv_igemm_kernel<MT_, WM_, WN_, FL_>));                       \
         hipLaunchKernelGGL((conv_igemm_kernel<MT_, WM_, WN_, FL_>), grid, dim3(256), (size_t)p.lds_bytes, s, a);   \
     } while (0)
-    const ConvFamily* special = nullptr;
-    {
-        int nf = 0;
-        const ConvFamily* fam = conv_families(&nf);
-        for (int i = 0; i < nf; ++i)
-            if (fam[i].variant == p.variant) special = &fam[i];
-    }
     if (special) {
         if (!special->eligible(a_in)) return -7;
         FS_TRY_(special->launch(a, s));

@@ -1187,7 +1187,7 @@ void cstream_plan(const ConvArgs& a, ConvPlan* out) {
     ConvPlan p{};
     const int inst = cstream_instance(a);
     const int TH = inst ? kInst[inst - 1].TH : 16;
-    p.variant = 7;
+    p.variant = CV_CSTREAM;
     p.BN = a.Cout;
     p.CC = a.Cin;
     p.TH = TH;

@@ -27,10 +27,23 @@ enum SrcMode {
     SRC_UP4 = 3,      // virtual[i] = tensor[i/4] (as-written NEAREST x4 upsample; wgrad only)
 };
 
+// ConvPlan::variant.  0..4: the conv_igemm_kernel<MT,WM,WN> instances (the direct kernel, fs_conv.hip); from CV_WINO on every value is one specialised
+// kernel family and has one row in the family table of fs_conv.hip (conv_family()), which carries what the host code needs to know about it.
+// The numbers are what FS_CONV_VARIANT takes and FS_CONV_DEBUG prints.
+enum ConvVariant {
+    CV_IGEMM_32_2_2 = 0, CV_IGEMM_32_2_1 = 1, CV_IGEMM_16_4_1 = 2, CV_IGEMM_32_1_2 = 3, CV_IGEMM_32_1_1 = 4,
+    CV_WINO = 5,      // wino_conv_kernel (fs_wino.hip)
+    CV_WINO2 = 6,     // wino2_conv_kernel (fs_wino2.hip)
+    CV_CSTREAM = 7,   // conv_stream_kernel (fs_cstream.hip)
+    CV_WINO2H = 8,    // wino2h_conv_kernel (fs_wino2h.hip)
+    CV_S16 = 9,       // conv_s16_kernel (fs_s16.hip)
+    CV_WINO4 = 10,    // wino4_conv_kernel (fs_wino4.hip)
+    CV_WINO4T = 11,   // wino4t_conv_kernel, 16-tile items (fs_wino4t.hip)
+    CV_WINO6 = 12,    // the split-bf16 pipeline: input transform, 36 GEMMs on the bf16 matrix cores, output transform (fs_wino6.hip)
+};
+
 struct ConvPlan {
-    int variant;  // conv_igemm_kernel<MT,WM,WN>: 0 <32,2,2>  1 <32,2,1>  2 <16,4,1>  3 <32,1,2>  4 <32,1,1>;  5 wino_conv_kernel;  6 wino2_conv_kernel;
-                  // 7 conv_stream_kernel;  8 wino2h_conv_kernel;  9 conv_s16_kernel;  10 wino4_conv_kernel (F(4x4,3x3));  11 wino4t_conv_kernel (F(4x4,3x3), 16-tile items)
-                  // 12 the split-bf16 F(4x4,3x3) pipeline of fs_wino6.hip (input transform, 36 GEMMs on the bf16 matrix cores, output transform)
+    int variant;  // which kernel runs the plan: a ConvVariant (below)
     int BN;       // output channels per workgroup
     int flat;     // Cin==3: K runs over (kw,ci) contiguously per kernel row
     int CC;       // input channels staged per chunk
@@ -84,12 +97,12 @@ struct FinArgs {
 struct ConvArgs {
     const float* x;  // [N,H,W,Cin]
     const float* w;  // [KH*KW, Cin, Cout] (HWIO); + n*w_nstride for per-sample weights
-    const float* w_wino;  // optional: the same filter Winograd-transformed, [16][Cin][Cout] (fs::wt_wino); enables variant 5
-    const float* w_wino2; // optional: ... in the K-contiguous order [16][Cin/8][Cout][8] (fs::wt_wino2); enables variant 6
-    const float* w_wino4; // optional: the filter transformed for F(4x4,3x3), [36][Cin/4][Cout/64][2][4][16][2] (fs::wt_wino4); enables variant 10
-    const float* w_wino4t; // optional: the filter transformed for F(4x4,3x3) in the register layout of fs_wino4t.hip, [Cin/8][Cout/16][18][64][4] (fs::wt_wino4t); enables variant 11
+    const float* w_wino;  // optional: the same filter Winograd-transformed, [16][Cin][Cout] (fs::wt_wino); enables CV_WINO
+    const float* w_wino2; // optional: ... in the K-contiguous order [16][Cin/8][Cout][8] (fs::wt_wino2); enables CV_WINO2
+    const float* w_wino4; // optional: the filter transformed for F(4x4,3x3), [36][Cin/4][Cout/64][2][4][16][2] (fs::wt_wino4); enables CV_WINO4
+    const float* w_wino4t; // optional: the filter transformed for F(4x4,3x3) in the register layout of fs_wino4t.hip, [Cin/8][Cout/16][18][64][4] (fs::wt_wino4t); enables CV_WINO4T
     const float* w_wino4u; // optional, with w_wino4t: the same filter in the layout of the 128-channel item form of fs_wino4t.hip, [Cin/8][Cout/32][36][64][4] (fs::wt_wino4u)
-    const unsigned short* w_wino6; // optional: the F(4x4,3x3) filter as three bf16 pieces, [36][Cin/32][3][Cout][32] (fs::wt_wino6), with w6_ws: enables variant 12 (fs_wino6.hip)
+    const unsigned short* w_wino6; // optional: the F(4x4,3x3) filter as three bf16 pieces, [36][Cin/32][3][Cout][32] (fs::wt_wino6), with w6_ws: enables CV_WINO6 (fs_wino6.hip)
     float* w6_ws;          // scratch of the split-bf16 pipeline: V [36][tiles][Cin] + M [36][tiles][Cout] of one tile chunk (w6_ws_floats capacity; wino6_ws_floats() = one pass)
     size_t w6_ws_floats;
     hipStream_t w6_side;   // optional second stream + three events (fs_wino6.hip, round 6): the launch runs as two tile chunks software-pipelined over the two streams --
@@ -547,7 +560,7 @@ bool conv_route_ok(const ConvArgs& a);   // a.p filled: can the launch take a.ro
 bool wino2_eligible(const ConvArgs& a);
 void wino2_plan(const ConvArgs& a, ConvPlan* out);
 int wino2_launch(const ConvArgs& a, hipStream_t s);
-bool wino2h_eligible(const ConvArgs& a);                                                       // fs_wino2h.hip: plan variant 8
+bool wino2h_eligible(const ConvArgs& a);                                                       // fs_wino2h.hip: CV_WINO2H
 long wino2h_items(const ConvArgs& a);
 void wino2h_plan(const ConvArgs& a, ConvPlan* out);
 int wino2h_launch(const ConvArgs& a, hipStream_t s);
@@ -562,24 +575,24 @@ int gram_bwd2_route_grid(int N, int H, int W, int C);
 int gram_bwd2_launch(const float* F, const float* S, const float* add, float* dF, int N, int HW, int C, hipStream_t s, const float* above = nullptr,
                      int W = 0, const float* content = nullptr, float cscale = 0.f, float* cpartial = nullptr);
 int gram_symmetrize(const float* dG, float* S, int N, int C, float scale, hipStream_t s);   // S[n] = scale * (dG[n] + dG[n]^T)
-// streaming conv of the narrow full-resolution layers (fs_cstream.hip): plan variant 7
+// streaming conv of the narrow full-resolution layers (fs_cstream.hip): CV_CSTREAM
 bool cstream_eligible(const ConvArgs& a);
 void cstream_plan(const ConvArgs& a, ConvPlan* out);
 int cstream_launch(const ConvArgs& a, hipStream_t s);
-bool s16_eligible(const ConvArgs& a);                                                          // fs_s16.hip: plan variant 9 (16 output channels: 9x9 image layer, kw-folded output layer)
+bool s16_eligible(const ConvArgs& a);                                                          // fs_s16.hip: CV_S16 (16 output channels: 9x9 image layer, kw-folded output layer)
 void s16_plan(const ConvArgs& a, ConvPlan* out);
 int s16_launch(const ConvArgs& a, hipStream_t s);
 bool conv3x3_to3_eligible(const ConvArgs& a);                                                 // fs_c3.hip
 int conv3x3_to3_launch(const ConvArgs& a, hipStream_t s);
-int wt_wino4(const float* w, float* U, int Cin, int Cout, hipStream_t s);                      // fs_wino4.hip: Winograd F(4x4,3x3), plan variant 10
+int wt_wino4(const float* w, float* U, int Cin, int Cout, hipStream_t s);                      // fs_wino4.hip: Winograd F(4x4,3x3), CV_WINO4
 bool wino4_eligible(const ConvArgs& a);
 void wino4_plan(const ConvArgs& a, ConvPlan* out);
 int wino4_launch(const ConvArgs& a, hipStream_t s);
-int wt_wino4t(const float* w, float* U, int Cin, int Cout, hipStream_t s);                     // fs_wino4t.hip: F(4x4,3x3) with 16-tile items (transform-net residual convs), plan variant 11
+int wt_wino4t(const float* w, float* U, int Cin, int Cout, hipStream_t s);                     // fs_wino4t.hip: F(4x4,3x3) with 16-tile items (transform-net residual convs), CV_WINO4T
 int wt_wino4t_batch(const WinoBatch& b, int Cin, int Cout, hipStream_t s);
 int wt_wino4u(const float* w, float* U, int Cin, int Cout, hipStream_t s);                      // ... for its 128-channel item form (ConvArgs::w_wino4u)
 bool wino4t_eligible(const ConvArgs& a);
-// fs_wino6.hip: F(4x4,3x3) with the Winograd-domain products as six exact bf16-piece products (round 6), plan variant 12
+// fs_wino6.hip: F(4x4,3x3) with the Winograd-domain products as six exact bf16-piece products (round 6), CV_WINO6
 int wt_wino6(const float* w, unsigned short* U, int Cin, int Cout, hipStream_t s);
 size_t wino6_filter_floats(int Cin, int Cout);
 size_t wino6_ws_floats(int N, int Ho, int Wo, int Cin, int Cout);
@@ -610,15 +623,21 @@ struct WinoGen {
 };
 inline WinoGen wino_gen() { return WinoGen{knob(K_WINO_V)}; }
 // One row per specialised conv kernel family: conv_plan takes the first row whose eligible() accepts the launch, conv_launch finds the row of the
-// plan's variant again (and re-checks eligibility: a plan made for other arguments is refused with -7).  fs_conv.hip holds the table.
+// plan's variant again (and re-checks eligibility: a plan made for other arguments is refused with -7).  fs_conv.hip holds the table; the traits are
+// the only place that says what a family can do -- host code asks conv_family(variant), never a list of numbers.
 struct ConvFamily {
     const char* name;
-    int variant;       // ConvPlan::variant of its plans
-    bool winograd;     // off under FS_CONV_WINO=0
+    int variant;          // ConvVariant of its plans
+    int wino_tile;        // Winograd output-tile edge m of F(m x m, 3x3): 2 or 4 (off under FS_CONV_WINO=0; (m+2)^2 products per tile are the FLOPs executed); 0: not Winograd
+    bool pool_epilogue;   // the epilogue can write ConvArgs::pool_out ...
+    bool keeps_n;         // ... and honours ConvArgs::y_keep_n
+    bool takes_fin;       // persistent kernel that can take FinArgs (the fused instance-norm finalize)
+    int prof_row, prof_row_tagged;   // ProfFam row of a launch; of one with ConvArgs::prof_tag set
     bool (*eligible)(const ConvArgs&);
     void (*plan)(const ConvArgs&, ConvPlan*);
     int (*launch)(const ConvArgs&, hipStream_t);
 };
+const ConvFamily* conv_family(int variant);   // the row of a plan variant; nullptr: the direct kernel
 const ConvFamily* conv_families(int* n);
 // does a launch of this size qualify?  (one workgroup reads N*C*T*groups records: beyond a few 10^4 a launch of its own,
 // spread over the chip, is faster)

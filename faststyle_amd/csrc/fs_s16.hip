@@ -1031,7 +1031,7 @@ bool s16_eligible(const ConvArgs& a) {
 void s16_plan(const ConvArgs& a, ConvPlan* out) {
     ConvPlan p{};
     const int inst = s16_instance(a);
-    p.variant = 9;
+    p.variant = CV_S16;
     p.BN = a.Cout;
     p.CC = a.Cin;
     p.flat = a.Cin == 3;   // (K runs over (kw, ci) contiguously per kernel row)

@@ -502,8 +502,8 @@ int tnet_forward(const TnetLayout& L, const float* params, const float* x, float
     bool any_fused = false;
     for (int i = 0; i < 16; ++i) {
         const Unit& u = L.u[i];
-        fused[i] = u.kind != 2 && (u.plan.variant == 6 || u.plan.variant == 7 || u.plan.variant == 8) && u.plan.rem_ks == 0 &&
-                   fused_finalize_ok(N, u.Cout, u.tiles, u.kind == 1 ? 4 : 1);
+        const ConvFamily* fam = conv_family(u.plan.variant);
+        fused[i] = u.kind != 2 && fam && fam->takes_fin && u.plan.rem_ks == 0 && fused_finalize_ok(N, u.Cout, u.tiles, u.kind == 1 ? 4 : 1);
         any_fused = any_fused || fused[i];
     }
     if (any_fused) FS_TRY(zero_words(ws + L.fin_counter, 16, s));   // (a kernel: memset nodes misbehave in single-stream graph replays, see fs_perceptual_loss)
@@ -652,7 +652,7 @@ static int unit_dgrad(const TnetLayout& L, const Unit& u, const float* params, c
     a.rem_ws = ws + L.rem_ws;
     a.rem_ws_floats = (size_t)kRemUnits * 16384;
     a.p = conv_plan(a);
-    if (below && rec_tiles && a.w_wino4t && a.p.variant == 11 && a.p.TW == 16 && a.p.ksplit <= 1 && a.Ho == below->Hout && a.Wo == below->Wout &&
+    if (below && rec_tiles && a.w_wino4t && a.p.variant == CV_WINO4T && a.p.TW == 16 && a.p.ksplit <= 1 && a.Ho == below->Hout && a.Wo == below->Wout &&
         a.Cout == below->Cout && knob(K_INBWD_FUSED)) {
         ConvArgs f = a;
         f.inb_z = ws + below->z;
@@ -663,7 +663,7 @@ static int unit_dgrad(const TnetLayout& L, const Unit& u, const float* params, c
         f.inb_relu = below_relu;
         f.inb_rec = ws + L.inb_rec;
         const ConvPlan pf = conv_plan(f);
-        if (pf.variant == 11 && pf.TW == 16 && pf.ksplit <= 1 && pf.tiles_y == a.p.tiles_y && pf.tiles_x == a.p.tiles_x) {
+        if (pf.variant == CV_WINO4T && pf.TW == 16 && pf.ksplit <= 1 && pf.tiles_y == a.p.tiles_y && pf.tiles_x == a.p.tiles_x) {
             f.p = pf;
             *rec_tiles = pf.tiles_y * pf.tiles_x;
             return conv_launch(f, s);

@@ -13,7 +13,6 @@
 #include "fs_tnet.h"   // StreamAux
 
 #include <cstdlib>
-
 #include <cstring>
 
 namespace fs {
@@ -49,10 +48,13 @@ static bool w6_layer_ok(int l, bool dgrad) {
     const int ci = dgrad ? kCout[l] : kCin[l], co = dgrad ? kCin[l] : kCout[l];
     return l >= 1 && ci % 32 == 0 && co % 128 == 0 && (long)ci * co >= (long)knob(K_WINO6_MINCC);
 }
+struct PrepFilters {   // float offsets of the layouts of one (layer, direction); set only where prep_layout took them
+    size_t wino, wino2, wino4, wino4t, wino4u, wino6;
+};
 struct PrepLayout {
     unsigned mask;
     size_t flipt[FS_VGG_NLAYERS];
-    size_t wino[FS_VGG_NLAYERS][2], wino2[FS_VGG_NLAYERS][2], wino4[FS_VGG_NLAYERS][2], wino4t[FS_VGG_NLAYERS][2], wino4u[FS_VGG_NLAYERS][2], wino6[FS_VGG_NLAYERS][2];   // [layer][dgrad]
+    PrepFilters f[FS_VGG_NLAYERS][2];   // [layer][dgrad]
     size_t total;
 };
 static PrepLayout prep_layout(unsigned mask) {
@@ -68,24 +70,23 @@ static PrepLayout prep_layout(unsigned mask) {
     for (int l = 1; l < FS_VGG_NLAYERS; ++l)
         for (int d = 0; d < 2; ++d) {
             const size_t cc = (size_t)kCin[l] * kCout[l];
+            PrepFilters& f = P.f[l][d];
             if (mask & PREP_F2) {
-                P.wino[l][d] = take(16 * cc);
-                P.wino2[l][d] = take(16 * cc);
+                f.wino = take(16 * cc);
+                f.wino2 = take(16 * cc);
             }
-            if (mask & PREP_W4) P.wino4[l][d] = take(36 * cc);
+            if (mask & PREP_W4) f.wino4 = take(36 * cc);
             if (mask & PREP_W4T) {
-                P.wino4t[l][d] = take(36 * cc);
-                if ((d ? kCin[l] : kCout[l]) % 128 == 0) P.wino4u[l][d] = take(36 * cc);
+                f.wino4t = take(36 * cc);
+                if ((d ? kCin[l] : kCout[l]) % 128 == 0) f.wino4u = take(36 * cc);
             }
-            if ((mask & PREP_W6) && w6_layer_ok(l, d == 1)) P.wino6[l][d] = take(wino6_filter_floats(d ? kCout[l] : kCin[l], d ? kCin[l] : kCout[l]));
+            if ((mask & PREP_W6) && w6_layer_ok(l, d == 1)) f.wino6 = take(wino6_filter_floats(d ? kCout[l] : kCin[l], d ? kCin[l] : kCout[l]));
         }
     P.total = n;
     return P;
 }
 size_t vgg_prepared_floats() { return prep_layout(vgg_prep_mask()).total; }
-// which generation the knobs of the moment want for the F(4x4) convs (FS_WINO_V >= 5: fs_wino4t.hip; 4: fs_wino4.hip) and whether the deep layers may take fs_wino6.hip
-static bool vgg_use_4t() { return wino_gen().f4_reg(); }
-static bool vgg_want_w6() { return wino_gen().split_bf16(); }
+static bool vgg_want_w6() { return wino_gen().split_bf16(); }   // may the deep layers take fs_wino6.hip under the knobs of the moment
 // debugging aid: FS_VGG_WINO_MASK selects the layers that may take the Winograd kernel (bit l: forward of layer l,
 // bit 16+l: its input gradient); default all
 static bool wino_layer_on(int bit) {
@@ -100,16 +101,17 @@ int vgg_prepare(const float* const w[FS_VGG_NLAYERS], float* prepared, hipStream
             // forward: the stored HWIO filter; input gradient: its flip-transposed copy [3][3][Cout][Cin] with the channel roles swapped
             const float* src = d ? prepared + P.flipt[l] : w[l];
             const int ci = d ? kCout[l] : kCin[l], co = d ? kCin[l] : kCout[l];
+            const PrepFilters& f = P.f[l][d];
             if (P.mask & PREP_F2) {
-                FS_TRY(wt_wino(src, prepared + P.wino[l][d], ci, co, s));
-                FS_TRY(wt_wino2(src, prepared + P.wino2[l][d], ci, co, s));
+                FS_TRY(wt_wino(src, prepared + f.wino, ci, co, s));
+                FS_TRY(wt_wino2(src, prepared + f.wino2, ci, co, s));
             }
-            if (P.mask & PREP_W4) FS_TRY(wt_wino4(src, prepared + P.wino4[l][d], ci, co, s));
+            if (P.mask & PREP_W4) FS_TRY(wt_wino4(src, prepared + f.wino4, ci, co, s));
             if (P.mask & PREP_W4T) {
-                FS_TRY(wt_wino4t(src, prepared + P.wino4t[l][d], ci, co, s));
-                if (co % 128 == 0) FS_TRY(wt_wino4u(src, prepared + P.wino4u[l][d], ci, co, s));
+                FS_TRY(wt_wino4t(src, prepared + f.wino4t, ci, co, s));
+                if (co % 128 == 0) FS_TRY(wt_wino4u(src, prepared + f.wino4u, ci, co, s));
             }
-            if ((P.mask & PREP_W6) && w6_layer_ok(l, d == 1)) FS_TRY(wt_wino6(src, reinterpret_cast<unsigned short*>(prepared + P.wino6[l][d]), ci, co, s));
+            if ((P.mask & PREP_W6) && w6_layer_ok(l, d == 1)) FS_TRY(wt_wino6(src, reinterpret_cast<unsigned short*>(prepared + f.wino6), ci, co, s));
         }
     return (int)P.mask;   // >= 0: the generations the buffer carries
 }
@@ -135,6 +137,60 @@ static WgradArgs gram_args(int N, int H, int W, int C) {
     return a;
 }
 
+// What the conv launches of one call share: where their filters come from and what they may use.
+struct VggRun {
+    const float* const* w;   // the stored HWIO filters
+    const float* prepared;   // the buffer of fs_vgg_prepare, or nullptr: direct kernels only
+    PrepLayout P;            // what that buffer carries (nothing without one)
+    float* ws;               // the workspace laid out by vgg_layout
+    const StreamAux* aux;    // side stream + events for the overlap forms of the split-bf16 pipeline, or nullptr
+    bool offer_w6;           // the launches may be handed the split-bf16 layout
+};
+static VggRun vgg_run(const float* const* w, const float* prepared, unsigned prep_mask, float* ws, const StreamAux* aux = nullptr) {
+    return VggRun{w, prepared, prep_layout(prepared ? prep_mask : 0), ws, aux, true};
+}
+static void w6_pipe_args(ConvArgs* a, const StreamAux* aux);
+// THE description of a VGG16 3x3 conv launch: layer l, forward or input gradient (dgrad), batch N.  R == nullptr: the shape alone (vgg_layout's planning
+// pass).  Otherwise also the filter -- w[l], or for the input gradient its flip-transposed copy in the prepared buffer (a.w stays nullptr without a
+// buffer: the caller provides the copy) --, the split-K scratch, and every prepared layout the launch may read.  The one place that holds the promise of
+// the header: a layout is handed over only if the buffer carries it AND the knobs of the moment want it AND FS_VGG_WINO_MASK allows the layer AND the
+// channel counts fit; conv_plan's family table then picks among what is offered, and with nothing offered the direct kernels run.
+static ConvArgs vgg_conv_args(const VggLayout& L, int l, bool dgrad, int N, const VggRun* R) {
+    ConvArgs a{};
+    a.N = N;
+    a.H = a.Ho = L.Hl[l];
+    a.W = a.Wo = L.Wl[l];
+    a.Cin = dgrad ? kCout[l] : kCin[l];
+    a.Cout = dgrad ? kCin[l] : kCout[l];
+    a.KH = a.KW = 3;
+    a.stride = 1;
+    a.pad_t = a.pad_l = 1;
+    if (!R) return a;
+    a.split_ws = R->ws + L.splitws;
+    a.split_ws_floats = L.splitws_floats;
+    const float* prep = R->prepared;
+    const PrepLayout& P = R->P;
+    a.w = !dgrad ? R->w[l] : prep ? prep + P.flipt[l] : nullptr;
+    if (!prep || l < 1 || !wino_layer_on(dgrad ? 16 + l : l)) return a;
+    const WinoGen g = wino_gen();
+    const PrepFilters& f = P.f[l][dgrad];
+    if (P.mask & PREP_F2) {
+        a.w_wino = prep + f.wino;
+        a.w_wino2 = prep + f.wino2;
+    }
+    if ((P.mask & PREP_W4) && !g.f4_reg()) a.w_wino4 = prep + f.wino4;
+    if ((P.mask & PREP_W4T) && g.f4_reg()) {
+        a.w_wino4t = prep + f.wino4t;
+        if (a.Cout % 128 == 0) a.w_wino4u = prep + f.wino4u;
+    }
+    if (R->offer_w6 && (P.mask & PREP_W6) && vgg_want_w6() && L.w6ws_floats && w6_layer_ok(l, dgrad)) {
+        a.w_wino6 = reinterpret_cast<const unsigned short*>(prep + f.wino6);
+        a.w6_ws = R->ws + L.w6ws;
+        a.w6_ws_floats = L.w6ws_floats;
+        w6_pipe_args(&a, R->aux);
+    }
+    return a;
+}
 void vgg_layout(int N, int H, int W, const fs_loss_cfg& cfg, bool with_content, VggLayout* L) {
     memset(L, 0, sizeof(*L));
     L->N = N;
@@ -199,20 +255,17 @@ void vgg_layout(int N, int H, int W, const fs_loss_cfg& cfg, bool with_content, 
     L->d_tap = b.take(max_act);
     L->d_tap2 = b.take(max_act);
     L->scratch = b.take(2048);
-    // split-K scratch: plan every VGG conv (forward at its batch, dgrad at N) with unlimited scratch and keep the max need
-    size_t need = 0;
+    // split-K scratch: plan every VGG conv (forward at its batch, dgrad at N) with unlimited scratch and keep the max need; scratch of the split-bf16
+    // pipeline (FS_WINO_V=6): V + M of the largest launch that may take it, one pass (capped: beyond the cap the launch runs in tile chunks)
+    size_t need = 0, need6 = 0;
     for (int l = 0; l <= lmax; ++l)
         for (int dir = 0; dir < 2; ++dir) {
             if (dir == 1 && l == 0) continue;
-            ConvArgs a{};
-            a.N = dir == 0 ? (l <= cmax ? L->NB : N) : N;
-            a.H = a.Ho = L->Hl[l];
-            a.W = a.Wo = L->Wl[l];
-            a.Cin = dir == 0 ? kCin[l] : kCout[l];
-            a.Cout = dir == 0 ? kCout[l] : kCin[l];
-            a.KH = a.KW = 3;
-            a.stride = 1;
-            a.pad_t = a.pad_l = 1;
+            ConvArgs a = vgg_conv_args(*L, l, dir == 1, dir == 0 && l <= cmax ? L->NB : N, nullptr);
+            if (vgg_want_w6() && w6_layer_ok(l, dir == 1)) {
+                const size_t f = wino6_ws_floats(a.N, a.H, a.W, a.Cin, a.Cout);
+                if (f > need6) need6 = f;
+            }
             a.split_ws = reinterpret_cast<float*>(16);
             a.split_ws_floats = ~(size_t)0;
             const ConvPlan p = conv_plan(a);
@@ -221,22 +274,12 @@ void vgg_layout(int N, int H, int W, const fs_loss_cfg& cfg, bool with_content, 
         }
     L->splitws_floats = need;
     L->splitws = b.take(need ? need : 4);
-    // scratch of the split-bf16 pipeline (FS_WINO_V=6): V + M of the largest launch that may take it, one pass (capped: beyond the cap the launch runs in tile chunks)
-    size_t need6 = 0;
-    if (vgg_want_w6())
-        for (int l = 1; l <= lmax; ++l)
-            for (int dir = 0; dir < 2; ++dir) {
-                if (!w6_layer_ok(l, dir == 1)) continue;
-                const size_t f = wino6_ws_floats(dir == 0 ? (l <= cmax ? L->NB : N) : N, L->Hl[l], L->Wl[l], dir == 0 ? kCin[l] : kCout[l], dir == 0 ? kCout[l] : kCin[l]);
-                if (f > need6) need6 = f;
-            }
     const size_t cap6 = (size_t)knob(K_WINO6_WS_MB) * (1u << 18);   // floats
     if (need6 > cap6) need6 = cap6;
     L->w6ws_floats = need6;
     L->w6ws = b.take(need6 ? need6 : 4);
     L->total_floats = b.off;
 }
-
 
 // Two half-batch chains on two streams (round 6, the split-bf16 pipeline only).  A run of consecutive layers that all take fs_wino6.hip is launched as chain A
 // (samples [0, N/2)) on the caller's stream and chain B (the other half) on the side stream: the layers of a chain depend on each other, the chains do not, so
@@ -256,7 +299,7 @@ static void w6_pipe_args(ConvArgs* a, const StreamAux* aux) {
 // (a half of at least FS_WINO6_CHAIN_MINTILES tiles, default 1024 = conv4_x at batch 32, where the chains were measured; below it -- batch 4 per GPU: 256 tiles
 // per launch -- ONE chain: 3.283 -> 3.239 ms per batch-4 step against the fp32 kernel's split-K launches, profiles/r06_ab_wino6_exact_waits.txt)
 static bool w6_chain_launch_ok(const ConvArgs& a) {
-    return a.p.variant == 12 && !(a.N & 1) && !a.y_keep_n && (long)(a.N / 2) * cdiv(a.Ho, 4) * cdiv(a.Wo, 4) >= (long)knob(K_WINO6_CHAIN_MINTILES) &&
+    return a.p.variant == CV_WINO6 && !(a.N & 1) && !a.y_keep_n && (long)(a.N / 2) * cdiv(a.Ho, 4) * cdiv(a.Wo, 4) >= (long)knob(K_WINO6_CHAIN_MINTILES) &&
            a.w6_ws_floats >= 2 * wino6_ws_floats(a.N / 2, a.Ho, a.Wo, a.Cin, a.Cout);
 }
 struct W6Chains {   // fork / join bookkeeping of one run
@@ -300,7 +343,7 @@ int W6Chains::launch(const ConvArgs& a) {
         hb[h] = w6_half(a, h);
         hb[h].p = conv_plan(hb[h]);
     }
-    if (hb[0].p.variant != 12 || hb[1].p.variant != 12) {   // (a half the pipeline does not take -- knobs that disagree: FS_WINO6_CHAIN_MINTILES below FS_WINO6_MINTILES): the whole launch on the caller's stream
+    if (hb[0].p.variant != CV_WINO6 || hb[1].p.variant != CV_WINO6) {   // (a half the pipeline does not take -- knobs that disagree: FS_WINO6_CHAIN_MINTILES below FS_WINO6_MINTILES): the whole launch on the caller's stream
         FS_TRY(end());
         return conv_launch(a, s);
     }
@@ -309,45 +352,22 @@ int W6Chains::launch(const ConvArgs& a) {
     return 0;
 }
 
-// pool: optional destination of the 2x2/2 max-pool of the result; *pooled tells whether the conv launch produced it
-static int vgg_conv(const float* x, int N, int H, int W, int l, const float* w, const float* w_wino, const float* w_wino2, const float* w_wino4, const float* w_wino4t, const float* w_wino4u, const float* bias, const float* ab,
-                    float* y, float* split_ws, size_t split_ws_floats, hipStream_t s, float* pool = nullptr, bool* pooled = nullptr, int y_keep_n = 0,
-                    const unsigned short* w_wino6 = nullptr, float* w6_ws = nullptr, size_t w6_ws_floats = 0, W6Chains* chains = nullptr, const StreamAux* aux = nullptr) {
-    ConvArgs a{};
-    if (w_wino6) w6_pipe_args(&a, aux);
-    a.w_wino6 = w_wino6;
-    a.w6_ws = w6_ws;
-    a.w6_ws_floats = w6_ws_floats;
-    a.x = x;
-    a.w = w;
-    a.w_wino = w_wino;
-    a.w_wino2 = w_wino2;
-    a.w_wino4 = w_wino4;
-    a.w_wino4t = w_wino4t;
-    a.w_wino4u = w_wino4u;
-    a.y = y;
-    a.N = N;
-    a.H = a.Ho = H;
-    a.W = a.Wo = W;
-    a.Cin = kCin[l];
-    a.Cout = kCout[l];
-    a.KH = a.KW = 3;
-    a.stride = 1;
-    a.pad_t = a.pad_l = 1;
+// What only the forward launches have, on top of vgg_conv_args (a.x, a.y set by the caller): bias + ReLU, the image-mean affine of layer 0, the pooling
+// epilogue and the chains.  pool: optional destination of the 2x2/2 max-pool of the result; *pooled tells whether the conv launch produced it
+static int vgg_conv(ConvArgs a, int l, const float* bias, const float* ab, float* pool, bool* pooled, int y_keep_n, W6Chains* chains, hipStream_t s) {
     a.bias = bias;
     a.out_relu = 1;
-    a.split_ws = split_ws;
-    a.split_ws_floats = split_ws_floats;
     if (l == 0) {  // images - mean folded into the load (padding stays zero, as in TF)
         a.in_a = ab;
         a.in_b = ab + 4;
     }
     a.p = conv_plan(a);
-    if (pooled) *pooled = false;
-    if (pool && (a.p.variant == 5 || a.p.variant == 6 || a.p.variant == 10 || a.p.variant == 11 || a.p.variant == 12) && a.p.ksplit <= 1 && !(H & 1) && !(W & 1) && knob(K_VGG_POOL_FUSED)) {
+    *pooled = false;
+    const ConvFamily* fam = conv_family(a.p.variant);
+    if (pool && fam && fam->pool_epilogue && a.p.ksplit <= 1 && !(a.H & 1) && !(a.W & 1) && knob(K_VGG_POOL_FUSED)) {
         a.pool_out = pool;   // the Winograd epilogues hold whole 2x2 tiles: the pooled tensor comes for one extra store per tile
-        if (pooled) *pooled = true;
-        if ((a.p.variant == 11 || a.p.variant == 12) && knob(K_VGG_SKIP_CONTENT_Y)) a.y_keep_n = y_keep_n;
+        *pooled = true;
+        if (fam->keeps_n && knob(K_VGG_SKIP_CONTENT_Y)) a.y_keep_n = y_keep_n;
     }
     if (chains) {   // (a run of split-bf16 launches goes out as two half-batch chains; anything else closes the run first)
         if (w6_chain_launch_ok(a)) return chains->launch(a);
@@ -357,36 +377,29 @@ static int vgg_conv(const float* x, int N, int H, int W, int l, const float* w, 
 }
 
 // forward through layers [0..lmax]; samples [0,N) go all the way, [N,NB) stop after cmax
-// prepared: the buffer of fs_vgg_prepare (Winograd-transformed filters) or nullptr (direct convolutions only)
-static int vgg_forward(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], const float* const b[FS_VGG_NLAYERS],
-                       const float* prepared, float* ws, hipStream_t s, unsigned prep_mask = 0, const StreamAux* aux = nullptr) {
+// R.prepared: the buffer of fs_vgg_prepare (Winograd-transformed filters) or nullptr (direct convolutions only)
+static int vgg_forward(const VggLayout& L, const VggRun& R, const float* const b[FS_VGG_NLAYERS], hipStream_t s) {
+    float* ws = R.ws;
     FS_TRY(vgg_consts(ws + L.ab, s));
-    const PrepLayout P = prep_layout(prepared ? prep_mask : 0);
-    W6Chains chains{aux, s};
-    const bool use_chains = w6_chains_on(aux, L.N);
+    W6Chains chains{R.aux, s};
+    const bool use_chains = w6_chains_on(R.aux, L.N);
     const float* src = ws + L.xin;
     for (int l = 0; l <= L.lmax; ++l) {
-        bool pooled = false;
         const int nb = l <= L.cmax ? L.NB : L.N;
-        const bool wl = prepared && l >= 1 && wino_layer_on(l);
-        const bool f2 = wl && (P.mask & PREP_F2), w4 = wl && (P.mask & PREP_W4) && !vgg_use_4t(), w4t = wl && (P.mask & PREP_W4T) && vgg_use_4t();
-        const bool w6 = wl && (P.mask & PREP_W6) && vgg_want_w6() && L.w6ws_floats && w6_layer_ok(l, false);
-        FS_TRY(vgg_conv(src, nb, L.Hl[l], L.Wl[l], l, w[l], f2 ? prepared + P.wino[l][0] : nullptr, f2 ? prepared + P.wino2[l][0] : nullptr,
-                        w4 ? prepared + P.wino4[l][0] : nullptr, w4t ? prepared + P.wino4t[l][0] : nullptr,
-                        (w4t && kCout[l] % 128 == 0) ? prepared + P.wino4u[l][0] : nullptr, b[l],
-                        ws + L.ab, ws + L.act[l], ws + L.splitws, L.splitws_floats, s,
-                        (pool_after(l) && l < L.lmax) ? ws + L.pool[pool_index(l)] : nullptr, &pooled,
-                        // (the content half [N, NB) only feeds the next layer: of a pooled layer below the LAST content layer it needs the pooled tensor
-                        // alone -- unless a content term of its own reads the full-resolution half, --loss_content_layers takes several)
-                        (nb > L.N && l < L.cmax && !((L.content_mask >> l) & 1u)) ? L.N : 0,
-                        w6 ? reinterpret_cast<const unsigned short*>(prepared + P.wino6[l][0]) : nullptr, ws + L.w6ws, L.w6ws_floats,
-                        (use_chains && nb == L.N) ? &chains : nullptr, aux));
-        src = ws + L.act[l];
-        if (pool_after(l) && l < L.lmax) {
+        ConvArgs a = vgg_conv_args(L, l, false, nb, &R);
+        a.x = src;
+        a.y = ws + L.act[l];
+        float* pool = (pool_after(l) && l < L.lmax) ? ws + L.pool[pool_index(l)] : nullptr;
+        // (the content half [N, NB) only feeds the next layer: of a pooled layer below the LAST content layer it needs the pooled tensor
+        // alone -- unless a content term of its own reads the full-resolution half, --loss_content_layers takes several)
+        const int y_keep_n = (nb > L.N && l < L.cmax && !((L.content_mask >> l) & 1u)) ? L.N : 0;
+        bool pooled = false;
+        FS_TRY(vgg_conv(a, l, b[l], ws + L.ab, pool, &pooled, y_keep_n, (use_chains && nb == L.N) ? &chains : nullptr, s));
+        src = a.y;
+        if (pool) {
             FS_TRY(chains.end());
-            if (!pooled)
-                FS_TRY(maxpool(ws + L.act[l], ws + L.pool[pool_index(l)], nb, L.Hl[l], L.Wl[l], kCout[l], s));
-            src = ws + L.pool[pool_index(l)];
+            if (!pooled) FS_TRY(maxpool(a.y, pool, nb, L.Hl[l], L.Wl[l], kCout[l], s));
+            src = pool;
         }
     }
     return chains.end();
@@ -409,7 +422,7 @@ int vgg_features(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], const
                  int n_layers, const int* layers, float* const* out, float* ws, hipStream_t s) {
     if (hipMemcpyAsync(ws + L.xin, x, (size_t)L.N * L.H * L.W * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
         return -10;
-    FS_TRY(vgg_forward(L, w, b, nullptr, ws, s));
+    FS_TRY(vgg_forward(L, vgg_run(w, nullptr, 0, ws), b, s));
     for (int i = 0; i < n_layers; ++i) {
         const int l = layers[i];
         const size_t bytes = (size_t)L.N * L.Hl[l] * L.Wl[l] * kCout[l] * sizeof(float);
@@ -418,77 +431,100 @@ int vgg_features(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], const
     return 0;
 }
 
-// Adjoint of vgg_features (round 6; the pieces train.py:198-204 / slow_style.py:140-176 differentiate through when a script composes its own objective):
-// dfeat[i] = dL/d(post-ReLU activation of layers[i]) [N,Hl,Wl,C] for any subset of layers -> dx = dL/d(images) [N,H,W,3].  The forward is recomputed
-// into the workspace (VGG is frozen; with `prepared` on the Winograd kernels of fs_perceptual_loss, without on the direct ones), then the backward of
-// perceptual_loss with the given tensors as tap gradients: per layer the 3x3 input-gradient conv with the flip-transposed filter, the tap added and the ReLU
-// mask applied in its epilogue, the 2x2 max-pool gradient routed to the first maximum (TF MaxPoolGrad) by vgg_bwd_route.
-int vgg_dgrad(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], const float* const b[FS_VGG_NLAYERS], const float* prepared, unsigned prep_mask,
-              const float* x, int n_layers, const int* layers, const float* const* dfeat, float* dx, float* ws, float* flipt_scratch, hipStream_t s) {
+// The backward walk over layers lmax..0 behind a forward (vgg_dgrad, perceptual_loss).  d_pre[l] = (gradient reaching act[l]) * (act[l] > 0).  For the
+// last layer it is the tap gradient alone; below, the dgrad conv of layer l either writes d_pre[l-1] directly (no pool in between: tap add and ReLU mask
+// fused into its epilogue) or writes the pooled gradient that vgg_bwd_route scatters.  The callers differ in where a layer's tap gradient comes from:
+// tap_grad(l, &tap, fuse_above, fuse_dst, &fused) has the contract of perceptual_loss's compute_tap; bit l of tap_layers: layer l has one.
+// flipt_scratch: see vgg_dgrad.
+template <class TapGrad>
+static int vgg_backward(const VggLayout& L, const VggRun& R, unsigned tap_layers, TapGrad&& tap_grad, float* dx, float* flipt_scratch, hipStream_t s) {
     const int N = L.N;
-    if (x != ws + L.xin && hipMemcpyAsync(ws + L.xin, x, (size_t)N * L.H * L.W * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return -10;
-    FS_TRY(vgg_forward(L, w, b, prepared, ws, s, prep_mask));
-    const PrepLayout P = prep_layout(prepared ? prep_mask : 0);
-    auto tap_of = [&](int l) -> const float* {
-        for (int i = 0; i < n_layers; ++i)
-            if (layers[i] == l) return dfeat[i];
-        return nullptr;
-    };
+    float* ws = R.ws;
     float* pre_cur = ws + L.d_pre;
     float* pre_nxt = ws + L.d_in[0];
-    FS_TRY(vgg_bwd_route(ws + L.act[L.lmax], nullptr, tap_of(L.lmax), 0, pre_cur, N, L.Hl[L.lmax], L.Wl[L.lmax], kCout[L.lmax], s));
+    {
+        const float* tap = nullptr;
+        bool fused = false;
+        FS_TRY(tap_grad(L.lmax, &tap, nullptr, pre_cur, &fused));
+        if (!fused)
+            FS_TRY(vgg_bwd_route(ws + L.act[L.lmax], nullptr, tap, 0, pre_cur, N, L.Hl[L.lmax], L.Wl[L.lmax], kCout[L.lmax], s));
+    }
+    // (runs of split-bf16 input-gradient launches -- conv4_3, conv4_2, conv4_1 at the training shapes -- go out as two half-batch chains, see W6Chains)
+    W6Chains chains{R.aux, s};
+    const bool use_chains = w6_chains_on(R.aux, N);
+    auto launch = [&](const ConvArgs& a) -> int {
+        if (use_chains && w6_chain_launch_ok(a)) return chains.launch(a);
+        FS_TRY(chains.end());
+        return conv_launch(a, s);
+    };
     for (int l = L.lmax; l >= 0; --l) {
-        ConvArgs a{};
+        ConvArgs a = vgg_conv_args(L, l, true, N, &R);
         a.x = pre_cur;
-        a.N = N;
-        a.H = a.Ho = L.Hl[l];
-        a.W = a.Wo = L.Wl[l];
-        a.Cin = kCout[l];
-        a.Cout = kCin[l];
-        a.KH = a.KW = 3;
-        a.stride = 1;
-        a.pad_t = a.pad_l = 1;
-        float* flipt = nullptr;
-        if (prepared) {
-            a.w = prepared + P.flipt[l];
-            const bool wl = l >= 1 && wino_layer_on(16 + l);
-            a.w_wino = (wl && (P.mask & PREP_F2)) ? prepared + P.wino[l][1] : nullptr;
-            a.w_wino2 = (wl && (P.mask & PREP_F2)) ? prepared + P.wino2[l][1] : nullptr;
-            a.w_wino4 = (wl && (P.mask & PREP_W4) && !vgg_use_4t()) ? prepared + P.wino4[l][1] : nullptr;
-            a.w_wino4t = (wl && (P.mask & PREP_W4T) && vgg_use_4t()) ? prepared + P.wino4t[l][1] : nullptr;
-            a.w_wino4u = (a.w_wino4t && kCin[l] % 128 == 0) ? prepared + P.wino4u[l][1] : nullptr;
-        } else {   // no prepared buffer: flip-transpose this layer's filter into the caller's scratch (9 * 512 * 512 floats)
-            flipt = flipt_scratch;
-            FS_TRY(wt_flip_transpose(w[l], flipt, 3, 3, kCin[l], kCout[l], s));
-            a.w = flipt;
+        if (!a.w) {   // no prepared buffer: flip-transpose this layer's filter into the caller's scratch
+            FS_TRY(wt_flip_transpose(R.w[l], flipt_scratch, 3, 3, kCin[l], kCout[l], s));
+            a.w = flipt_scratch;
         }
-        a.split_ws = ws + L.splitws;
-        a.split_ws_floats = L.splitws_floats;
         if (l == 0) {
+            FS_TRY(chains.end());
             a.y = dx;
-            if (conv3x3_to3_eligible(a)) return conv3x3_to3_launch(a, s);
+            if (conv3x3_to3_eligible(a)) return conv3x3_to3_launch(a, s);   // 64 -> 3 channels: vector-ALU kernel (fs_c3.hip), no padded MFMA columns
             a.p = conv_plan(a);
             return conv_launch(a, s);
         }
-        const float* tap = tap_of(l - 1);
+        const float* tap = nullptr;
         if (!pool_after(l - 1)) {
+            if ((tap_layers >> (l - 1)) & 1u) FS_TRY(chains.end());   // (a tap gradient is computed on the caller's stream from tensors both chains write: join first)
+            FS_TRY(tap_grad(l - 1, &tap, nullptr, nullptr, nullptr));
             a.y = pre_nxt;
             a.add_src = tap;
             a.add_pad = 0;
             a.mask_src = ws + L.act[l - 1];
             a.p = conv_plan(a);
-            FS_TRY(conv_launch(a, s));
+            FS_TRY(launch(a));
         } else {
             a.y = ws + L.d_in[1];
             a.p = conv_plan(a);
-            FS_TRY(conv_launch(a, s));
-            FS_TRY(vgg_bwd_route(ws + L.act[l - 1], ws + L.d_in[1], tap, 1, pre_nxt, N, L.Hl[l - 1], L.Wl[l - 1], kCout[l - 1], s));
+            FS_TRY(launch(a));
+            FS_TRY(chains.end());
+            bool fused = false;
+            FS_TRY(tap_grad(l - 1, &tap, ws + L.d_in[1], pre_nxt, &fused));
+            if (!fused)
+                FS_TRY(vgg_bwd_route(ws + L.act[l - 1], ws + L.d_in[1], tap, 1, pre_nxt, N, L.Hl[l - 1], L.Wl[l - 1], kCout[l - 1], s));
         }
         float* t = pre_cur;
         pre_cur = pre_nxt;
         pre_nxt = t;
     }
     return 0;
+}
+
+// Adjoint of vgg_features (round 6; the pieces train.py:198-204 / slow_style.py:140-176 differentiate through when a script composes its own objective):
+// dfeat[i] = dL/d(post-ReLU activation of layers[i]) [N,Hl,Wl,C] for any subset of layers -> dx = dL/d(images) [N,H,W,3].  The forward is recomputed
+// into the workspace (VGG is frozen; with `prepared` on the Winograd kernels of fs_perceptual_loss, without on the direct ones), then the backward walk
+// of perceptual_loss with the given tensors as tap gradients (nothing to fuse: they exist): per layer the 3x3 input-gradient conv with the flip-transposed
+// filter, the tap added and the ReLU mask applied in its epilogue, the 2x2 max-pool gradient routed to the first maximum (TF MaxPoolGrad) by vgg_bwd_route.
+// Two things differ from perceptual_loss's walk on purpose:
+//   * its input-gradient launches are never offered the split-bf16 layout and run no chains (the forward above them is offered it);
+//   * without a prepared buffer each layer's filter is flip-transposed into flipt_scratch (the caller's, 9 * 512 * 512 floats) just before its launch.
+int vgg_dgrad(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], const float* const b[FS_VGG_NLAYERS], const float* prepared, unsigned prep_mask,
+              const float* x, int n_layers, const int* layers, const float* const* dfeat, float* dx, float* ws, float* flipt_scratch, hipStream_t s) {
+    if (x != ws + L.xin && hipMemcpyAsync(ws + L.xin, x, (size_t)L.N * L.H * L.W * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return -10;
+    VggRun R = vgg_run(w, prepared, prep_mask, ws);
+    FS_TRY(vgg_forward(L, R, b, s));
+    R.offer_w6 = false;
+    unsigned tap_layers = 0;
+    for (int i = 0; i < n_layers; ++i) tap_layers |= 1u << layers[i];
+    auto given_tap = [&](int l, const float** out, const float*, float*, bool* fused) -> int {
+        *out = nullptr;
+        for (int i = 0; i < n_layers; ++i)
+            if (layers[i] == l) {
+                *out = dfeat[i];
+                break;
+            }
+        if (fused) *fused = false;
+        return 0;
+    };
+    return vgg_backward(L, R, tap_layers, given_tap, dx, flipt_scratch, s);
 }
 
 int style_targets(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], const float* const b[FS_VGG_NLAYERS],
@@ -500,7 +536,7 @@ int style_targets(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], cons
     for (int i = 0; i < cfg.n_style; ++i)
         if (cfg.style_layer[i] > lmax) lmax = cfg.style_layer[i];
     L2.lmax = lmax;
-    FS_TRY(vgg_forward(L2, w, b, nullptr, ws, s));
+    FS_TRY(vgg_forward(L2, vgg_run(w, nullptr, 0, ws), b, s));
     for (int i = 0; i < cfg.n_style; ++i) FS_TRY(gram_forward(L2, cfg.style_layer[i], ws + L2.act[cfg.style_layer[i]], grams[i], ws, s));
     return 0;
 }
@@ -521,8 +557,8 @@ int perceptual_loss(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], co
     // with the fork in the graph the same node behaved).  No memset on any capturable path of the library any more.)
     // (round 5: the four scalars are WRITTEN once, by loss_finish at the end, from the partial sums every term leaves in ws + L.lossp -- the per-term
     // sum launches, the clear and the total are gone)
-    FS_TRY(vgg_forward(L, w, b, prepared, ws, s, prep_mask, aux));
-    const PrepLayout P = prep_layout(prep_mask);
+    const VggRun R = vgg_run(w, prepared, prep_mask, ws, aux);
+    FS_TRY(vgg_forward(L, R, b, s));
 
     // ---- losses ----
     LossFinish lf{};
@@ -579,7 +615,6 @@ int perceptual_loss(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], co
     }
 
     // ---- backward ----
-    // tap gradient of layer l (content term first, the style term accumulates through add_src)
     // tap gradient of layer l (content term first, the style term accumulates through add_src).
     // fuse_dst != nullptr: the caller wants d_pre[l] = (tap + max-pool gradient of fuse_above routed through act[l]) * (act[l] > 0)
     // written to fuse_dst.  A layer whose only term is ONE style term gets that from the epilogue of the Gram-gradient conv
@@ -590,12 +625,10 @@ int perceptual_loss(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], co
         const size_t act_n = (size_t)N * H * W * C;  // the y half
         const float* tap = nullptr;
         if (fused) *fused = false;
-        int n_terms = 0;
-        for (int i = 0; i < cfg.n_content; ++i) n_terms += cfg.content_layer[i] == l;
-        for (int i = 0; i < cfg.n_style; ++i) n_terms += cfg.style_layer[i] == l;
         int n_style_here = 0, n_content_here = 0;
         for (int k = 0; k < cfg.n_style; ++k) n_style_here += cfg.style_layer[k] == l;
         for (int k = 0; k < cfg.n_content; ++k) n_content_here += cfg.content_layer[k] == l;
+        const int n_terms = n_style_here + n_content_here;
         const bool route_in_gram = fuse_dst && fuse_above && n_style_here == 1 && gram_bwd2_route_eligible(N, H, W, C);
         // (round 5) a layer that carries one content and one style term and takes the routed Gram-gradient launch below forms the content term THERE
         // (F is that kernel's operand): no sqdiff pass, no content-gradient tensor
@@ -671,91 +704,10 @@ int perceptual_loss(const VggLayout& L, const float* const w[FS_VGG_NLAYERS], co
         *out = tap;
         return 0;
     };
-    // d_pre[l] = (gradient reaching act[l]) * (act[l] > 0).  For the last layer it is the tap gradient alone;
-    // below, the dgrad conv of layer l either writes d_pre[l-1] directly (no pool in between: tap add and
-    // ReLU mask fused into its epilogue) or writes the pooled gradient that vgg_bwd_route scatters.
-    float* pre_cur = ws + L.d_pre;
-    float* pre_nxt = ws + L.d_in[0];
-    {
-        const float* tap = nullptr;
-        bool fused = false;
-        FS_TRY(compute_tap(L.lmax, &tap, nullptr, pre_cur, &fused));
-        if (!fused)
-            FS_TRY(vgg_bwd_route(ws + L.act[L.lmax], nullptr, tap, 0, pre_cur, N, L.Hl[L.lmax], L.Wl[L.lmax], kCout[L.lmax], s));
-    }
-    // (runs of split-bf16 input-gradient launches -- conv4_3, conv4_2, conv4_1 at the training shapes -- go out as two half-batch chains, see W6Chains)
-    W6Chains bchains{aux, s};
-    const bool use_chains = w6_chains_on(aux, N);
-    auto launch_bwd = [&](const ConvArgs& a) -> int {
-        if (use_chains && w6_chain_launch_ok(a)) return bchains.launch(a);
-        FS_TRY(bchains.end());
-        return conv_launch(a, s);
-    };
-    for (int l = L.lmax; l >= 0; --l) {
-        const int C = kCout[l], H = L.Hl[l], W = L.Wl[l];
-        ConvArgs a{};
-        a.x = pre_cur;
-        a.w = prepared + P.flipt[l];
-        const bool wl = l >= 1 && wino_layer_on(16 + l);
-        a.w_wino = (wl && (P.mask & PREP_F2)) ? prepared + P.wino[l][1] : nullptr;
-        a.w_wino2 = (wl && (P.mask & PREP_F2)) ? prepared + P.wino2[l][1] : nullptr;
-        a.w_wino4 = (wl && (P.mask & PREP_W4) && !vgg_use_4t()) ? prepared + P.wino4[l][1] : nullptr;
-        a.w_wino4t = (wl && (P.mask & PREP_W4T) && vgg_use_4t()) ? prepared + P.wino4t[l][1] : nullptr;
-        a.w_wino4u = (a.w_wino4t && kCin[l] % 128 == 0) ? prepared + P.wino4u[l][1] : nullptr;
-        if (wl && (P.mask & PREP_W6) && vgg_want_w6() && L.w6ws_floats && w6_layer_ok(l, true)) {
-            a.w_wino6 = reinterpret_cast<const unsigned short*>(prepared + P.wino6[l][1]);
-            a.w6_ws = ws + L.w6ws;
-            a.w6_ws_floats = L.w6ws_floats;
-            w6_pipe_args(&a, aux);
-        }
-        a.N = N;
-        a.H = a.Ho = H;
-        a.W = a.Wo = W;
-        a.Cin = C;
-        a.Cout = kCin[l];
-        a.KH = a.KW = 3;
-        a.stride = 1;
-        a.pad_t = a.pad_l = 1;
-        a.split_ws = ws + L.splitws;
-        a.split_ws_floats = L.splitws_floats;
-        if (l == 0) {
-            FS_TRY(bchains.end());
-            a.y = dy;
-            if (conv3x3_to3_eligible(a)) {   // 64 -> 3 channels: vector-ALU kernel (fs_c3.hip), no padded MFMA columns
-                FS_TRY(conv3x3_to3_launch(a, s));
-                break;
-            }
-            a.p = conv_plan(a);
-            FS_TRY(conv_launch(a, s));
-            break;
-        }
-        const float* tap = nullptr;
-        if (!pool_after(l - 1)) {
-            bool has_tap = false;   // (a tap gradient is computed on the caller's stream from tensors both chains write: join first)
-            for (int i = 0; i < cfg.n_content; ++i) has_tap = has_tap || cfg.content_layer[i] == l - 1;
-            for (int i = 0; i < cfg.n_style; ++i) has_tap = has_tap || cfg.style_layer[i] == l - 1;
-            if (has_tap) FS_TRY(bchains.end());
-            FS_TRY(compute_tap(l - 1, &tap, nullptr, nullptr, nullptr));
-            a.y = pre_nxt;
-            a.add_src = tap;
-            a.add_pad = 0;
-            a.mask_src = ws + L.act[l - 1];
-            a.p = conv_plan(a);
-            FS_TRY(launch_bwd(a));
-        } else {
-            a.y = ws + L.d_in[1];
-            a.p = conv_plan(a);
-            FS_TRY(launch_bwd(a));
-            FS_TRY(bchains.end());
-            bool fused = false;
-            FS_TRY(compute_tap(l - 1, &tap, ws + L.d_in[1], pre_nxt, &fused));
-            if (!fused)
-                FS_TRY(vgg_bwd_route(ws + L.act[l - 1], ws + L.d_in[1], tap, 1, pre_nxt, N, L.Hl[l - 1], L.Wl[l - 1], kCout[l - 1], s));
-        }
-        float* t = pre_cur;
-        pre_cur = pre_nxt;
-        pre_nxt = t;
-    }
+    unsigned tap_layers = 0;   // the layers that carry a term
+    for (int i = 0; i < cfg.n_content; ++i) tap_layers |= 1u << cfg.content_layer[i];
+    for (int i = 0; i < cfg.n_style; ++i) tap_layers |= 1u << cfg.style_layer[i];
+    FS_TRY(vgg_backward(L, R, tap_layers, compute_tap, dy, nullptr, s));
     // TV term on y itself (reference losses.py:70-97, train.py:183-184); beta defaults to 0
     if (cfg.beta != 0.0f) {
         float* pp = term(3, 1024, cfg.beta);

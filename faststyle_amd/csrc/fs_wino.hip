@@ -522,7 +522,7 @@ bool wino_eligible(const ConvArgs& a) {
 // workgroup of 8 waves per CU) and scratch for the partials is available
 void wino_plan(const ConvArgs& a, ConvPlan* out) {
     ConvPlan p{};
-    p.variant = 5;
+    p.variant = CV_WINO;
     p.BN = kBN;
     p.CC = kCC;
     p.TH = p.TW = 2 * kTT;

@@ -806,7 +806,7 @@ bool wino2_eligible(const ConvArgs& a) {
 
 void wino2_plan(const ConvArgs& a, ConvPlan* out) {
     ConvPlan p{};
-    p.variant = 6;
+    p.variant = CV_WINO2;
     p.BN = kBN;
     p.CC = kCC;
     p.TH = p.TW = 2 * kTT;

@@ -578,7 +578,7 @@ void wino2h_plan(const ConvArgs& a, ConvPlan* out) {
     ConvPlan p{};
     int bh = 4, bw = 8;
     wino2h_shape(a.Ho, a.Wo, &bh, &bw);
-    p.variant = 8;
+    p.variant = CV_WINO2H;
     p.BN = kBN;
     p.CC = kCC;
     p.TH = 2 * bh;

@@ -622,7 +622,7 @@ bool wino4_eligible(const ConvArgs& a) {
 
 void wino4_plan(const ConvArgs& a, ConvPlan* out) {
     ConvPlan p{};
-    p.variant = 10;
+    p.variant = CV_WINO4;
     p.BN = kBN;
     p.CC = kCC;
     p.TH = kBH;

@@ -158,7 +158,7 @@ void wino4t_plan(const ConvArgs& a, ConvPlan* out) {
     ConvPlan p{};
     const bool cb2 = wino4t_use_cb2(a);
     const int tb = cb2 ? 1 : wino4t_pick_tb(a);
-    p.variant = 11;
+    p.variant = CV_WINO4T;
     p.BN = cb2 ? 2 * kBN : kBN;
     p.CC = kCC;
     p.TH = kBH;

@@ -465,7 +465,7 @@ bool wino6_eligible(const ConvArgs& a) {
 
 void wino6_plan(const ConvArgs& a, ConvPlan* out) {
     ConvPlan p{};
-    p.variant = 12;
+    p.variant = CV_WINO6;
     p.BN = kW6TN;
     p.CC = kW6K;
     p.TH = p.TW = 4;

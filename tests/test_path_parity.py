@@ -524,6 +524,121 @@ def test_vgg_dgrad_named_export_matches_oracle(eng, layers, prepared):
     assert flat_close(dx, want)
 
 
+# ----------------------------------------------------------------------------- which kernels a VGG16 launch is handed, per Winograd generation
+# The prepared buffer is built under `prepare`, the calls run under `run` (a buffer prepared under other knobs must fall to the direct kernels).
+SELECTION_SETTINGS = {
+    "v1": ({"FS_WINO_V": 1}, {}),
+    "v2": ({"FS_WINO_V": 2}, {}),
+    "v4": ({"FS_WINO_V": 4}, {}),
+    "v5": ({"FS_WINO_V": 5}, {}),
+    "v6": ({"FS_WINO_V": 6, "FS_WINO6_MINCC": 0, "FS_WINO6_MINTILES": 1}, {}),
+    "wino_off": ({"FS_CONV_WINO": 0}, {}),
+    "prepared_v6_run_v4": ({"FS_WINO_V": 6, "FS_WINO6_MINCC": 0, "FS_WINO6_MINTILES": 1}, {"FS_WINO_V": 4}),
+}
+SELECTION_DGRAD_LAYERS = ("conv1_2", "conv2_2", "conv3_3", "conv4_3")
+# profiler rows (fs_profile_family_name) the tables below speak of
+I22, I21, I41, I12, I11 = ("conv_igemm_kernel<%s>" % t for t in ("32,2,2", "32,2,1", "16,4,1", "32,1,2", "32,1,1"))
+WINO, WINO2, WINO4, WINO4T = "wino_conv_kernel", "wino2_conv_kernel (VGG16 convs)", "wino4_conv_kernel", "wino4t_conv_kernel (VGG16 convs)"
+WINO6 = "wino6 pipeline (VGG16 convs: input transform + split-bf16 GEMMs + output transform)"
+C3, GSTREAM, GWGRAD, GBWD, GBWD_I = ("conv3x3_to3_kernel", "gram_stream_kernel", "conv_wgrad_kernel (Gram forward)", "gram_bwd_kernel",
+                                     "conv_igemm_kernel (Gram backward, 1x1 per-sample filters)")
+# Launch counts per profiler row of one fs_perceptual_loss call and one fs_vgg_dgrad call, RECORDED ON THE PARENT COMMIT of the change that gave the VGG16
+# launches one args builder (this test uses existing exports only and ran there unchanged; the tables were pasted from its printed output -- never taken
+# from the code under test).  Recorded with the parent's sources on the emulator at 1 x 20 x 28 AND at 2 x 36 x 44: the same counts at both shapes.  Which
+# kernel a launch takes is decided by host code that asks the device nothing, so the product library on the GPU plans the same launches at 2 x 36 x 44:
+# the "hip" entries are those tables.
+SELECTION_LAUNCHES = {
+    ("emu", "v1"): {"perceptual_loss": {I22: 1, WINO: 18, C3: 1, GSTREAM: 4, GBWD: 3, GBWD_I: 1},
+        "vgg_dgrad": {I22: 1, WINO: 18, C3: 1}},
+    ("emu", "v2"): {"perceptual_loss": {I22: 1, WINO: 11, WINO2: 7, C3: 1, GSTREAM: 4, GBWD: 3, GBWD_I: 1},
+        "vgg_dgrad": {I22: 1, WINO: 11, WINO2: 7, C3: 1}},
+    ("emu", "v4"): {"perceptual_loss": {I22: 1, C3: 1, GSTREAM: 4, GBWD: 3, GBWD_I: 1, WINO4: 18},
+        "vgg_dgrad": {I22: 1, C3: 1, WINO4: 18}},
+    ("emu", "v5"): {"perceptual_loss": {I22: 1, C3: 1, GSTREAM: 4, GBWD: 3, GBWD_I: 1, WINO4T: 18},
+        "vgg_dgrad": {I22: 1, C3: 1, WINO4T: 18}},
+    ("emu", "v6"): {"perceptual_loss": {I22: 1, C3: 1, GSTREAM: 4, GBWD: 3, GBWD_I: 1, WINO4T: 3, WINO6: 15},
+        "vgg_dgrad": {I22: 1, C3: 1, WINO4T: 10, WINO6: 8}},
+    ("emu", "wino_off"): {"perceptual_loss": {I22: 1, I11: 18, C3: 1, GSTREAM: 4, GBWD: 3, GBWD_I: 1},
+        "vgg_dgrad": {I22: 1, I11: 18, C3: 1}},
+    ("emu", "prepared_v6_run_v4"): {"perceptual_loss": {I22: 1, I11: 18, C3: 1, GSTREAM: 4, GBWD: 3, GBWD_I: 1},
+        "vgg_dgrad": {I22: 1, I11: 18, C3: 1}},
+}
+SELECTION_LAUNCHES.update({("hip", setting): table for (_, setting), table in list(SELECTION_LAUNCHES.items())})
+
+
+def profiled_launches(eng, call):
+    """call() under fs_profile_begin / fs_profile_end -> (its result, {row name: launches} of the rows that saw a launch)."""
+    import ctypes
+    from faststyle_amd import _lib
+    assert eng.lib.fs_profile_begin(eng.ctx) == 0
+    try:
+        out = call()
+    finally:
+        buf = (ctypes.c_double * (3 * _lib.FS_PROFILE_FAMILIES))()
+        rc = eng.lib.fs_profile_end(eng.ctx, ctypes.byref(buf))
+    assert rc == 0
+    names = _lib.profile_family_names(eng.lib)
+    return out, {names[f]: int(buf[3 * f]) for f in range(_lib.FS_PROFILE_FAMILIES) if buf[3 * f]}
+
+
+_selection_problem = {}
+
+
+def selection_problem(shape):
+    """Inputs and the float64 oracle of the selection test, computed once per shape and shared (read-only) by every setting."""
+    if shape not in _selection_problem:
+        rng = np.random.default_rng(1)
+        Wv = perceptual.synthetic_vgg_weights(seed=3)
+        style = rng.uniform(0, 255, (1, 23, 27, 3)).astype(np.float32)
+        y = rng.uniform(0, 255, shape + (3,)).astype(np.float32)
+        xc = rng.uniform(0, 255, shape + (3,)).astype(np.float32)
+        tgo = perceptual.target_grams(style.astype(np.float64), f64(Wv), engine.default_loss_cfg()["style_layers"])
+        feats = perceptual.vgg16(xc.astype(np.float64), f64(Wv), upto="conv3_3")
+        lo, dyo = perceptual.perceptual_loss(y.astype(np.float64), [feats["conv3_3"]], tgo, f64(Wv), beta=1e-4)
+        upto = max(SELECTION_DGRAD_LAYERS)
+        fy, cache = perceptual.vgg16(y.astype(np.float64), f64(Wv), upto=upto, keep=True)
+        dfe = {n: (rng.standard_normal(fy[n].shape) / np.sqrt(fy[n][0].size)).astype(np.float32) for n in SELECTION_DGRAD_LAYERS}
+        dxo = perceptual.vgg16_bwd({n: dfe[n].astype(np.float64) for n in SELECTION_DGRAD_LAYERS}, fy, f64(Wv), cache, upto=upto)
+        _selection_problem[shape] = dict(Wv=Wv, style=style, y=y, xc=xc, dfe=dfe, dxo=dxo, dyo=dyo,
+                                         losses=[lo[k] for k in ("loss", "content_loss", "style_loss", "tv_loss")])
+    return _selection_problem[shape]
+
+
+@pytest.mark.parametrize("setting", list(SELECTION_SETTINGS))
+def test_vgg_filter_selection_per_generation(eng, knob, setting):
+    """Which prepared filter layouts fs_perceptual_loss and fs_vgg_dgrad hand their 3x3 launches: FS_WINO_V 1, 2, 4, 5, 6 with the buffer prepared under the
+    same knob, FS_CONV_WINO=0, and a buffer prepared under FS_WINO_V=6 that runs under FS_WINO_V=4 (no layout both the buffer and the knobs agree on: the
+    direct kernels).  2 x 36 x 44 (emulator: 1 x 20 x 28): the maps behind conv1_2 and conv2_2 have even extents -- the pool comes from the Winograd
+    epilogue --, the one behind conv3_3 is odd -- the separate maxpool --, every tile grid is ragged.  Per setting: the launches per profiler row equal the
+    table recorded on the parent commit, the losses are within 2e-5 of the float64 oracle and both gradients flat_close to it (the assertions of
+    test_perceptual_loss_and_gradient_match_oracle)."""
+    prepare, run = SELECTION_SETTINGS[setting]
+    backend = "emu" if on_emulator(eng) else "hip"
+    pb = selection_problem((1, 20, 28) if backend == "emu" else (2, 36, 44))
+    for k, v in prepare.items():
+        knob(k, v)
+    eng.vgg_load(pb["Wv"])
+    for k, v in run.items():
+        knob(k, v)
+    cfg = engine.default_loss_cfg()
+    cfg["beta"] = 1e-4
+    up = eng.mem.from_numpy
+    tg = eng.style_targets(up(pb["style"]), cfg)
+    (losses, dy), n_loss = profiled_launches(eng, lambda: eng.perceptual_loss(up(pb["y"]), up(pb["xc"]), tg, cfg))
+    losses, dy = eng.mem.to_numpy(losses).copy(), eng.mem.to_numpy(dy).copy()
+    dx, n_dgrad = profiled_launches(eng, lambda: eng.vgg_dgrad(up(pb["y"]), list(SELECTION_DGRAD_LAYERS), [up(pb["dfe"][n]) for n in SELECTION_DGRAD_LAYERS]))
+    dx = eng.mem.to_numpy(dx).copy()
+    print("(%r, %r): {\"perceptual_loss\": %r,\n    \"vgg_dgrad\": %r}," % (backend, setting, n_loss, n_dgrad))
+    print("   loss error %.2e   dy %.2e   dx %.2e (max-abs, relative to the largest element)" % (
+        np.abs(losses / np.asarray(pb["losses"]) - 1).max(), np.abs(dy - pb["dyo"]).max() / np.abs(pb["dyo"]).max(), np.abs(dx - pb["dxo"]).max() / np.abs(pb["dxo"]).max()))
+    want = SELECTION_LAUNCHES[(backend, setting)]
+    assert n_loss == want["perceptual_loss"]
+    assert n_dgrad == want["vgg_dgrad"]
+    np.testing.assert_allclose(losses, pb["losses"], rtol=2e-5)
+    assert flat_close(dy, pb["dyo"])
+    assert flat_close(dx, pb["dxo"])
+
+
 def test_adam_tf_step_matches_oracle(eng):
     rng = np.random.default_rng(2)
     n = 5000
