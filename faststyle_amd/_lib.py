@@ -165,6 +165,10 @@ PROTOTYPES = {
     "fs_jpeg_parse": (c_int, [c_void_p, c_size_t, POINTER(fs_jpeg_info)]),
     "fs_jpeg_decode": (c_int, [c_void_p, c_size_t, POINTER(fs_jpeg_info), c_void_p, c_size_t]),
     "fs_jpeg_reconstruct_many": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
+    "fs_jpeg_forward_many": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
+    "fs_jpeg_encode_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_jpeg_info)]),
+    "fs_jpeg_write_bound": (c_size_t, [POINTER(fs_jpeg_info)]),
+    "fs_jpeg_write": (c_int, [POINTER(fs_jpeg_info), c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_size_t)]),
     "fs_u8_to_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "fs_f32_to_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
 }

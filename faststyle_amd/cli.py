@@ -79,4 +79,7 @@ def stylize_webcam_parser():
         ('--resolution', dict(nargs=2, type=int, default=None, help='capture width height (default: the camera default)')),
         ('--frames_dir', dict(default=None, help='(addition) read frames from this directory instead of a camera')),
         ('--output_dir', dict(default='./frames_out', help='(addition) where --frames_dir results go')),
+        ('--output_format', dict(choices=['png', 'jpg'], default='png', help="(addition) file type of the --frames_dir results: 'png' through PIL, "
+                                                                            "'jpg' encoded by the library (forward DCT on the GPU, 4:2:0)")),
+        ('--output_quality', dict(default=95, type=int, help='(addition) JPEG quality 1..100 of --output_format jpg')),
     ])

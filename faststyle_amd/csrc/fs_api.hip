@@ -155,6 +155,31 @@ int fs_jpeg_reconstruct_many(fs_ctx* ctx, void* coef_base, size_t coef_bytes, co
                                              static_cast<unsigned char*>(rgb_base), rgb_bytes, ctx->stream);
     return rc ? fail(rc, "fs_jpeg_reconstruct_many: launch failed (%d)", rc) : 0;
 }
+int fs_jpeg_forward_many(fs_ctx* ctx, const void* src_base, size_t src_bytes, const fs_jpegenc_item* items_host, const fs_jpegenc_item* items_dev, int K,
+                         void* coef_base, size_t coef_bytes) {
+    if (!ctx || !src_base || !items_host || !items_dev || !coef_base) return fail(-1, "fs_jpeg_forward_many: null argument");
+    if (K < 1 || K > 65535) return fail(-1, "fs_jpeg_forward_many: K must be in [1, 65535], got %d", K);
+    if ((uintptr_t)items_dev & 7) return fail(-5, "fs_jpeg_forward_many: the descriptor table must be 8-byte aligned");
+    if ((uintptr_t)coef_base & 15) return fail(-5, "fs_jpeg_forward_many: coef_base must be 16-byte aligned");
+    unsigned long long max_blocks = 0;
+    for (int k = 0; k < K; ++k) {
+        const fs_jpegenc_item& it = items_host[k];
+        const int rc = fs::jpegenc_item_check(it, src_bytes, coef_bytes);
+        if (rc == -2)
+            return fail(-2, "fs_jpeg_forward_many: image %d: pixel_bytes must be 3 (RGB) or 4 (RGBX), 1 with one component, and quality in [1, 100]; got %d and %d",
+                        k, it.pixel_bytes, it.quality);
+        if (rc == -5 || (rc == 0 && it.pixel_bytes == 4 && ((uintptr_t)src_base & 3)))
+            return fail(-5, "fs_jpeg_forward_many: image %d: coef_offset and qt_offset must be multiples of 16, a source of 4-byte pixels 4-byte aligned", k);
+        if (rc)
+            return fail(rc, "fs_jpeg_forward_many: image %d (%dx%d, %d components, %dx%d sampling) has a bad geometry or does not fit the %zu source / %zu coefficient bytes",
+                        k, it.width, it.height, it.ncomp, it.hs, it.vs, src_bytes, coef_bytes);
+        const unsigned long long b = fs::jpegenc_item_blocks(it);
+        max_blocks = b > max_blocks ? b : max_blocks;
+    }
+    const int rc = fs::jpeg_forward_many(static_cast<const unsigned char*>(src_base), src_bytes, items_dev, K, max_blocks,
+                                         static_cast<unsigned char*>(coef_base), coef_bytes, ctx->stream);
+    return rc ? fail(rc, "fs_jpeg_forward_many: launch failed (%d)", rc) : 0;
+}
 int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
                   const int32_t* move_dst, int M, float* batch_out) {
     if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");

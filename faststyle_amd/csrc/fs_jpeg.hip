@@ -10,34 +10,9 @@
 
 #include <cstring>
 
-#include "fs_kernels.h"
+#include "fs_jpeg.h"
 
 namespace fs {
-namespace {
-
-// ---------------------------------------------------------------- geometry shared by host and device
-struct JpegGeom {
-    int bw[3], bh[3];                 // blocks per row / column of each component plane (whole MCUs)
-    unsigned long long plane[3];      // byte offset of each plane from the image's coefficient offset
-    unsigned long long coef_count;    // int16 coefficients of all planes
-    int cw, ch;                       // true chroma extent: ceil(W / hs), ceil(H / vs)
-};
-
-__host__ __device__ inline void jpeg_geom(int W, int H, int ncomp, int hs, int vs, JpegGeom& g) {
-    const int mx = (W + 8 * hs - 1) / (8 * hs), my = (H + 8 * vs - 1) / (8 * vs);
-    unsigned long long off = 0;
-    for (int c = 0; c < 3; ++c) {
-        g.bw[c] = c < ncomp ? mx * (c ? 1 : hs) : 0;
-        g.bh[c] = c < ncomp ? my * (c ? 1 : vs) : 0;
-        g.plane[c] = off;
-        off += (unsigned long long)g.bw[c] * g.bh[c] * 128;
-    }
-    g.coef_count = off / 2;
-    g.cw = (W + hs - 1) / hs;
-    g.ch = (H + vs - 1) / vs;
-}
-
-}  // namespace
 
 // 0, or the error code of fs_jpeg_reconstruct_many for this descriptor; the kernels skip a descriptor that fails it
 __host__ __device__ int jpeg_item_check(const fs_jpeg_item& it, unsigned long long coef_bytes, unsigned long long rgb_bytes) {
@@ -59,10 +34,6 @@ __host__ __device__ int jpeg_item_check(const fs_jpeg_item& it, unsigned long lo
 namespace {
 
 // ---------------------------------------------------------------- host: markers and Huffman decoding
-const unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                   41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                   30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 constexpr int kLookBits = 9;
 
 struct Huff {
@@ -107,22 +78,6 @@ int build_huff(Huff& h, const unsigned char* counts, const unsigned char* syms, 
     h.maxcode[17] = 0x7fffffff;
     h.set = true;
     return 0;
-}
-
-void fill_info(fs_jpeg_info& in) {
-    JpegGeom g;
-    jpeg_geom(in.width, in.height, in.ncomp, in.hs[0], in.vs[0], g);
-    in.mcu_x = g.bw[0] / in.hs[0];
-    in.mcu_y = g.bh[0] / in.vs[0];
-    for (int c = 0; c < 3; ++c) {
-        in.blocks_x[c] = g.bw[c];
-        in.blocks_y[c] = g.bh[c];
-        in.plane_offset[c] = g.plane[c];
-    }
-    in.coef_count = g.coef_count;
-    in.qt_offset = (g.coef_count * 2 + 15) & ~15ull;
-    in.coef_bytes = in.qt_offset + 384;
-    in.rgb_bytes = (uint64_t)in.width * in.height * 3;
 }
 
 // Markers up to and including SOS.  0: handled (h.info filled, the tables of the scan present), 1: a JPEG for PIL, < 0: malformed.
@@ -192,7 +147,7 @@ int parse_headers(const unsigned char* p, size_t n, Header& h, const char* who) 
                 if (pq > 1 || tq > 3) return set_error(-2, "%s: bad quantisation table header", who);
                 if (pq == 1) return 1;         // 16-bit tables: PIL's
                 if (len < 65) return set_error(-2, "%s: truncated quantisation table", who);
-                for (int i = 0; i < 64; ++i) h.qt[tq][kZigzag[i]] = seg[1 + i];
+                for (int i = 0; i < 64; ++i) h.qt[tq][kJpegZigzag[i]] = seg[1 + i];
                 h.qt_set[tq] = true;
                 seg += 65;
                 len -= 65;
@@ -228,7 +183,7 @@ int parse_headers(const unsigned char* p, size_t n, Header& h, const char* who) 
                 if (h.adobe) return 1;
                 if (!h.jfif && !(h.comp_id[0] == 1 && h.comp_id[1] == 2 && h.comp_id[2] == 3)) return 1;
             }
-            fill_info(h.info);
+            jpeg_fill_info(h.info);
             if (h.info.coef_count > (1ull << 28)) return 1;
             h.info.scan_offset = pos;
             return 0;
@@ -367,7 +322,7 @@ int fs_jpeg_decode(const void* jpeg, size_t n, const fs_jpeg_info* info, void* o
                             }
                             k += r;
                             if (k > 63 || s > 10) return set_error(-4, "fs_jpeg_decode: coefficient outside the block in MCU (%d, %d)", mx, my);
-                            dst[kZigzag[k]] = (int16_t)receive_extend(b, s);
+                            dst[kJpegZigzag[k]] = (int16_t)receive_extend(b, s);
                             ++k;
                         }
                         if (b.overrun()) return set_error(-4, "fs_jpeg_decode: scan data ends in MCU (%d, %d)", mx, my);

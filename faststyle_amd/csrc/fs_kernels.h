@@ -16,6 +16,7 @@ typedef unsigned int fs_u32x4 __attribute__((ext_vector_type(4)));   // payload 
 
 struct fs_resize_item;   // include/faststyle_io.h
 struct fs_jpeg_item;
+struct fs_jpegenc_item;
 
 namespace fs {
 
@@ -669,6 +670,12 @@ __host__ __device__ int jpeg_item_check(const ::fs_jpeg_item& it, unsigned long 
 void jpeg_item_extent(const ::fs_jpeg_item& it, unsigned long long* blocks, unsigned long long* groups);
 int jpeg_reconstruct_many(unsigned char* coef_base, size_t coef_bytes, const ::fs_jpeg_item* items_dev, int K, unsigned long long max_blocks,
                           unsigned long long max_groups, unsigned char* rgb_base, size_t rgb_bytes, hipStream_t s);
+// the device half of the JPEG encoder (fs_jpegenc.hip): the descriptor check shared by fs_jpeg_forward_many and the kernels (0 or that call's
+// error code), one image's block count, and the two launches
+__host__ __device__ int jpegenc_item_check(const ::fs_jpegenc_item& it, unsigned long long src_bytes, unsigned long long coef_bytes);
+unsigned long long jpegenc_item_blocks(const ::fs_jpegenc_item& it);
+int jpeg_forward_many(const unsigned char* src_base, size_t src_bytes, const ::fs_jpegenc_item* items_dev, int K, unsigned long long max_blocks,
+                      unsigned char* coef_base, size_t coef_bytes, hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);
 // ... with the per-sample sums taken from records [N][T][C][2] (rec == nullptr: computed here into `scratch`), reduced in the apply kernel's

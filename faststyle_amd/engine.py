@@ -111,8 +111,8 @@ def default_loss_cfg():
 
 
 class JpegHost(object):
-    """The two host calls of the JPEG decoder (csrc/fs_jpeg.hip).  They need the library and no device: the engine has them through this
-    class, and a tool that measures the host half alone makes a JpegHost of its own."""
+    """The host calls of the JPEG decoder (csrc/fs_jpeg.hip) and encoder (csrc/fs_jpegenc.hip).  They need the library and no device: the engine
+    has them through this class, and a tool that measures the host half alone makes a JpegHost of its own."""
 
     def __init__(self, lib=None):
         self.lib = lib if lib is not None else L.load()
@@ -128,6 +128,33 @@ class JpegHost(object):
         """fs_jpeg_decode: the Huffman pass of a handled JPEG into info.coef_bytes bytes at host address out_addr; returns its answer
         (0, or what makes the caller decode the file with PIL).  Releases the interpreter lock; any number of threads at once."""
         return self.lib.fs_jpeg_decode(data, len(data), ctypes.byref(info), ctypes.c_void_p(out_addr), out_bytes)
+
+    # ---- the encoder's host half (csrc/fs_jpegenc.hip)
+    def jpeg_encode_plan(self, width, height, ncomp=3, hs=2, vs=2):
+        """(answer, info) of fs_jpeg_encode_plan: the fs_jpeg_info of the file jpeg_write writes for this geometry (hs x vs: the luma sampling,
+        2x2 = 4:2:0, 2x1 = 4:2:2, 1x1 = 4:4:4); info is None unless the answer is 0."""
+        info = L.fs_jpeg_info()
+        rc = self.lib.fs_jpeg_encode_plan(int(width), int(height), int(ncomp), int(hs), int(vs), ctypes.byref(info))
+        return rc, (info if rc == 0 else None)
+
+    def jpeg_write_bound(self, info):
+        """fs_jpeg_write_bound: a buffer size that surely holds the file of this info."""
+        return int(self.lib.fs_jpeg_write_bound(ctypes.byref(info)))
+
+    def jpeg_write(self, info, coef_addr, coef_bytes, out_addr, cap):
+        """fs_jpeg_write: Huffman-codes the coefficient buffer at host address coef_addr (what jpeg_forward_many left, downloaded) into the cap
+        bytes at host address out_addr; returns (answer, file length).  Releases the interpreter lock; any number of threads at once."""
+        n = ctypes.c_size_t(0)
+        rc = self.lib.fs_jpeg_write(ctypes.byref(info), ctypes.c_void_p(coef_addr), int(coef_bytes), ctypes.c_void_p(out_addr), int(cap), ctypes.byref(n))
+        return rc, int(n.value)
+
+    def jpeg_write_bytes(self, info, coef):
+        """The file of one image as bytes; coef: host uint8 array holding its coefficient buffer."""
+        coef = np.ascontiguousarray(coef, dtype=np.uint8)
+        out = np.empty(self.jpeg_write_bound(info), dtype=np.uint8)
+        rc, n = self.jpeg_write(info, coef.ctypes.data, coef.nbytes, out.ctypes.data, out.nbytes)
+        L.check(self.lib, rc, "fs_jpeg_write")
+        return out[:n].tobytes()
 
 
 class Engine(JpegHost):
@@ -699,6 +726,30 @@ class Engine(JpegHost):
                 "fs_jpeg_reconstruct_many")
         self._keep = [keep, items]
         return rgb
+
+    # ------------------------------------------------------------------ baseline JPEG encoding (csrc/fs_jpegenc.hip)
+    JPEGENC_ITEM = np.dtype([("src_offset", "<u8"), ("coef_offset", "<u8"), ("qt_offset", "<u8"), ("width", "<i4"), ("height", "<i4"),
+                             ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("pixel_bytes", "<i4"), ("quality", "<i4"),
+                             ("reserved", "<i4")])      # fs_jpegenc_item
+
+    @classmethod
+    def jpegenc_item(cls, info, src_offset, coef_offset, pixel_bytes, quality):
+        """The JPEGENC_ITEM row of an image (info: jpeg_encode_plan's) whose pixels lie at byte src_offset of the source buffer and whose
+        coefficient buffer, the one jpeg_write reads, goes to byte coef_offset."""
+        return (src_offset, coef_offset, coef_offset + info.qt_offset, info.width, info.height, info.ncomp, info.hs[0], info.vs[0], pixel_bytes,
+                quality, 0)
+
+    def jpeg_forward_many(self, src, items, coef, items_dev=None):
+        """fs_jpeg_forward_many: src, coef device uint8 buffers; items host JPEGENC_ITEM rows; the coefficient buffer of every image is written
+        into ``coef`` where its row says.  ``src`` is only read.  items_dev as for resize_bicubic_u8_many."""
+        self._sync_stream()
+        items = np.ascontiguousarray(items, dtype=self.JPEGENC_ITEM)
+        ptr, keep = self._table_ptr(items, items_dev)
+        L.check(self.lib, self.lib.fs_jpeg_forward_many(self.ctx, self.mem.ptr_u8(src), int(np.prod(src.shape)), items.ctypes.data, ptr,
+                                                        int(items.shape[0]), self.mem.ptr_u8(coef), int(np.prod(coef.shape))),
+                "fs_jpeg_forward_many")
+        self._keep = [keep, items]
+        return coef
 
     def synth_uniform(self, out, seed, rank, batch_index):
         """Uniform [0,255) float32 values into ``out``: Philox4x32-10 keyed by seed, counter (element block, batch_index, rank) (fs_synth_uniform)."""

@@ -1,4 +1,4 @@
-/* faststyle_io.h -- C ABI of the training-data input path.
+/* faststyle_io.h -- C ABI of the training-data input path and of the frame tools' image input / output.
  *
  * Replaces, for the reference's train.py input pipeline:
  *   datapipe.py:38-49   tf.TFRecordReader().read + tf.parse_single_example   -> fs_tfrecord_scan, fs_example_bytes/_int64
@@ -10,6 +10,8 @@
  * decoding, stays on the host threads (fs_jpeg_parse / fs_jpeg_decode, no Python work around it); the int16 coefficients cross PCIe and
  * dequantisation, inverse DCT, chroma upsampling and colour conversion run on the GPU (fs_jpeg_reconstruct_many), bit-identical to PIL's
  * decode of the same bytes.  A JPEG outside the handled set is PIL's, as before.
+ * The way out mirrors it (the fs_jpeg_forward_many / fs_jpeg_write calls at the end): a u8 frame on the device becomes quantised coefficients
+ * there, and host threads Huffman-code them into the baseline file PIL would write for the same pixels.
  *
  * The host-side functions are pure C (no HIP calls) and work without a GPU.  All return 0 / a
  * non-negative count on success and a negative code on error (fs_last_error() has the text).
@@ -171,6 +173,63 @@ typedef struct fs_jpeg_item {
  * dst_offset not 4-byte aligned. */
 int fs_jpeg_reconstruct_many(fs_ctx* ctx, void* coef_base, size_t coef_bytes, const fs_jpeg_item* items_host, const fs_jpeg_item* items_dev,
                              int K, void* rgb_base, size_t rgb_bytes);
+
+/* ---- Baseline JPEG encoding (csrc/fs_jpegenc.hip): the decoder's split, the other way round.  The data-parallel part -- colour conversion,
+ * chroma downsampling, forward DCT, quantisation -- runs on the GPU (fs_jpeg_forward_many) and leaves, per image, exactly the coefficient buffer
+ * fs_jpeg_decode would write for the file; the int16 coefficients cross PCIe and the serial part, Huffman coding and the markers, runs on host
+ * threads (fs_jpeg_write: pure C, no HIP calls, no global state, no allocation; any number of threads at once).  The arithmetic is the integer
+ * arithmetic of the IJG library's default compressor (16-bit fixed-point RGB -> YCbCr, box downsampling with the alternating bias, the accurate
+ * integer DCT, the Annex K tables scaled by the quality), and the file is laid out as that library lays it out: the bytes PIL writes for the same
+ * pixels, quality and subsampling (tests/test_jpeg_encode.py).  Not written: optimised Huffman tables, restart markers, progressive or arithmetic
+ * coding, metadata beyond the JFIF header. */
+
+/* One image of fs_jpeg_forward_many: height rows of width pixels of pixel_bytes bytes (3 = RGB, 4 = RGBX with src_offset a multiple of 4 and the
+ * fourth byte never read, 1 = the samples of a grayscale image: ncomp 1), no row padding, src_offset bytes into src_base -- what fs_f32_to_u8 and
+ * fs_jpeg_reconstruct_many produce.  The coefficient planes go to coef_base + coef_offset and the three quantisation tables to coef_base +
+ * qt_offset (both multiples of 16; for a buffer fs_jpeg_write is to read at byte o: coef_offset = o, qt_offset = o + info.qt_offset).
+ * hs, vs: the luma sampling factors, 1x1, 2x1 or 2x2 (4:4:4, 4:2:2, 4:2:0); quality: 1..100, the IJG scale.  56 bytes, 8-byte aligned. */
+typedef struct fs_jpegenc_item {
+    uint64_t src_offset;
+    uint64_t coef_offset;
+    uint64_t qt_offset;
+    int32_t width, height;
+    int32_t ncomp;
+    int32_t hs, vs;
+    int32_t pixel_bytes;
+    int32_t quality;
+    int32_t reserved;
+} fs_jpegenc_item;
+
+/* The mirror of fs_jpeg_reconstruct_many: K images in one launch sequence (two kernels).  Each image's region of coef_base first holds its
+ * component samples (a block's first 64 bytes), then, in place, the quantised coefficients: 64 int16 per block in natural order, planes and
+ * padding to whole MCUs as described at fs_jpeg_info, the tables (64 uint16 each, natural order, zeros beyond ncomp) derived from `quality`:
+ * entry = (Annex K entry * scale + 50) / 100 clamped to [1, 255], scale = 5000 / quality below 50, else 200 - 2 * quality.  A block that only
+ * pads the last MCU column or row is not transformed: its AC coefficients are 0 and its DC is that of the preceding block of its MCU.  The
+ * source pixels are only read.  The descriptor table is passed twice, as for fs_resize_bicubic_u8x_many (items_host is only checked).
+ * Asynchronous on the ctx stream, allocates nothing, can be captured into a hipGraph.  No value of the pixel data reaches an address; a
+ * descriptor the check refuses is skipped by the kernels too.
+ * Errors: -1 null argument / K outside [1, 65535] / a bad geometry / an image outside src_bytes or coef_bytes, -2 a pixel_bytes other than 3 or
+ * 4 (other than 1 with ncomp 1) or a quality outside [1, 100], -5 items_dev not 8-byte aligned, coef_base or an image's coef_offset / qt_offset
+ * not 16-byte aligned, the source of an image of 4-byte pixels not 4-byte aligned. */
+int fs_jpeg_forward_many(fs_ctx* ctx, const void* src_base, size_t src_bytes, const fs_jpegenc_item* items_host, const fs_jpegenc_item* items_dev,
+                         int K, void* coef_base, size_t coef_bytes);
+
+/* The fs_jpeg_info that fs_jpeg_parse would report for the file fs_jpeg_write writes of a width x height image of ncomp components with luma
+ * sampling hs x vs: tables 0 / 1 / 1, no restart interval, scan_offset 0.  Returns -1 for a geometry outside the handled set (dimensions
+ * 1..65535; ncomp 1 with 1x1, or ncomp 3 with 1x1, 2x1 or 2x2) or a null info. */
+int fs_jpeg_encode_plan(int width, int height, int ncomp, int hs, int vs, fs_jpeg_info* info);
+
+/* A size that surely holds the file fs_jpeg_write writes for this info, whatever the coefficients (0: a null or inconsistent info). */
+size_t fs_jpeg_write_bound(const fs_jpeg_info* info);
+
+/* Writes the complete baseline file of the coefficient buffer `coef` (coef_bytes >= info->coef_bytes, laid out as fs_jpeg_decode /
+ * fs_jpeg_forward_many leave it, the quantisation tables read at info->qt_offset) into out[0, cap) and its length into *n: SOI, the JFIF header
+ * (1.01, no units, density 1x1), one DQT segment per table, SOF0, one DHT segment per Annex K Huffman table (DC 0, AC 0, DC 1, AC 1; the first
+ * two for grayscale), SOS, the scan (zigzag order, DC prediction per component, ZRL / EOB, 0xFF bytes stuffed, the last byte padded with 1-bits),
+ * EOI.  Every write is checked against cap.  Returns 0, or -1 null argument / an info that fs_jpeg_encode_plan did not fill / coef_bytes too
+ * small / a quantisation entry outside [1, 255], -3 cap too small (nothing is written at or beyond out + cap), -4 a coefficient outside the
+ * baseline range (a DC difference beyond category 11, an AC value beyond category 10), -5 coef not 2-byte aligned. */
+int fs_jpeg_write(const fs_jpeg_info* info, const void* coef, size_t coef_bytes, void* out, size_t cap, size_t* n);
 
 #ifdef __cplusplus
 }

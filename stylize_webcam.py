@@ -7,6 +7,9 @@ image does not ship; without it the script can still filter a *directory of fram
     python stylize_webcam.py --model_path models/starry_final.ckpt --frames_dir in/ --output_dir out/
 (frames are read RGB with PIL and converted to the BGR order a cv2 capture would deliver, so the
 reference's channel handling -- BGR fed as is, output swapped -- is reproduced bit for bit).
+``--output_format jpg [--output_quality 95]`` writes <name>.jpg instead of <name>.png, encoded by the
+library (faststyle_amd/stream.py, jpeg=): the bytes PIL would write for the pixels of the .png at that
+quality, 4:2:0.
 """
 import os
 import sys
@@ -46,7 +49,16 @@ def run_frames_dir(args):
     st = None
     pend = collections.deque()
 
+    # --output_format jpg: the lanes encode.  The .png holds img_out[:, :, ::-1], the lane's frame with R and B swapped back -- which is the frame
+    # of a lane that does not swap, so the encoder is given that one (swap_rb=False) and its bytes go to disk as they are.
+    jpg = args.output_format == 'jpg'
+    kw = dict(swap_rb=False, jpeg=dict(quality=args.output_quality, subsampling=2)) if jpg else {}
+
     def save(n, img_out):
+        if jpg:
+            with open(os.path.join(args.output_dir, os.path.splitext(n)[0] + '.jpg'), 'wb') as f:
+                f.write(img_out)
+            return
         # cv2.imshow / VideoWriter interpret that array as BGR; save exactly what they would show
         Image.fromarray(img_out[:, :, ::-1]).save(os.path.join(args.output_dir, os.path.splitext(n)[0] + '.png'))
 
@@ -61,9 +73,10 @@ def run_frames_dir(args):
             shape = frame.shape[:2]
             print('Resolution is: {0} by {1}'.format(frame.shape[1], frame.shape[0]))
             if depth > 1:
-                st = stream.PipelinedStylizer(eng, variables, frame.shape[0], frame.shape[1], depth=depth, upsample_method=args.upsample_method)
+                st = stream.PipelinedStylizer(eng, variables, frame.shape[0], frame.shape[1], depth=depth, upsample_method=args.upsample_method,
+                                                 **kw)
             else:
-                st = stream.FrameStylizer(eng, variables, frame.shape[0], frame.shape[1], args.upsample_method)
+                st = stream.FrameStylizer(eng, variables, frame.shape[0], frame.shape[1], args.upsample_method, **kw)
         if depth > 1:
             if len(pend) >= depth:
                 save(pend.popleft(), st.fetch())

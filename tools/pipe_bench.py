@@ -1,6 +1,9 @@
 #!/usr/bin/env python
 """Throughput of the TFRecord input pipeline alone (decode threads + GPU resize + HBM shuffle queue) on
-synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native]
+synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode]
+"host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
+Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
+files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
 "host_native": the host half of the native JPEG path (fs_jpeg_parse + fs_jpeg_decode: the Huffman pass, coefficients dropped) and then the PIL
 host half, at the same thread count, one after the other over the same shards.
 "host": the host half only -- record framing, Example parsing and the JPEG decode pool, decoded images dropped (no engine, no GPU): what a rank's
@@ -17,10 +20,66 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from faststyle_amd import datapipe, engine, tfrecord  # noqa: E402
 
 
+def host_encode(n, th):
+    """-> dict of the two rates (frames/s); prints them."""
+    import ctypes
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    host = engine.JpegHost()
+    rng = np.random.default_rng(0)
+    base = rng.integers(0, 256, (90, 160, 3), dtype=np.uint8)
+    frames, coefs, sizes = [], [], []
+    for k in range(16):      # 16 distinct natural-ish frames (upsampled noise), reused
+        im = Image.fromarray(np.roll(base, 5 * k, axis=1)).resize((1280, 720), Image.BICUBIC)
+        buf = io.BytesIO()
+        im.save(buf, "JPEG", quality=95, subsampling=2)
+        data = buf.getvalue()
+        rc, info = host.jpeg_parse(data)
+        coef = np.zeros(int(info.coef_bytes), dtype=np.uint8)
+        assert rc == 0 and host.jpeg_decode(data, info, coef.ctypes.data, coef.nbytes) == 0
+        rc, plan = host.jpeg_encode_plan(1280, 720, 3, 2, 2)
+        assert rc == 0 and host.jpeg_write_bytes(plan, coef) == data          # the same file, byte for byte
+        frames.append(im)
+        coefs.append(coef)
+        sizes.append(len(data))
+    bound = host.jpeg_write_bound(plan)
+    import threading
+    local = threading.local()
+
+    def native(k):
+        if not hasattr(local, "out"):
+            local.out = ctypes.create_string_buffer(bound)
+        c = coefs[k % 16]
+        rc, m = host.jpeg_write(plan, c.ctypes.data, c.nbytes, ctypes.addressof(local.out), bound)
+        assert rc == 0
+        return len(ctypes.string_at(local.out, m))
+
+    def pil(k):
+        buf = io.BytesIO()
+        frames[k % 16].save(buf, "JPEG", quality=95, subsampling=2)
+        return len(buf.getvalue())
+
+    res = {"frames": n, "threads": th, "host_cores": os.cpu_count(), "size": [720, 1280], "quality": 95, "subsampling": "4:2:0",
+           "mean_file_bytes": float(np.mean(sizes))}
+    for name, fn in (("fs_jpeg_write", native), ("pil_save_jpeg", pil)):
+        with ThreadPoolExecutor(th) as ex:
+            list(ex.map(fn, range(2 * th)))       # warm-up
+            t0 = time.time()
+            total = sum(ex.map(fn, range(n)))
+            dt = time.time() - t0
+        res[name + "_frames_per_s"] = n / dt
+        print("host_encode: %.0f frames/s %s (%d 720p frames, %.1f KB/file, in %.2f s, %d threads, %d host cores)"
+              % (n / dt, name, n, total / n / 1e3, dt, th, os.cpu_count()))
+    return res
+
+
 def main():
     from PIL import Image
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     threads = int(sys.argv[2]) if len(sys.argv) > 2 else None
+    if len(sys.argv) > 3 and sys.argv[3] == "host_encode":
+        host_encode(n, threads or 4)
+        return
     rng = np.random.default_rng(0)
     d = tempfile.mkdtemp()
     base = rng.integers(0, 256, (60, 80, 3), dtype=np.uint8)
