@@ -20,6 +20,8 @@ FS_FLAG_UPSAMPLE_DECONV = 2
 FS_FLAG_BF16 = 4
 FS_FLAG_PARAMS_FROZEN = 8
 FS_TNET_WS_Z, FS_TNET_WS_A, FS_TNET_WS_B, FS_TNET_WS_MEAN, FS_TNET_WS_RSTD, FS_TNET_WS_H = 0, 1, 2, 3, 4, 5
+FS_TNET_BWS_Z, FS_TNET_BWS_A, FS_TNET_BWS_B, FS_TNET_BWS_MEAN, FS_TNET_BWS_RSTD, FS_TNET_BWS_H = 0, 1, 2, 3, 4, 5
+FS_TNET_BWS_ZFOLD, FS_TNET_BWS_WPK, FS_TNET_BWS_PLAN = 6, 7, 8
 FS_PAD_SAME, FS_PAD_VALID, FS_PAD_EXPLICIT = 0, 1, 2
 FS_SRC_PLAIN, FS_SRC_REFLECT, FS_SRC_DILATE2 = 0, 1, 2
 FS_PROFILE_FAMILIES = 23
@@ -117,6 +119,7 @@ PROTOTYPES = {
     "fs_gram_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t]),
     "fs_gram_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t]),
     "fs_tnet_ws_tensor": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_int * 4)]),
+    "fs_tnet_bf16_ws_tensor": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_int * 8), POINTER(c_int)]),
     "fs_perceptual_ws_tensor": (c_int, [c_int, c_int, c_int, POINTER(fs_loss_cfg), c_int, POINTER(c_size_t), POINTER(c_int * 4)]),
     "fs_perceptual_ws_input": (c_int, [c_int, c_int, c_int, POINTER(fs_loss_cfg), POINTER(c_size_t), POINTER(c_size_t)]),
     "fs_loss_sqdiff": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_float, c_void_p, c_void_p]),

@@ -33,6 +33,7 @@ struct fs_ctx {
     } fwd_recs[8];
     int fwd_rec_next = 0;
     fs::BTnetLayout* btnet;  // bf16 inference layout (allocated on first use)
+    unsigned btnet_epoch = 0;  // fs::tune_epoch() it was planned under
     hipStream_t side;      // second stream for the filter-gradient branch of fs_tnet_backward
     hipEvent_t ev[34];
     bool have_side;
@@ -329,7 +330,11 @@ int fs_tnet_forward(fs_ctx* ctx, const float* params, const float* x, int N, int
             return fail(-2, "fs_tnet_forward: FS_FLAG_BF16 is inference-only and covers the resize-conv models");
         if (!ctx->btnet) ctx->btnet = new fs::BTnetLayout();
         fs::BTnetLayout* B = ctx->btnet;
-        if (B->geo.N != N || B->geo.H != H || B->geo.W != W) fs::tnet_layout_bf16(N, H, W, B);
+        // (like the fp32 layout, the plans depend on the tuning knobs: re-planned after fs_debug_reload_env)
+        if (B->geo.N != N || B->geo.H != H || B->geo.W != W || ctx->btnet_epoch != fs::tune_epoch()) {
+            fs::tnet_layout_bf16(N, H, W, B);
+            ctx->btnet_epoch = fs::tune_epoch();
+        }
         if (ws_bytes < B->total_bytes)
             return fail(-3, "fs_tnet_forward: workspace too small (%zu < %zu bytes)", ws_bytes, B->total_bytes);
         const int rc = fs::tnet_forward_bf16(*B, params, x, y, ws, ctx->stream);
@@ -423,6 +428,44 @@ int fs_tnet_ws_tensor(int N, int H, int W, int flags, int unit, int what, size_t
     }
     delete L;
     return rc;
+}
+
+// inspection: where fs_tnet_forward(FS_FLAG_BF16) leaves every intermediate inside the caller's workspace, and how each unit's conv was planned
+int fs_tnet_bf16_ws_tensor(int N, int H, int W, int unit, int what, size_t* offset_bytes, int dims[8], int* elem_bytes) {
+    if (N < 1 || H < 41 || W < 41) return fail(-2, "fs_tnet_bf16_ws_tensor: need N>=1 and H,W>=41 (got %d,%d,%d)", N, H, W);
+    if (!dims || (what != FS_TNET_BWS_PLAN && (!offset_bytes || !elem_bytes))) return fail(-1, "fs_tnet_bf16_ws_tensor: null argument");
+    if (what < 0 || what > FS_TNET_BWS_PLAN) return fail(-2, "fs_tnet_bf16_ws_tensor: tensor %d out of range", what);
+    if (what == FS_TNET_BWS_H ? (unit < 0 || unit >= 5) : (unit < 0 || unit >= 16))
+        return fail(-2, "fs_tnet_bf16_ws_tensor: %s %d out of range", what == FS_TNET_BWS_H ? "residual block" : "unit", unit);
+    if (what == FS_TNET_BWS_ZFOLD && unit != 15) return fail(-2, "fs_tnet_bf16_ws_tensor: only unit 15 has a folded output (got %d)", unit);
+    fs::BTnetLayout* B = new fs::BTnetLayout();
+    fs::tnet_layout_bf16(N, H, W, B);
+    const fs::Unit& u = B->geo.u[what == FS_TNET_BWS_H ? 3 + 2 * unit + 1 : unit];
+    const fs::ConvBPlan& p = B->plan[what == FS_TNET_BWS_H ? 0 : unit];
+    if (what == FS_TNET_BWS_PLAN) {
+        if (elem_bytes) *elem_bytes = 0;
+        if (offset_bytes) *offset_bytes = 0;
+        dims[0] = p.bs, dims[1] = p.BN, dims[2] = p.WM, dims[3] = p.CC;
+        dims[4] = p.cout_pad, dims[5] = p.tiles_y, dims[6] = p.tiles_x, dims[7] = p.c4;
+    } else if (what == FS_TNET_BWS_H) {
+        *offset_bytes = B->h[unit], *elem_bytes = 2;
+        dims[0] = N, dims[1] = u.Hout, dims[2] = u.Wout, dims[3] = 64;
+    } else if (what == FS_TNET_BWS_ZFOLD) {
+        *offset_bytes = B->zfold, *elem_bytes = 2;
+        dims[0] = N, dims[1] = u.Hc, dims[2] = u.Wc, dims[3] = 16;
+    } else if (what == FS_TNET_BWS_WPK) {
+        *offset_bytes = B->wpk[unit], *elem_bytes = 2;
+        dims[0] = p.c4 ? u.K : u.K * u.KWx, dims[1] = p.cout_pad, dims[2] = p.c4 ? 48 : u.Cin, dims[3] = 1;
+    } else if (what == FS_TNET_BWS_Z) {
+        *offset_bytes = B->z[unit], *elem_bytes = unit == 15 ? 4 : 2;
+        dims[0] = N, dims[1] = u.Hout, dims[2] = u.Wout, dims[3] = u.Cout;
+    } else {
+        *offset_bytes = what == FS_TNET_BWS_A ? B->a[unit] : (what == FS_TNET_BWS_B ? B->b[unit] : (what == FS_TNET_BWS_MEAN ? B->mean[unit] : B->rstd[unit]));
+        *elem_bytes = 4;
+        dims[0] = N, dims[1] = u.Cout, dims[2] = dims[3] = 1;
+    }
+    delete B;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------ VGG / losses

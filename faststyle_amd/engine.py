@@ -525,6 +525,31 @@ class Engine(JpegHost):
         shape = tuple(dims) if what in (L.FS_TNET_WS_Z, L.FS_TNET_WS_H) else (dims[0], dims[1])
         return self.mem.view(self._tnet_ws[key][0], off.value, shape)
 
+    def tnet_bf16_plan(self, N, H, W, unit):
+        """How unit 0..15 of the bf16 inference path is planned under the library's tuning knobs of the moment (FS_TNET_BWS_PLAN)."""
+        dims = (ctypes.c_int * 8)()
+        L.check(self.lib, self.lib.fs_tnet_bf16_ws_tensor(N, H, W, unit, L.FS_TNET_BWS_PLAN, None, ctypes.byref(dims), None), "fs_tnet_bf16_ws_tensor")
+        return dict(zip(("bs", "BN", "WM", "CC", "cout_pad", "tiles_y", "tiles_x", "c4"), (int(v) for v in dims)))
+
+    def tnet_bf16_saved(self, workspace, N, H, W, unit, what):
+        """Host copy of a tensor tnet_forward(bf16=True, workspace=workspace) left in `workspace`, a new_tnet_workspace(N, H, W, bf16=True) pair:
+        numpy uint16 (bfloat16 bit patterns) or float32, whichever the path stores (fs_tnet_bf16_ws_tensor)."""
+        off, dims, esz = ctypes.c_size_t(), (ctypes.c_int * 8)(), ctypes.c_int()
+        L.check(self.lib, self.lib.fs_tnet_bf16_ws_tensor(N, H, W, unit, what, ctypes.byref(off), ctypes.byref(dims), ctypes.byref(esz)),
+                "fs_tnet_bf16_ws_tensor")
+        ws, nbytes = workspace
+        if nbytes != self._tnet_key(N, H, W, True)[4]:
+            raise L.FaststyleError("not a bf16 transform-net workspace of shape %s" % ((N, H, W),))
+        shape = tuple(int(d) for d in dims[:4])
+        if what in (L.FS_TNET_BWS_A, L.FS_TNET_BWS_B, L.FS_TNET_BWS_MEAN, L.FS_TNET_BWS_RSTD):
+            shape = shape[:2]
+        elif what == L.FS_TNET_BWS_WPK:
+            shape = shape[:3]
+        n = int(np.prod(shape))
+        assert off.value % 4 == 0 and off.value + n * esz.value <= nbytes
+        raw = np.ascontiguousarray(self.mem.to_numpy(self.mem.view(ws, off.value // 4, ((n * esz.value + 3) // 4,))))
+        return raw.view(np.uint16 if esz.value == 2 else np.float32)[:n].reshape(shape).copy()
+
     def vgg_saved(self, N, H, W, cfg, layer_name):
         """View of the post-ReLU activations fs_perceptual_loss left in its (cached) workspace: [NB,h,w,c], the first N
         samples are the net outputs, the next N (up to the last content layer) the content batch."""

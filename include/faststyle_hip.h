@@ -187,6 +187,24 @@ int fs_adam_tf_step(fs_ctx* ctx, float* p, const float* g, float* m, float* v, s
 #define FS_TNET_WS_H 5
 int fs_tnet_ws_tensor(int N, int H, int W, int flags, int unit, int what, size_t* offset_floats, int dims[4]);
 int fs_perceptual_ws_tensor(int N, int H, int W, const fs_loss_cfg* cfg, int layer, size_t* offset_floats, int dims[4]);
+/* fs_tnet_bf16_ws_tensor: after fs_tnet_forward(..., FS_FLAG_BF16), which overwrites nothing it wrote.  Offsets are in BYTES from the start of
+ *   `ws`; *elem_bytes is 2 (bfloat16, as unsigned short) or 4 (float).  unit as above.  what:
+ *   FS_TNET_BWS_Z the unit's stored raw conv output [N,Ho,Wo,C], bf16 (the resize-convs in their pixel-shuffled [N,2H,2W,C] order; unit 15: the
+ *   folded fp32 [N,Ho,Wo,3]); _A / _B / _MEAN / _RSTD the fp32 per-sample constants [N,C]; FS_TNET_BWS_H (unit = k in 0..4) the bf16 output of
+ *   residual block k; FS_TNET_BWS_ZFOLD (unit 15) the 16 virtual channels of the kw-folded output layer, bf16 [N,Ho,Wo+4,16];
+ *   FS_TNET_BWS_WPK the unit's packed bf16 filter [taps][cout_pad][Cin] (image layer: [9][cout_pad][48]);
+ *   FS_TNET_BWS_PLAN no tensor: dims[0..7] = how the unit's conv is planned under the tuning knobs of the moment -- bs (instance of the streaming
+ *   kernel, 0: the kernels of fs_bf16.hip), BN, WM, CC, cout_pad, tiles_y, tiles_x, c4 (offset_bytes / elem_bytes may be null). */
+#define FS_TNET_BWS_Z 0
+#define FS_TNET_BWS_A 1
+#define FS_TNET_BWS_B 2
+#define FS_TNET_BWS_MEAN 3
+#define FS_TNET_BWS_RSTD 4
+#define FS_TNET_BWS_H 5
+#define FS_TNET_BWS_ZFOLD 6
+#define FS_TNET_BWS_WPK 7
+#define FS_TNET_BWS_PLAN 8
+int fs_tnet_bf16_ws_tensor(int N, int H, int W, int unit, int what, size_t* offset_bytes, int dims[8], int* elem_bytes);
 /* fs_perceptual_ws_input: where fs_perceptual_loss stages y and content ([y ; content] is ONE 2N batch through the shared VGG layers).  Passing
  *   y == ws + *y_offset_floats and / or content == ws + *content_offset_floats skips the corresponding device copy: the transform net can write
  *   its output, and the input pipeline its batch, straight into the workspace (train.py:250-256 without the sess.run round trip).

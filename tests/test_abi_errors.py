@@ -45,6 +45,26 @@ def test_tnet_entry_points_reject_bad_arguments(eng):
     assert lib.fs_tnet_ws_tensor(1, 64, 64, 0, 16, L.FS_TNET_WS_Z, ctypes.byref(off), ctypes.byref(dims)) == -2 and "16" in err(e)
     assert lib.fs_tnet_ws_tensor(1, 64, 64, 0, 5, L.FS_TNET_WS_H, ctypes.byref(off), ctypes.byref(dims)) == -2
     assert lib.fs_tnet_ws_tensor(1, 64, 64, L.FS_FLAG_BF16, 0, L.FS_TNET_WS_Z, ctypes.byref(off), ctypes.byref(dims)) == -2
+    # ... and its bf16 counterpart
+    d8, esz = (ctypes.c_int * 8)(), ctypes.c_int()
+    bws = lambda n, h, w, unit, what, o=ctypes.byref(off), d=ctypes.byref(d8), e=ctypes.byref(esz): lib.fs_tnet_bf16_ws_tensor(n, h, w, unit, what, o, d, e)
+    assert bws(1, 40, 64, 0, L.FS_TNET_BWS_Z) == -2 and "41" in err(e) and "40" in err(e)
+    assert bws(0, 64, 64, 0, L.FS_TNET_BWS_Z) == -2
+    assert bws(1, 64, 64, 16, L.FS_TNET_BWS_Z) == -2 and "16" in err(e)
+    assert bws(1, 64, 64, -1, L.FS_TNET_BWS_WPK) == -2
+    assert bws(1, 64, 64, 5, L.FS_TNET_BWS_H) == -2 and "residual block 5" in err(e)
+    assert bws(1, 64, 64, 14, L.FS_TNET_BWS_ZFOLD) == -2 and "15" in err(e)
+    assert bws(1, 64, 64, 0, L.FS_TNET_BWS_PLAN + 1) == -2 and bws(1, 64, 64, 0, -1) == -2
+    assert bws(1, 64, 64, 0, L.FS_TNET_BWS_Z, o=None) == -1 and "null" in err(e)
+    assert bws(1, 64, 64, 0, L.FS_TNET_BWS_Z, e=None) == -1 and bws(1, 64, 64, 0, L.FS_TNET_BWS_PLAN, d=None) == -1
+    assert bws(1, 64, 64, 16, L.FS_TNET_BWS_PLAN, o=None, e=None) == -2
+    # what it accepts: every tensor lies inside the workspace fs_tnet_workspace_bytes sizes; the PLAN query needs neither offset nor element size
+    total = lib.fs_tnet_workspace_bytes(1, 64, 64, L.FS_FLAG_BF16)
+    for unit, what in [(u, w) for u in range(16) for w in (L.FS_TNET_BWS_Z, L.FS_TNET_BWS_A, L.FS_TNET_BWS_B, L.FS_TNET_BWS_MEAN, L.FS_TNET_BWS_RSTD,
+                                                            L.FS_TNET_BWS_WPK)] + [(k, L.FS_TNET_BWS_H) for k in range(5)] + [(15, L.FS_TNET_BWS_ZFOLD)]:
+        assert bws(1, 64, 64, unit, what) == 0 and esz.value in (2, 4) and off.value % 256 == 0
+        assert off.value + int(np.prod(d8[:4])) * esz.value <= total, (unit, what)
+    assert bws(1, 64, 64, 3, L.FS_TNET_BWS_PLAN, o=None, e=None) == 0 and d8[0] == 3 and d8[1] == 64 and d8[4] == 64
     name = ctypes.c_char_p()
     assert lib.fs_tnet_param_info(48, ctypes.byref(name), None, None, None) == -1 and "48" in err(e)
     assert lib.fs_tnet_invalidate(None) == -1
