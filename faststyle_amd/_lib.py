@@ -25,6 +25,8 @@ FS_TNET_BWS_ZFOLD, FS_TNET_BWS_WPK, FS_TNET_BWS_PLAN = 6, 7, 8
 FS_PAD_SAME, FS_PAD_VALID, FS_PAD_EXPLICIT = 0, 1, 2
 FS_SRC_PLAIN, FS_SRC_REFLECT, FS_SRC_DILATE2 = 0, 1, 2
 FS_PROFILE_FAMILIES = 23
+FS_CV_INTER_CUBIC, FS_CV_INTER_AREA = 2, 3                                       # cv2.INTER_CUBIC, cv2.INTER_AREA
+FS_CVRESIZE_PATH_CUBIC, FS_CVRESIZE_PATH_AREA_FAST, FS_CVRESIZE_PATH_AREA = 0, 1, 2
 
 
 def profile_family_names(lib):
@@ -70,6 +72,14 @@ class fs_jpeg_info(Structure):
                 ("blocks_x", ctypes.c_int32 * 3), ("blocks_y", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32),
                 ("scan_offset", c_uint64), ("plane_offset", c_uint64 * 3), ("qt_offset", c_uint64), ("coef_count", c_uint64),
                 ("coef_bytes", c_uint64), ("rgb_bytes", c_uint64)]
+
+
+class fs_cvresize_info(Structure):
+    """include/faststyle_io.h: what fs_cvresize_plan reports."""
+    _fields_ = [("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32), ("dst_h", ctypes.c_int32), ("dst_w", ctypes.c_int32),
+                ("interpolation", ctypes.c_int32), ("path", ctypes.c_int32), ("factor_x", ctypes.c_int32), ("factor_y", ctypes.c_int32),
+                ("x_taps", ctypes.c_int32), ("y_taps", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2),
+                ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("x_offset", c_uint64), ("y_offset", c_uint64), ("table_bytes", c_uint64)]
 
 
 class fs_wgrad_desc(Structure):
@@ -172,6 +182,9 @@ PROTOTYPES = {
     "fs_jpeg_encode_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_jpeg_info)]),
     "fs_jpeg_write_bound": (c_size_t, [POINTER(fs_jpeg_info)]),
     "fs_jpeg_write": (c_int, [POINTER(fs_jpeg_info), c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_size_t)]),
+    "fs_cvresize_plan": (c_int, [c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, POINTER(fs_cvresize_info)]),
+    "fs_cvresize_tables": (c_int, [POINTER(fs_cvresize_info), c_void_p, c_size_t]),
+    "fs_cvresize_u8": (c_int, [c_void_p, POINTER(fs_cvresize_info), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "fs_u8_to_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "fs_f32_to_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
 }

@@ -82,4 +82,10 @@ def stylize_webcam_parser():
         ('--output_format', dict(choices=['png', 'jpg'], default='png', help="(addition) file type of the --frames_dir results: 'png' through PIL, "
                                                                             "'jpg' encoded by the library (forward DCT on the GPU, 4:2:0)")),
         ('--output_quality', dict(default=95, type=int, help='(addition) JPEG quality 1..100 of --output_format jpg')),
+        ('--frame_size', dict(nargs=2, type=int, default=None, metavar=('W', 'H'),
+                              help="(addition) resize every --frames_dir frame to W x H on the device with cv2.resize's resampling (area when "
+                                   "shrinking, cubic otherwise); not together with --resolution, which keeps its PIL resize")),
+        ('--input_decode', dict(choices=['pil', 'native'], default='pil',
+                                help="(addition) decoder of the --frames_dir frames: 'pil', or 'native' -- baseline .jpg / .jpeg files go in as "
+                                     "bytes (Huffman pass on host threads, reconstruction on the GPU); other files still go through PIL")),
     ])

@@ -181,6 +181,18 @@ int fs_jpeg_forward_many(fs_ctx* ctx, const void* src_base, size_t src_bytes, co
                                          static_cast<unsigned char*>(coef_base), coef_bytes, ctx->stream);
     return rc ? fail(rc, "fs_jpeg_forward_many: launch failed (%d)", rc) : 0;
 }
+int fs_cvresize_u8(fs_ctx* ctx, const fs_cvresize_info* plan, const void* tables_dev, const unsigned char* src, int src_pixel_bytes, int N, int swap_rb,
+                   unsigned char* dst) {
+    if (!ctx || !plan || !src || !dst) return fail(-1, "fs_cvresize_u8: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_cvresize_u8: N must be in [1, 65535], got %d", N);
+    if (src_pixel_bytes != 3 && src_pixel_bytes != 4) return fail(-2, "fs_cvresize_u8: src_pixel_bytes must be 3 (RGB) or 4 (RGBX), got %d", src_pixel_bytes);
+    if (!fs::cvresize_plan_ok(*plan)) return fail(-1, "fs_cvresize_u8: the plan (%dx%d -> %dx%d) was not filled by fs_cvresize_plan", plan->src_h, plan->src_w, plan->dst_h, plan->dst_w);
+    if (plan->table_bytes && !tables_dev) return fail(-1, "fs_cvresize_u8: null tables for a plan with %llu table bytes", (unsigned long long)plan->table_bytes);
+    if (plan->table_bytes && ((uintptr_t)tables_dev & 15)) return fail(-5, "fs_cvresize_u8: tables_dev must be 16-byte aligned");
+    if (src_pixel_bytes == 4 && ((uintptr_t)src & 3)) return fail(-5, "fs_cvresize_u8: a source of 4-byte pixels must be 4-byte aligned");
+    const int rc = fs::cvresize_u8(*plan, static_cast<const unsigned char*>(tables_dev), src, src_pixel_bytes, N, swap_rb ? 1 : 0, dst, ctx->stream);
+    return rc ? fail(rc, "fs_cvresize_u8: launch failed (%d)", rc) : 0;
+}
 int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
                   const int32_t* move_dst, int M, float* batch_out) {
     if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");

@@ -17,6 +17,7 @@ typedef unsigned int fs_u32x4 __attribute__((ext_vector_type(4)));   // payload 
 struct fs_resize_item;   // include/faststyle_io.h
 struct fs_jpeg_item;
 struct fs_jpegenc_item;
+struct fs_cvresize_info;
 
 namespace fs {
 
@@ -676,6 +677,10 @@ __host__ __device__ int jpegenc_item_check(const ::fs_jpegenc_item& it, unsigned
 unsigned long long jpegenc_item_blocks(const ::fs_jpegenc_item& it);
 int jpeg_forward_many(const unsigned char* src_base, size_t src_bytes, const ::fs_jpegenc_item* items_dev, int K, unsigned long long max_blocks,
                       unsigned char* coef_base, size_t coef_bytes, hipStream_t s);
+// cv2.resize on u8 images (fs_cvresize.hip): whether a plan is what fs_cvresize_plan fills, and the launch of its path (pixel_bytes 3 or 4)
+bool cvresize_plan_ok(const ::fs_cvresize_info& plan);
+int cvresize_u8(const ::fs_cvresize_info& plan, const unsigned char* tables, const unsigned char* src, int pixel_bytes, int N, int swap_rb,
+                unsigned char* dst, hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);
 // ... with the per-sample sums taken from records [N][T][C][2] (rec == nullptr: computed here into `scratch`), reduced in the apply kernel's

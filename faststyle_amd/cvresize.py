@@ -109,9 +109,7 @@ def resize_area_u8(img, fx, fy):
             else:
                 out[:hfast, :wfast] = np.clip(cv_round(blk.astype(np.float32) * np.float32(1.0 / area)), 0, 255).astype(np.uint8)
         for dy in range(Hd):                                            # edge cells: the mean of the pixels that exist (0 when none)
-            for dx in range(Wd):
-                if dy < hfast and dx < wfast:
-                    continue
+            for dx in range(wfast if dy < hfast else 0, Wd):            # (only dy >= hfast or dx >= wfast)
                 y0, x0 = dy * isy, dx * isx
                 cell = src[y0:min(y0 + isy, H), x0:min(x0 + isx, W)]
                 if cell.size == 0:

@@ -157,7 +157,56 @@ class JpegHost(object):
         return out[:n].tobytes()
 
 
-class Engine(JpegHost):
+class CvResizePlan(object):
+    """One planned cv2.resize (fs_cvresize_plan): ``info`` the library's fs_cvresize_info, ``tables`` its per-axis tables on the host (uint8),
+    and -- once an engine has run it -- the device copy of the tables, uploaded once per plan."""
+
+    def __init__(self, info, tables):
+        self.info = info
+        self.tables = tables
+        self.tables_dev = None
+        self.src_shape = (int(info.src_h), int(info.src_w))
+        self.dst_shape = (int(info.dst_h), int(info.dst_w))
+        self.path = int(info.path)
+
+    def axis_table(self, axis):
+        """The entries of one axis table ('x' or 'y') as cvresize.py states them: cubic -> (idx [n_dst,4], w [n_dst,4]); area -> the list of
+        (dst index, src index, float32 weight) of _area_tab; the area fast path has none (None)."""
+        i = self.info
+        n_dst, off, taps = (i.dst_w, i.x_offset, i.x_taps) if axis == "x" else (i.dst_h, i.y_offset, i.y_taps)
+        if self.path == L.FS_CVRESIZE_PATH_AREA_FAST:
+            return None
+        if self.path == L.FS_CVRESIZE_PATH_CUBIC:
+            t = self.tables[off:off + n_dst * 32].view("<i4").reshape(n_dst, 8)
+            return t[:, :4].astype(np.int64), t[:, 4:].astype(np.int64)
+        ofs = self.tables[off:off + (n_dst + 1) * 4].view("<i4")
+        start = off + ((n_dst + 1) * 4 + 7) // 8 * 8
+        rows = self.tables[start:start + taps * 8].view(np.dtype([("si", "<i4"), ("alpha", "<f4")]))
+        return [(d, int(rows["si"][k]), rows["alpha"][k]) for d in range(n_dst) for k in range(int(ofs[d]), int(ofs[d + 1]))]
+
+
+class CvResizeHost(object):
+    """The host calls of the cv2.resize kernels (csrc/fs_cvresize.hip): plan and tables.  They need the library and no device."""
+
+    def __init__(self, lib=None):
+        self.lib = lib if lib is not None else L.load()
+
+    def cvresize_plan(self, H, W, fx, fy, interpolation=None):
+        """fs_cvresize_plan + fs_cvresize_tables of cv2.resize(img [H,W,3] u8, None, fx=fx, fy=fy, interpolation): a CvResizePlan.
+        interpolation: L.FS_CV_INTER_CUBIC / L.FS_CV_INTER_AREA; None: the dispatch of the reference's utils.imresize on two axes -- area when
+        both axes shrink or stay and at least one shrinks, otherwise cubic.  A refused request raises FaststyleError."""
+        fx, fy = float(fx), float(fy)
+        if interpolation is None:
+            interpolation = L.FS_CV_INTER_AREA if (fx <= 1.0 and fy <= 1.0 and (fx < 1.0 or fy < 1.0)) else L.FS_CV_INTER_CUBIC
+        info = L.fs_cvresize_info()
+        L.check(self.lib, self.lib.fs_cvresize_plan(int(H), int(W), fx, fy, int(interpolation), ctypes.byref(info)), "fs_cvresize_plan")
+        tables = np.zeros(int(info.table_bytes), np.uint8)
+        L.check(self.lib, self.lib.fs_cvresize_tables(ctypes.byref(info), ctypes.c_void_p(tables.ctypes.data) if tables.size else None,
+                                                      tables.nbytes), "fs_cvresize_tables")
+        return CvResizePlan(info, tables)
+
+
+class Engine(JpegHost, CvResizeHost):
     # Workspaces are cached per shape (a backward must find the workspace its forward filled; a captured hipGraph replays raw
     # pointers into its own).  The cache is bounded by BYTES, least recently used first: stylizing a directory of mixed
     # resolutions must not pile up one multi-GB workspace per size.  Entries a live hipGraph replays into are pinned by
@@ -775,6 +824,33 @@ class Engine(JpegHost):
                 "fs_jpeg_forward_many")
         self._keep = [keep, items]
         return coef
+
+    # ------------------------------------------------------------------ cv2.resize on u8 images (csrc/fs_cvresize.hip)
+    def cvresize_u8(self, src_dev, plan, out_dev, swap_rb=False):
+        """fs_cvresize_u8: src_dev device uint8 [H,W,3|4] or [N,H,W,3|4] (4: RGBX, the fourth byte never read) -> out_dev device uint8
+        [Hd,Wd,3] / [N,Hd,Wd,3], the result of cvresize.resize_cubic_u8 / resize_area_u8 for the plan's (fx, fy); swap_rb: R and B exchanged.
+        The plan's tables go to the device on its first use."""
+        self._sync_stream()
+        shape = tuple(int(d) for d in src_dev.shape)
+        N = shape[0] if len(shape) == 4 else 1
+        pb = shape[-1]
+        if shape[-3:-1] != plan.src_shape or int(np.prod(out_dev.shape)) != N * plan.dst_shape[0] * plan.dst_shape[1] * 3:
+            raise L.FaststyleError("cvresize_u8: source %s / destination %s do not fit the plan %s -> %s" % (shape, tuple(out_dev.shape), plan.src_shape,
+                                                                                                          plan.dst_shape))
+        if plan.tables_dev is None and plan.tables.size:
+            plan.tables_dev = self.mem.upload_u8(plan.tables)
+        tab = self.mem.ptr_u8(plan.tables_dev) if plan.tables_dev is not None else None
+        L.check(self.lib, self.lib.fs_cvresize_u8(self.ctx, ctypes.byref(plan.info), tab, self.mem.ptr_u8(src_dev), pb, N, 1 if swap_rb else 0,
+                                                  self.mem.ptr_u8(out_dev)), "fs_cvresize_u8")
+        return out_dev
+
+    def cvresize(self, img, fx, fy, interpolation=None, swap_rb=False):
+        """Host uint8 [H,W,3] -> host uint8 [Hd,Wd,3]: upload, cvresize_u8, download (utils.imresize with an engine)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        plan = self.cvresize_plan(img.shape[0], img.shape[1], fx, fy, interpolation)
+        out = self.mem.upload_u8(np.zeros(plan.dst_shape + (3,), np.uint8))
+        self.cvresize_u8(self.mem.upload_u8(img), plan, out, swap_rb=swap_rb)
+        return np.array(self.mem.to_numpy(out), copy=True)
 
     def synth_uniform(self, out, seed, rank, batch_index):
         """Uniform [0,255) float32 values into ``out``: Philox4x32-10 keyed by seed, counter (element block, batch_index, rank) (fs_synth_uniform)."""

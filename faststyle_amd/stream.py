@@ -12,6 +12,14 @@ With ``jpeg=dict(quality=95, subsampling=2)`` a stylizer returns the frame as th
 file instead of the u8 array (the bytes PIL writes for that array, quality and subsampling): the device
 pass ends with fs_jpeg_forward_many on the u8 frame, inside the graph, the int16 coefficients come down
 instead of the pixels, and fs_jpeg_write entropy-codes them on host threads (csrc/fs_jpegenc.hip).
+
+With ``source=dict(height=Hs, width=Ws, interpolation=None, swap_rb=False, jpeg=None)`` the input side moves onto the device as well: pixel
+frames arrive at the source size and the device pass begins with cv2.resize's resampling to the stylizer's size (fs_cvresize_u8, csrc/
+fs_cvresize.hip; interpolation None: area when shrinking, cubic otherwise; swap_rb: R and B exchanged on the way, a cv2 capture's order); with
+``jpeg=dict(width=, height=, components=, sampling=(hs, vs))`` (jpeg_source() builds the dict from a first file) a frame may also arrive as the
+bytes of a baseline JPEG file of that geometry: fs_jpeg_parse / fs_jpeg_decode run on the host into a pinned coefficient buffer, and
+fs_jpeg_reconstruct_many, the resize, the net and the optional encoder run in the captured graph.  A file that does not fit raises
+FrameNotTaken before anything is enqueued; the caller decodes it with PIL and hands the pixels to the same stylizer.
 """
 import ctypes
 
@@ -20,11 +28,26 @@ import numpy as np
 from . import _lib as L
 
 
+class FrameNotTaken(L.FaststyleError):
+    """A frame given as JPEG bytes that the native decoder does not take (another geometry than the stylizer's source, a file outside the
+    handled set, a scan that does not decode): nothing was enqueued; decode it otherwise and pass the pixels."""
+
+
+def jpeg_source(eng, data, **kw):
+    """The ``source=`` dict of a stylizer fed with JPEG files like ``data`` (the bytes of a first file): its size and JPEG geometry, plus
+    whatever ``kw`` adds (interpolation=, swap_rb=).  None for a file fs_jpeg_parse does not take."""
+    rc, info = eng.jpeg_parse(data)
+    if rc != 0:
+        return None
+    return dict(kw, height=int(info.height), width=int(info.width),
+                jpeg=dict(width=int(info.width), height=int(info.height), components=int(info.ncomp), sampling=(int(info.hs[0]), int(info.vs[0]))))
+
+
 class FrameStylizer(object):
     KEEP_GRAPH = False     # tests: keep the captured hipGraph_t so that its node types can be inspected
 
     def __init__(self, eng, variables, height, width, upsample_method="resize", batch=1, swap_rb=True, use_graph=True,
-                 bf16=False, jpeg=None, jpeg_threads=4):
+                 bf16=False, jpeg=None, jpeg_threads=4, source=None):
         self.eng = eng
         self.variables = variables
         self.method = upsample_method
@@ -48,6 +71,89 @@ class FrameStylizer(object):
         self._pool = None
         if jpeg is not None:
             self._jpeg_setup(dict(jpeg), int(jpeg_threads))
+        self.source = None
+        self.in_shape = self.shape       # the pixel frames __call__ takes, and the device buffer they are uploaded into
+        self._pix_dst = self._in_u8
+        self._src_plan = None
+        self._src_jpeg = None
+        self._graph_jpeg = None
+        self._src_host = None
+        if source is not None:
+            self._source_setup(dict(source))
+
+    def _source_setup(self, opt):
+        """The input side's fixed parts: the resize plan from the source size (none when nothing is to be resized or swapped), the device buffer
+        of source pixels, and for JPEG frames the descriptor table, the device coefficient buffer and the decoded RGBX pixels."""
+        e, mem = self.eng, self.eng.mem
+        B, H, W, _ = self.shape
+        try:
+            Hs, Ws = int(opt.pop("height")), int(opt.pop("width"))
+        except KeyError:
+            raise L.FaststyleError("source needs height and width, got %r" % opt)
+        interpolation, swap, jp = opt.pop("interpolation", None), bool(opt.pop("swap_rb", False)), opt.pop("jpeg", None)
+        if opt:
+            raise L.FaststyleError("source takes height, width, interpolation, swap_rb and jpeg, got also %r" % opt)
+        self.source = dict(height=Hs, width=Ws, interpolation=interpolation, swap_rb=swap, jpeg=None if jp is None else dict(jp))
+        self.in_shape = (B, Hs, Ws, 3)
+        self._src_swap = swap
+        if (Hs, Ws) != (H, W) or swap:
+            self._src_plan = e.cvresize_plan(Hs, Ws, W / float(Ws), H / float(Hs), interpolation)
+            if self._src_plan.dst_shape != (H, W):
+                raise L.FaststyleError("source %dx%d does not resize to %dx%d but to %dx%d" % ((Hs, Ws, H, W) + self._src_plan.dst_shape))
+            self._pix_dst = mem.upload_u8(np.zeros(self.in_shape, np.uint8))
+        if jp is None:
+            return
+        jp = dict(jp)
+        try:
+            geom = (int(jp.pop("width")), int(jp.pop("height")), int(jp.pop("components")), tuple(int(v) for v in jp.pop("sampling")))
+        except (KeyError, TypeError):
+            raise L.FaststyleError("source jpeg needs width, height, components and sampling=(hs, vs), got %r" % self.source["jpeg"])
+        if jp or geom[:2] != (Ws, Hs):
+            raise L.FaststyleError("source jpeg %r does not describe the %dx%d source" % (self.source["jpeg"], Ws, Hs))
+        rc, info = e.jpeg_encode_plan(geom[0], geom[1], geom[2], *geom[3])      # (the fs_jpeg_info of this geometry: the buffer sizes)
+        L.check(e.lib, rc, "fs_jpeg_encode_plan")
+        self._src_jpeg = geom
+        self._sstride = (int(info.coef_bytes) + 15) & ~15
+        pb = 4 if self._src_plan is not None else 3              # RGBX for the resize to read; nothing to resize: straight into the net's input
+        self._sitems = np.zeros(B, dtype=e.JPEG_ITEM)
+        for b in range(B):
+            self._sitems[b] = e.jpeg_item(info, b * self._sstride, b * Hs * Ws * pb, pb)
+        self._sitems_dev = mem.upload_u8(self._sitems.view(np.uint8).reshape(-1))
+        self._src_coef = mem.upload_u8(np.zeros(B * self._sstride, np.uint8))
+        self._src_rgbx = mem.upload_u8(np.zeros((B, Hs, Ws, 4), np.uint8)) if pb == 4 else None
+        self._src_host = self.new_coef_staging()
+
+    def new_coef_staging(self):
+        """A host buffer for the decoded coefficients of one batch of JPEG frames (pinned on the GPU engine): (numpy view, the buffer)."""
+        mem = self.eng.mem
+        n = self.shape[0] * self._sstride
+        if hasattr(mem, "torch"):
+            t = mem.torch.zeros(n, dtype=mem.torch.uint8, pin_memory=True)
+            return t.numpy(), t
+        a = np.zeros(n, np.uint8)
+        return a, a
+
+    def decode_frames(self, files, staging):
+        """The host half of JPEG frames: fs_jpeg_parse + fs_jpeg_decode of each file into its slot of ``staging`` (new_coef_staging's).  Raises
+        FrameNotTaken for a file of another geometry, one the parser does not take, or one that does not decode.  Touches no device state and
+        holds no interpreter lock inside fs_jpeg_decode: decode threads call it ahead of the device."""
+        e = self.eng
+        if self._src_jpeg is None:
+            raise FrameNotTaken("this stylizer was built without source jpeg=: it takes pixel frames only")
+        if len(files) != self.shape[0]:
+            raise L.FaststyleError("%d JPEG frames, stylizer was built for a batch of %d" % (len(files), self.shape[0]))
+        view = staging[0]
+        for b, data in enumerate(files):
+            rc, info = e.jpeg_parse(data)
+            if rc != 0:
+                raise FrameNotTaken("fs_jpeg_parse answers %d for this frame" % rc)
+            geom = (int(info.width), int(info.height), int(info.ncomp), (int(info.hs[0]), int(info.vs[0])))
+            if geom != self._src_jpeg:
+                raise FrameNotTaken("frame geometry %r, stylizer was built for %r" % (geom, self._src_jpeg))
+            rc = e.jpeg_decode(data, info, view.ctypes.data + b * self._sstride, self._sstride)
+            if rc != 0:
+                raise FrameNotTaken("fs_jpeg_decode answers %d for this frame" % rc)
+        return staging
 
     # luma sampling factors of PIL's ``subsampling`` values
     SUBSAMPLING = {0: (1, 1), 1: (2, 1), 2: (2, 2), "4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
@@ -88,8 +194,16 @@ class FrameStylizer(object):
             return [self._write_one(coef_addr, b) for b in range(B)]
         return list(pool.map(lambda b: self._write_one(coef_addr, b), range(B)))
 
-    def _device_pass(self):
+    def _device_pass(self, jpeg_in=False):
         e = self.eng
+        if jpeg_in:                                          # the coefficients of the frame(s) are in self._src_coef
+            if self._src_plan is not None:
+                e.jpeg_reconstruct_many(self._src_coef, self._sitems, self._src_rgbx, items_dev=(self._sitems_dev, 0))
+                e.cvresize_u8(self._src_rgbx, self._src_plan, self._in_u8, swap_rb=self._src_swap)
+            else:
+                e.jpeg_reconstruct_many(self._src_coef, self._sitems, self._in_u8, items_dev=(self._sitems_dev, 0))
+        elif self._src_plan is not None:                     # source pixels are in self._pix_dst
+            e.cvresize_u8(self._pix_dst, self._src_plan, self._in_u8, swap_rb=self._src_swap)
         e.u8_to_f32(self._in_u8, self._in_f32)
         self._y = e.tnet_forward(self.variables, self._in_f32, upsample_method=self.method, bf16=self.bf16, frozen=True,   # one checkpoint, many frames
                                  workspace=self._ws)
@@ -97,25 +211,52 @@ class FrameStylizer(object):
         if self.jpeg is not None:
             e.jpeg_forward_many(self._out_u8, self._jitems, self._coef, items_dev=(self._jitems_dev, 0))
 
-    def _capture(self):
+    def _capture(self, jpeg_in=False):
+        """Capture the device pass of pixel frames (self._graph) or of JPEG frames (self._graph_jpeg).  The warm-up runs the pass once on
+        whatever the input buffers hold, and the JPEG pass consumes its coefficients: callers capture BEFORE they upload a JPEG frame."""
         torch = self.eng.mem.torch
         self.eng.invalidate_frozen()                       # the warm-up below rebuilds the filters in self._ws whatever the library remembers
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up outside capture (one-time initialisation)
-            self._device_pass()
+            self._device_pass(jpeg_in)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph(keep_graph=True) if self.KEEP_GRAPH else torch.cuda.CUDAGraph()
         # thread_local: calls made by OTHER threads (e.g. the RCCL watchdog of a data-parallel run) must not
         # invalidate this thread's capture
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._device_pass()
-        self._graph = g                                    # (replays raw pointers into self._ws, which lives as long as this object)
+            self._device_pass(jpeg_in)
+        if jpeg_in:
+            self._graph_jpeg = g
+        else:
+            self._graph = g                                # (replays raw pointers into self._ws, which lives as long as this object)
+
+    def _run(self, jpeg_in=False):
+        """The device pass of the frame(s) just uploaded: the captured graph's replay, or eager."""
+        if not self._use_graph:
+            self._device_pass(jpeg_in)
+        elif jpeg_in:
+            self._graph_jpeg.replay()                      # (captured by _upload_jpeg, ahead of the upload)
+        else:
+            if self._graph is None:
+                self._capture()
+            self._graph.replay()
+
+    def _upload_jpeg(self, staging):
+        """Decoded coefficients (decode_frames' staging) -> the device coefficient buffer, on the current stream."""
+        mem = self.eng.mem
+        if self._use_graph and self._graph_jpeg is None:
+            self._capture(True)
+        if hasattr(mem, "torch"):
+            self._src_coef.copy_(staging[1], non_blocking=True)
+        else:
+            self._src_coef[...] = staging[0]
 
     def release(self):
         """Drop the captured graph (and the encode threads)."""
         self._graph = None
+        self._graph_jpeg = None
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
@@ -128,24 +269,26 @@ class FrameStylizer(object):
 
     def __call__(self, frames_u8):
         """frames_u8: host uint8 [H,W,3] (or [B,H,W,3]) -> host uint8 stylized frame(s) of the net's output size; with jpeg=: the bytes of
-        its JPEG file (a list of them for a batch)."""
-        a = np.asarray(frames_u8)
-        single = a.ndim == 3
-        if single:
-            a = a[np.newaxis]
-        if a.shape != self.shape or a.dtype != np.uint8:
-            raise L.FaststyleError("frame shape %s dtype %s, stylizer was built for uint8 %s" % (a.shape, a.dtype, self.shape))
+        its JPEG file (a list of them for a batch).  With source=: the frames have the source's size; with source jpeg=: a frame may be the
+        bytes of a JPEG file (a list of them for a batch)."""
         mem = self.eng.mem
-        if hasattr(mem, "torch"):
-            self._in_u8.copy_(mem.torch.from_numpy(np.ascontiguousarray(a)), non_blocking=True)
+        files = as_jpeg_frames(frames_u8)
+        if files is not None:                                    # JPEG bytes (source jpeg=): host Huffman pass, then everything on the device
+            single = isinstance(frames_u8, (bytes, bytearray, memoryview))
+            self._upload_jpeg(self.decode_frames(files, self._src_host))       # (raises FrameNotTaken before anything is enqueued)
+            self._run(True)
         else:
-            self._in_u8[...] = a
-        if self._use_graph:
-            if self._graph is None:
-                self._capture()
-            self._graph.replay()
-        else:
-            self._device_pass()
+            a = np.asarray(frames_u8)
+            single = a.ndim == 3
+            if single:
+                a = a[np.newaxis]
+            if a.shape != self.in_shape or a.dtype != np.uint8:
+                raise L.FaststyleError("frame shape %s dtype %s, stylizer was built for uint8 %s" % (a.shape, a.dtype, self.in_shape))
+            if hasattr(mem, "torch"):
+                self._pix_dst.copy_(mem.torch.from_numpy(np.ascontiguousarray(a)), non_blocking=True)
+            else:
+                self._pix_dst[...] = a
+            self._run()
         if self.jpeg is not None:
             coef = np.ascontiguousarray(mem.to_numpy(self._coef))  # (synchronises)
             if self._pool is None and self.out_shape[0] > 1 and self._jthreads > 1:
@@ -155,6 +298,15 @@ class FrameStylizer(object):
             return files[0] if single else files
         out = np.array(mem.to_numpy(self._out_u8), copy=True)     # (synchronises; the device buffer is reused next frame)
         return out[0] if single else out
+
+
+def as_jpeg_frames(frames):
+    """[bytes, ...] when ``frames`` is one JPEG file's bytes or a list of them, else None (pixel frames)."""
+    if isinstance(frames, (bytes, bytearray, memoryview)):
+        return [bytes(frames)]
+    if isinstance(frames, (list, tuple)) and frames and all(isinstance(f, (bytes, bytearray, memoryview)) for f in frames):
+        return [bytes(f) for f in frames]
+    return None
 
 
 class PipelinedStylizer(object):
@@ -184,7 +336,7 @@ class PipelinedStylizer(object):
         self.lanes = [FrameStylizer(eng, variables, height, width, **kw) for _ in range(self.depth)]
         self.streams = [torch.cuda.Stream() for _ in self.lanes]
         self.events = [torch.cuda.Event() for _ in self.lanes]
-        self.host_in = [torch.empty(ln.shape, dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
+        self.host_in = [torch.empty(ln.in_shape, dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
         self.host_out = [torch.empty(ln.out_shape, dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
         self.jpeg = self.lanes[0].jpeg
         self._pool = None
@@ -195,28 +347,50 @@ class PipelinedStylizer(object):
         self._pending = collections.deque()
         self._n = 0
         self._single = collections.deque()
+        self.source = self.lanes[0].source
+        # JPEG frames (source jpeg=): run() decodes up to `_ahead` frames beyond the submitted ones (one per decode thread, `depth` at least), and
+        # frame number n decodes into staging buffer n % (_ahead + depth) -- when frame n is decoded, frame n - _ahead has been submitted, so frame
+        # n - _ahead - depth has been fetched and its upload from that buffer is complete
+        self._staging = None
+        self._decode_pool = None
+        self._ahead = self.depth
+        if self.lanes[0]._src_jpeg is not None:
+            from concurrent.futures import ThreadPoolExecutor
+            threads = max(1, int(jpeg_threads))
+            self._ahead = max(self.depth, threads)
+            self._staging = [self.lanes[0].new_coef_staging() for _ in range(self._ahead + self.depth)]
+            self._decode_pool = ThreadPoolExecutor(threads)
 
-    def submit(self, frames_u8):
+    def _decode(self, files, n):
+        """Frame number n's host half (any thread): its decoded staging buffer, or raises FrameNotTaken."""
+        return self.lanes[0].decode_frames(files, self._staging[n % len(self._staging)])
+
+    def submit(self, frames_u8, _decoded=None):
+        """Enqueue one frame (pixels; with source jpeg= also the bytes of a JPEG file, decoded here on the calling thread)."""
         if len(self._pending) >= self.depth:
             raise L.FaststyleError("PipelinedStylizer: %d frames in flight already -- fetch() one first" % self.depth)
-        a = np.asarray(frames_u8)
-        single = a.ndim == 3
-        if single:
-            a = a[np.newaxis]
         k = self._n % self.depth
         ln, st, torch = self.lanes[k], self.streams[k], self.torch
-        if a.shape != ln.shape or a.dtype != np.uint8:
-            raise L.FaststyleError("frame shape %s dtype %s, stylizer was built for uint8 %s" % (a.shape, a.dtype, ln.shape))
-        self.host_in[k].copy_(torch.from_numpy(np.ascontiguousarray(a)))       # (host -> pinned host; the lane's previous frame was fetched: its buffers are free)
+        files = as_jpeg_frames(frames_u8)
+        if files is not None:
+            single = not isinstance(frames_u8, (list, tuple))
+            staged = _decoded if _decoded is not None else self._decode(files, self._n)      # (FrameNotTaken: nothing is enqueued)
+        else:
+            a = np.asarray(frames_u8)
+            single = a.ndim == 3
+            if single:
+                a = a[np.newaxis]
+            if a.shape != ln.in_shape or a.dtype != np.uint8:
+                raise L.FaststyleError("frame shape %s dtype %s, stylizer was built for uint8 %s" % (a.shape, a.dtype, ln.in_shape))
+            self.host_in[k].copy_(torch.from_numpy(np.ascontiguousarray(a)))       # (host -> pinned host; the lane's previous frame was fetched: its buffers are free)
         st.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(st):
-            ln._in_u8.copy_(self.host_in[k], non_blocking=True)
-            if ln._use_graph:
-                if ln._graph is None:
-                    ln._capture()
-                ln._graph.replay()
+            if files is not None:
+                ln._upload_jpeg(staged)
+                ln._run(True)
             else:
-                ln._device_pass()
+                ln._pix_dst.copy_(self.host_in[k], non_blocking=True)
+                ln._run()
             if self.jpeg is not None:
                 self.host_coef[k].copy_(ln._coef, non_blocking=True)
             else:
@@ -244,11 +418,41 @@ class PipelinedStylizer(object):
         out = self.host_out[k].numpy().copy()
         return out[0] if single else out
 
-    def run(self, frames):
-        for f in frames:
+    def run(self, frames, not_taken=None):
+        """Results of ``frames`` in order, `depth` of them in flight.  JPEG frames (bytes) are decoded ahead on the thread pool, one frame
+        per decode thread beyond the submitted ones: the Huffman pass of the next frames overlaps device work.  not_taken: called with the bytes of a
+        frame that raised FrameNotTaken, returns its pixels (the driver's PIL decode); without it the exception reaches the caller."""
+        import collections
+        ahead = collections.deque()                              # (frame, decode future or None), in order
+        it = iter(frames)
+        done = False
+        while True:
+            while not done and len(ahead) < self._ahead:
+                try:
+                    f = next(it)
+                except StopIteration:
+                    done = True
+                    break
+                files = as_jpeg_frames(f)
+                n = self._n + len(ahead)
+                ahead.append((f, self._decode_pool.submit(self._decode, files, n) if files is not None and self._decode_pool is not None else None))
+            if not ahead:
+                break
+            f, fut = ahead.popleft()
+            staged = None
+            if fut is not None:
+                try:
+                    staged = fut.result()
+                except FrameNotTaken:
+                    if not_taken is None:
+                        for _, other in ahead:                   # (let the decodes in flight finish: they write into this object's buffers)
+                            if other is not None:
+                                other.exception()
+                        raise
+                    f = not_taken(f)
             if len(self._pending) >= self.depth:
                 yield self.fetch()
-            self.submit(f)
+            self.submit(f, _decoded=staged)
         while self._pending:
             yield self.fetch()
 
@@ -258,3 +462,6 @@ class PipelinedStylizer(object):
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
+        if getattr(self, "_decode_pool", None) is not None:
+            self._decode_pool.shutdown(wait=True)
+            self._decode_pool = None

@@ -17,17 +17,32 @@ def imread(path):
     return np.asarray(Image.open(path).convert("RGB"))
 
 
-def imresize(img, scale):
-    """utils.imresize (utils.py:25-40): cubic for scale>1, area for scale<1, identity at 1."""
+def imresize(img, scale, engine=None):
+    """utils.imresize (utils.py:25-40): cubic for scale>1, area for scale<1, identity at 1.  With ``engine`` the same array, computed by the
+    device kernels (csrc/fs_cvresize.hip) instead of the host restatement."""
     if scale == 1.0:
         return img
     from . import cvresize
     a = np.asarray(img)
     if a.dtype != np.uint8:      # (the reference only ever resizes what imread returned: uint8)
         a = np.clip(np.rint(a), 0, 255).astype(np.uint8)
+    resize = cvresize.resize if engine is None else (lambda x, s: _imresize_device(engine, x, s))
     if a.ndim == 2:
-        return cvresize.resize(a[:, :, None], scale)[:, :, 0]
-    return cvresize.resize(a, scale)
+        return resize(a[:, :, None], scale)[:, :, 0]
+    return resize(a, scale)
+
+
+def _imresize_device(engine, a, scale):
+    """cvresize.resize(a, scale) of a uint8 [H,W,C] image on the device: the kernels take three channels at a time (channels are independent, a
+    group short of three repeats its last one)."""
+    out = []
+    for c in range(0, a.shape[2], 3):
+        g = a[:, :, c:c + 3]
+        n = g.shape[2]
+        if n < 3:
+            g = np.concatenate([g] + [g[:, :, -1:]] * (3 - n), axis=2)
+        out.append(engine.cvresize(g, scale, scale)[:, :, :n])
+    return out[0] if len(out) == 1 else np.concatenate(out, axis=2)
 
 
 def imwrite(path, img):

@@ -231,6 +231,57 @@ size_t fs_jpeg_write_bound(const fs_jpeg_info* info);
  * baseline range (a DC difference beyond category 11, an AC value beyond category 10), -5 coef not 2-byte aligned. */
 int fs_jpeg_write(const fs_jpeg_info* info, const void* coef, size_t coef_bytes, void* out, size_t cap, size_t* n);
 
+/* ---- cv2.resize of OpenCV 3.1.0 on u8 images (csrc/fs_cvresize.hip): the resampling of the reference's utils.imresize and of the frame loop's
+ * --frame_size, bit-identical to faststyle_amd/cvresize.py (resize_cubic_u8 / resize_area_u8), whose docstring is the arithmetic contract.  The
+ * encoder's split: a host-only plan, host-only per-axis tables, and one asynchronous device call. */
+
+#define FS_CV_INTER_CUBIC 2           /* cv2.INTER_CUBIC */
+#define FS_CV_INTER_AREA 3            /* cv2.INTER_AREA */
+#define FS_CVRESIZE_PATH_CUBIC 0      /* 11-bit fixed-point Keys taps, int32 passes */
+#define FS_CVRESIZE_PATH_AREA_FAST 1  /* integer factors on both axes: box means, no tables */
+#define FS_CVRESIZE_PATH_AREA 2       /* fractional factors: coverage-weighted float32 sums in computeResizeAreaTab's order */
+
+/* What fs_cvresize_plan reports.  The tables of the two axes share one buffer of table_bytes bytes: the x axis at x_offset, the y axis at
+ * y_offset (multiples of 16).
+ *   cubic      per output index 8 int32: the four source indices (clamped to the edge pixel), then their four 11-bit weights;
+ *   area       n_dst + 1 int32 (entry d: the first tap of output index d; entry n_dst: x_taps / y_taps), padded to a multiple of 8 bytes, then per
+ *              tap {int32 source index, float32 weight}, in computeResizeAreaTab's order;
+ *   area fast  no tables (table_bytes 0): factor_x x factor_y boxes.
+ * No implicit padding: 12 int32, then double and uint64. */
+typedef struct fs_cvresize_info {
+    int32_t src_h, src_w;
+    int32_t dst_h, dst_w;              /* cvRound(src_h * fy), cvRound(src_w * fx), ties to even */
+    int32_t interpolation;             /* FS_CV_INTER_CUBIC or FS_CV_INTER_AREA, as asked */
+    int32_t path;                      /* FS_CVRESIZE_PATH_* */
+    int32_t factor_x, factor_y;        /* area fast: cvRound(1 / fx), cvRound(1 / fy); else 0 */
+    int32_t x_taps, y_taps;            /* area: entries of each axis table; else 0 */
+    int32_t reserved[2];
+    double fx, fy;
+    uint64_t x_offset, y_offset;
+    uint64_t table_bytes;
+} fs_cvresize_info;
+
+/* Plans cv2.resize(src [H,W,3] u8, dsize=None, fx, fy, interpolation).  Host only: no HIP call, no global state, no allocation.
+ * Errors: -1 null plan / H or W outside [1, 32767] / fx or fy not finite and positive / a destination side outside [1, 32767],
+ * -2 an interpolation other than the two above, or FS_CV_INTER_AREA with fx > 1 or fy > 1 (enlarging by area is not defined here). */
+int fs_cvresize_plan(int H, int W, double fx, double fy, int interpolation, fs_cvresize_info* plan);
+
+/* Writes the plan's tables into tables[0, plan->table_bytes): the double -> float32 arithmetic of cvresize._cubic_axis / _area_tab.  Host
+ * only, as fs_cvresize_plan.  Errors: -1 null argument (tables may be null when table_bytes is 0) / a plan fs_cvresize_plan did not fill /
+ * cap < table_bytes, -5 tables not 4-byte aligned. */
+int fs_cvresize_tables(const fs_cvresize_info* plan, void* tables, size_t cap);
+
+/* Resizes N images: src holds N images of src_h x src_w pixels of src_pixel_bytes bytes each (3 = RGB, 4 = RGBX as fs_jpeg_reconstruct_many
+ * writes it, the fourth byte never read), back to back without padding; dst receives N packed-RGB images of dst_h x dst_w pixels; with
+ * swap_rb != 0 R and B are exchanged on the way out (the BGR order of a cv2 capture).  tables_dev: the device copy of what fs_cvresize_tables
+ * wrote (ignored for the area fast path).  Asynchronous on the ctx stream, allocates nothing, can be captured into a hipGraph.  No pixel value
+ * reaches an address, and the kernels clamp every table entry into the source themselves: a stale or wrong table gives wrong pixels, nothing
+ * else.  A refused call launches nothing.
+ * Errors: -1 null argument / N outside [1, 65535] / a plan fs_cvresize_plan did not fill, -2 src_pixel_bytes other than 3 or 4,
+ * -5 tables_dev not 16-byte aligned, or a source of 4-byte pixels not 4-byte aligned. */
+int fs_cvresize_u8(fs_ctx* ctx, const fs_cvresize_info* plan, const void* tables_dev, const unsigned char* src, int src_pixel_bytes, int N,
+                   int swap_rb, unsigned char* dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,15 +49,15 @@ def optimise(eng, vgg_weights, style_img, cont_img, cfg, learn_rate, num_steps_b
 
 def main(args):
     from faststyle_amd import engine, utils, vgg16
+    eng = engine.Engine()
     style_img = utils.imread(args.style_img_path)
-    style_img = utils.imresize(style_img, args.style_target_resize)
+    style_img = utils.imresize(style_img, args.style_target_resize, engine=eng)
     style_img = style_img[np.newaxis, :].astype(np.float32)
     cont_img = utils.imread(args.cont_img_path)
-    cont_img = utils.imresize(cont_img, args.cont_target_resize)
+    cont_img = utils.imresize(cont_img, args.cont_target_resize, engine=eng)
     cont_img = cont_img[np.newaxis, :].astype(np.float32)
     cfg = dict(content_layers=args.loss_content_layers, content_weights=args.content_weights,
                style_layers=args.loss_style_layers, style_weights=args.style_weights, beta=args.beta)
-    eng = engine.Engine()
     vgg_w = vgg16.load_weights('libs/vgg16_weights.npz')             # slow_style.py:100 (path relative to CWD)
     img_out = optimise(eng, vgg_w, style_img, cont_img, cfg, args.learn_rate, args.num_steps_break)
     utils.imwrite(args.output_img_path, np.squeeze(img_out))

@@ -23,11 +23,11 @@ def main(argv=None):
     from faststyle_amd.im_transf_net import create_net
 
     # Read + preprocess input image (stylize_image.py:57-60).
+    eng = engine.Engine()                 # fails loudly without the HIP library / a GPU
     img = utils.imread(args.input_img_path)
-    img = utils.imresize(img, args.content_target_resize)
+    img = utils.imresize(img, args.content_target_resize, engine=eng)      # (cv2.resize's resampling, on the device)
     img_4d = img[np.newaxis, :].astype(np.float32)
 
-    eng = engine.Engine()                 # fails loudly without the HIP library / a GPU
     print('Loading up model...')
     variables = eng.mem.from_numpy(eng.flatten_params(ckpt.load_checkpoint(args.model_path),
                                                       upsample_method=args.upsample_method))

@@ -9,7 +9,9 @@ image does not ship; without it the script can still filter a *directory of fram
 reference's channel handling -- BGR fed as is, output swapped -- is reproduced bit for bit).
 ``--output_format jpg [--output_quality 95]`` writes <name>.jpg instead of <name>.png, encoded by the
 library (faststyle_amd/stream.py, jpeg=): the bytes PIL would write for the pixels of the .png at that
-quality, 4:2:0.
+quality, 4:2:0.  ``--frame_size W H`` resizes every frame on the device with cv2.resize's resampling (INTER_AREA shrinking,
+INTER_CUBIC otherwise), and ``--input_decode native`` hands baseline .jpg frames to the library's decoder (Huffman pass on host
+threads, reconstruction on the GPU) instead of PIL; the results are the same files.
 """
 import os
 import sys
@@ -36,6 +38,8 @@ def _load(args):
 def run_frames_dir(args):
     from PIL import Image
     from faststyle_amd import stream
+    if args.frame_size is not None and args.resolution is not None:
+        raise SystemExit('--frame_size (device resize) and --resolution (PIL resize) are mutually exclusive')
     names = sorted(f for f in os.listdir(args.frames_dir) if f.lower().endswith(('.jpg', '.jpeg', '.png')))
     if not names:
         raise SystemExit('no frames under %s' % args.frames_dir)
@@ -46,7 +50,6 @@ def run_frames_dir(args):
     # FS_FRAMES_IN_FLIGHT=1 for one at a time).  The results -- and their order -- are the same.
     import collections
     depth = int(os.environ.get('FS_FRAMES_IN_FLIGHT', '2')) if hasattr(eng.mem, 'torch') else 1
-    st = None
     pend = collections.deque()
 
     # --output_format jpg: the lanes encode.  The .png holds img_out[:, :, ::-1], the lane's frame with R and B swapped back -- which is the frame
@@ -62,30 +65,75 @@ def run_frames_dir(args):
         # cv2.imshow / VideoWriter interpret that array as BGR; save exactly what they would show
         Image.fromarray(img_out[:, :, ::-1]).save(os.path.join(args.output_dir, os.path.splitext(n)[0] + '.png'))
 
-    for n in names:
-        im = Image.open(os.path.join(args.frames_dir, n)).convert('RGB')
+    # --frame_size W H: every frame is resized to W x H on the device, with cv2.resize's resampling (stream.py, source=).  --input_decode native: the
+    # .jpg / .jpeg frames the library's decoder takes go in as file bytes (RGB; the lane swaps R and B on the device, source swap_rb: the BGR of a
+    # cv2 capture, as the PIL path below delivers it from the host); the others, and whatever fails to decode, go through PIL.  --resolution is a
+    # PIL resize and therefore keeps the PIL decode.
+    native = args.input_decode == 'native' and args.resolution is None
+
+    def pil_rgb(src):
+        im = Image.open(src).convert('RGB')
         if args.resolution is not None:
             im = im.resize(tuple(args.resolution))
-        frame = np.asarray(im, np.uint8)[:, :, ::-1]              # what cap.read() returns: BGR
-        if st is None or shape != frame.shape[:2]:
-            while pend:
-                save(pend.popleft(), st.fetch())
-            shape = frame.shape[:2]
-            print('Resolution is: {0} by {1}'.format(frame.shape[1], frame.shape[0]))
-            if depth > 1:
-                st = stream.PipelinedStylizer(eng, variables, frame.shape[0], frame.shape[1], depth=depth, upsample_method=args.upsample_method,
-                                                 **kw)
-            else:
-                st = stream.FrameStylizer(eng, variables, frame.shape[0], frame.shape[1], args.upsample_method, **kw)
-        if depth > 1:
-            if len(pend) >= depth:
-                save(pend.popleft(), st.fetch())
-            st.submit(np.ascontiguousarray(frame))
-            pend.append(n)
+        return np.asarray(im, np.uint8)
+
+    def frames():
+        """(name, key, frame): key tells which stylizer takes the frame -- ('pix', Hs, Ws) for BGR pixels, ('jpeg', source dict) for file bytes"""
+        for n in names:
+            path = os.path.join(args.frames_dir, n)
+            if native and n.lower().endswith(('.jpg', '.jpeg')):
+                with open(path, 'rb') as f:
+                    data = f.read()
+                src = stream.jpeg_source(eng, data, swap_rb=True)
+                if src is not None:
+                    yield n, ('jpeg', src), data
+                    continue
+            frame = np.ascontiguousarray(pil_rgb(path)[:, :, ::-1])          # what cap.read() returns: BGR
+            yield n, ('pix',) + frame.shape[:2], frame
+
+    def build(key):
+        if key[0] == 'jpeg':
+            source = key[1]
+            Hs, Ws = source['height'], source['width']
         else:
-            save(n, st(np.ascontiguousarray(frame)))                 # = cvtColor(astype(uint8)(Y), BGR2RGB)
-    while pend:
-        save(pend.popleft(), st.fetch())
+            Hs, Ws = key[1:]
+            source = dict(height=Hs, width=Ws) if args.frame_size is not None else None
+        W, H = args.frame_size if args.frame_size is not None else (Ws, Hs)
+        print('Resolution is: {0} by {1}'.format(W, H))
+        more = dict(kw, source=source) if source is not None else kw
+        if depth > 1:
+            return stream.PipelinedStylizer(eng, variables, H, W, depth=depth, upsample_method=args.upsample_method, **more)
+        return stream.FrameStylizer(eng, variables, H, W, args.upsample_method, **more)
+
+    def not_taken(data):
+        import io
+        return np.array(pil_rgb(io.BytesIO(data)))                           # (RGB: a stylizer of JPEG frames swaps on the device)
+
+    it = frames()
+    cur = next(it, None)
+    while cur is not None:                                                  # one stylizer per run of frames of the same source
+        key, nxt = cur[1], [None]
+        st = build(key)
+
+        def segment(item=cur):
+            while item is not None and item[1] == key:
+                pend.append(item[0])
+                yield item[2]
+                item = next(it, None)
+            nxt[0] = item
+
+        if depth > 1:
+            for out in st.run(segment(), not_taken=not_taken):
+                save(pend.popleft(), out)
+        else:
+            for frame in segment():
+                try:
+                    out = st(frame)                                          # = cvtColor(astype(uint8)(Y), BGR2RGB)
+                except stream.FrameNotTaken:
+                    out = st(not_taken(frame))
+                save(pend.popleft(), out)
+        st.release()
+        cur = nxt[0]
 
 
 def run_webcam(args):

@@ -1,6 +1,11 @@
 #!/usr/bin/env python
 """Throughput of the TFRecord input pipeline alone (decode threads + GPU resize + HBM shuffle queue) on
-synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode]
+synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode | frames_in]
+"frames_in": the frames-dir loop end to end (stylize_webcam.run_frames_dir, two frames in flight, --output_format jpg) at 720p over a directory of
+n JPEG frames: PIL decode against --input_decode native, and from 1080p sources PIL decode + PIL resize (--resolution) against native decode +
+device resize (--frame_size).  Every leg runs on the same device, legs alternate over the repeats, and a leg's rate is taken from the DIFFERENCE
+between its run over n frames and its run over n / 4 frames, so that engine start-up, checkpoint load and graph capture drop out; written to
+profiles/frames_in.json (or to the file named as a fourth argument).
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -73,10 +78,81 @@ def host_encode(n, th):
     return res
 
 
+def frames_in(n, repeats=3, out_json=None):
+    """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json."""
+    import contextlib
+    import json
+    import shutil
+    from PIL import Image
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import stylize_webcam
+    n = max(16, n // 4 * 4)
+    d = tempfile.mkdtemp()
+    rng = np.random.default_rng(0)
+    base = rng.integers(0, 256, (135, 240, 3), dtype=np.uint8)
+    dirs = {}
+    for tag, (w, h) in (("720p", (1280, 720)), ("1080p", (1920, 1080))):
+        files = []
+        for k in range(16):      # 16 distinct natural-ish frames (upsampled noise), reused
+            buf = io.BytesIO()
+            Image.fromarray(np.roll(base, 5 * k, axis=1)).resize((w, h), Image.BICUBIC).save(buf, "JPEG", quality=90)
+            files.append(buf.getvalue())
+        for count in (n, n // 4):
+            p = os.path.join(d, "%s_%d" % (tag, count))
+            os.makedirs(p)
+            for k in range(count):
+                with open(os.path.join(p, "f%05d.jpg" % k), "wb") as f:
+                    f.write(files[k % 16])
+            dirs[tag, count] = p
+        print("frames_in: %s sources, %.0f KB/file" % (tag, np.mean([len(f) for f in files]) / 1e3))
+    legs = [("pil_decode_720p", "720p", []),
+            ("native_decode_720p", "720p", ["--input_decode", "native"]),
+            ("pil_decode_pil_resize_1080p_to_720p", "1080p", ["--resolution", "1280", "720"]),
+            ("native_decode_device_resize_1080p_to_720p", "1080p", ["--input_decode", "native", "--frame_size", "1280", "720"]),
+            ("pil_decode_device_resize_1080p_to_720p", "1080p", ["--frame_size", "1280", "720"])]
+    parser = stylize_webcam.setup_parser()
+    out = os.path.join(d, "out")
+
+    def run(tag, count, flags):
+        args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--frames_dir", dirs[tag, count],
+                                  "--output_dir", out, "--output_format", "jpg"] + flags)
+        with contextlib.redirect_stdout(io.StringIO()):
+            t0 = time.time()
+            stylize_webcam.run_frames_dir(args)
+            dt = time.time() - t0
+        assert len(os.listdir(out)) == count
+        shutil.rmtree(out)
+        return dt
+
+    run("720p", n // 4, [])                                       # warm-up: library load, first kernels
+    times = {name: [] for name, _, _ in legs}
+    for _ in range(repeats):                                      # legs alternate: a drifting clock touches all of them alike
+        for name, tag, flags in legs:
+            times[name].append((run(tag, n, flags), run(tag, n // 4, flags)))
+            print("frames_in: %s: %.2f s for %d frames, %.2f s for %d" % ((name,) + (times[name][-1][0], n, times[name][-1][1], n // 4)), flush=True)
+    res = {"frames": n, "frames_in_flight": 2, "host_threads": "1 driver + 4 decode / encode",
+           "host_cores": os.cpu_count(), "omp_num_threads": os.environ.get("OMP_NUM_THREADS"), "output": "jpg quality 95 4:2:0",
+           "method": "rate = (n - n/4) / (t(n) - t(n/4)), median of %d alternating repeats" % repeats, "legs": {}}
+    for name, _, _ in legs:
+        rates = sorted((n - n // 4) / (a - b) for a, b in times[name])
+        res["legs"][name] = {"frames_per_s": rates[len(rates) // 2], "all_repeats": rates, "seconds_n_and_quarter": times[name]}
+        print("frames_in: %7.0f frames/s %s (repeats: %s)" % (rates[len(rates) // 2], name, ", ".join("%.0f" % r for r in rates)))
+    shutil.rmtree(d)
+    dst = out_json or os.path.join(root, "profiles", "frames_in.json")
+    with open(dst, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    return res
+
+
 def main():
     from PIL import Image
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     threads = int(sys.argv[2]) if len(sys.argv) > 2 else None
+    if len(sys.argv) > 3 and sys.argv[3] == "frames_in":
+        frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None)
+        return
     if len(sys.argv) > 3 and sys.argv[3] == "host_encode":
         host_encode(n, threads or 4)
         return

@@ -109,7 +109,7 @@ def main(args):
 
     # Load in style image that will define the model (train.py:135-137).
     style_img = utils.imread(args.style_img_path)
-    style_img = utils.imresize(style_img, args.style_target_resize)
+    style_img = utils.imresize(style_img, args.style_target_resize, engine=eng)
     style_img = style_img[np.newaxis, :].astype(np.float32)
 
     cfg = dict(content_layers=args.loss_content_layers, content_weights=args.content_weights,
