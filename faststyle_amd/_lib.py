@@ -82,6 +82,14 @@ class fs_cvresize_info(Structure):
                 ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("x_offset", c_uint64), ("y_offset", c_uint64), ("table_bytes", c_uint64)]
 
 
+class fs_yuv_desc(Structure):
+    """include/faststyle_io.h: one planar YCbCr frame geometry, filled by fs_yuv_plan."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
+                ("ncomp", ctypes.c_int32), ("siting", ctypes.c_int32), ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32),
+                ("chroma_w", ctypes.c_int32), ("chroma_h", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2),
+                ("plane_offset", c_uint64 * 3), ("plane_bytes", c_uint64 * 3), ("frame_bytes", c_uint64)]
+
+
 class fs_wgrad_desc(Structure):
     _fields_ = [("x", c_void_p), ("dy", c_void_p), ("dw", c_void_p),
                 ("N", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int),
@@ -185,6 +193,9 @@ PROTOTYPES = {
     "fs_cvresize_plan": (c_int, [c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, POINTER(fs_cvresize_info)]),
     "fs_cvresize_tables": (c_int, [POINTER(fs_cvresize_info), c_void_p, c_size_t]),
     "fs_cvresize_u8": (c_int, [c_void_p, POINTER(fs_cvresize_info), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fs_yuv_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(fs_yuv_desc)]),
+    "fs_yuv_to_rgb_u8": (c_int, [c_void_p, POINTER(fs_yuv_desc), c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fs_rgb_to_yuv_u8": (c_int, [c_void_p, POINTER(fs_yuv_desc), c_void_p, c_int, c_int, c_int, c_void_p]),
     "fs_u8_to_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "fs_f32_to_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
 }

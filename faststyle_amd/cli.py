@@ -84,8 +84,17 @@ def stylize_webcam_parser():
         ('--output_quality', dict(default=95, type=int, help='(addition) JPEG quality 1..100 of --output_format jpg')),
         ('--frame_size', dict(nargs=2, type=int, default=None, metavar=('W', 'H'),
                               help="(addition) resize every --frames_dir frame to W x H on the device with cv2.resize's resampling (area when "
-                                   "shrinking, cubic otherwise); not together with --resolution, which keeps its PIL resize")),
+                                   "shrinking, cubic otherwise); not together with --resolution, which keeps its PIL resize; also resizes "
+                                   "--video_in frames")),
         ('--input_decode', dict(choices=['pil', 'native'], default='pil',
                                 help="(addition) decoder of the --frames_dir frames: 'pil', or 'native' -- baseline .jpg / .jpeg files go in as "
                                      "bytes (Huffman pass on host threads, reconstruction on the GPU); other files still go through PIL")),
+        ('--video_in', dict(default=None, metavar='PATH|-',
+                            help="(addition) read frames from this YUV4MPEG2 stream ('-': standard input), e.g. the output of ffmpeg -f yuv4mpegpipe; "
+                                 "colour conversion on the device; composes with --frame_size, not with --frames_dir or --resolution")),
+        ('--video_out', dict(default=None, metavar='PATH|-',
+                             help="(addition) write the --video_in results as a YUV4MPEG2 stream ('-': standard output, every message then goes to "
+                                  "standard error) with the input's frame rate, aspect, sampling, siting and range; without it they go to --output_dir")),
+        ('--video_matrix', dict(choices=['bt601', 'bt709'], default='bt601',
+                                help="(addition) YCbCr matrix of the --video_in / --video_out streams (the format does not record it)")),
     ])

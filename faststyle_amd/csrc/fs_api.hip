@@ -193,6 +193,24 @@ int fs_cvresize_u8(fs_ctx* ctx, const fs_cvresize_info* plan, const void* tables
     const int rc = fs::cvresize_u8(*plan, static_cast<const unsigned char*>(tables_dev), src, src_pixel_bytes, N, swap_rb ? 1 : 0, dst, ctx->stream);
     return rc ? fail(rc, "fs_cvresize_u8: launch failed (%d)", rc) : 0;
 }
+int fs_yuv_to_rgb_u8(fs_ctx* ctx, const fs_yuv_desc* desc, const void* yuv, int N, int pixel_bytes, int swap_rb, unsigned char* rgb) {
+    if (!ctx || !desc || !yuv || !rgb) return fail(-1, "fs_yuv_to_rgb_u8: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_yuv_to_rgb_u8: N must be in [1, 65535], got %d", N);
+    if (pixel_bytes != 3 && pixel_bytes != 4) return fail(-2, "fs_yuv_to_rgb_u8: pixel_bytes must be 3 (RGB) or 4 (RGBX), got %d", pixel_bytes);
+    if (!fs::yuv_desc_ok(*desc)) return fail(-1, "fs_yuv_to_rgb_u8: the descriptor (%dx%d, %dx%d sampling) was not filled by fs_yuv_plan", desc->width, desc->height, desc->hs, desc->vs);
+    if (pixel_bytes == 4 && ((uintptr_t)rgb & 3)) return fail(-5, "fs_yuv_to_rgb_u8: a destination of 4-byte pixels must be 4-byte aligned");
+    const int rc = fs::yuv_to_rgb_u8(*desc, static_cast<const unsigned char*>(yuv), N, pixel_bytes, swap_rb ? 1 : 0, rgb, ctx->stream);
+    return rc ? fail(rc, "fs_yuv_to_rgb_u8: launch failed (%d)", rc) : 0;
+}
+int fs_rgb_to_yuv_u8(fs_ctx* ctx, const fs_yuv_desc* desc, const unsigned char* rgb, int pixel_bytes, int swap_rb, int N, void* yuv) {
+    if (!ctx || !desc || !rgb || !yuv) return fail(-1, "fs_rgb_to_yuv_u8: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_rgb_to_yuv_u8: N must be in [1, 65535], got %d", N);
+    if (pixel_bytes != 3 && pixel_bytes != 4) return fail(-2, "fs_rgb_to_yuv_u8: pixel_bytes must be 3 (RGB) or 4 (RGBX), got %d", pixel_bytes);
+    if (!fs::yuv_desc_ok(*desc)) return fail(-1, "fs_rgb_to_yuv_u8: the descriptor (%dx%d, %dx%d sampling) was not filled by fs_yuv_plan", desc->width, desc->height, desc->hs, desc->vs);
+    if (pixel_bytes == 4 && ((uintptr_t)rgb & 3)) return fail(-5, "fs_rgb_to_yuv_u8: a source of 4-byte pixels must be 4-byte aligned");
+    const int rc = fs::rgb_to_yuv_u8(*desc, rgb, pixel_bytes, swap_rb ? 1 : 0, N, static_cast<unsigned char*>(yuv), ctx->stream);
+    return rc ? fail(rc, "fs_rgb_to_yuv_u8: launch failed (%d)", rc) : 0;
+}
 int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
                   const int32_t* move_dst, int M, float* batch_out) {
     if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");

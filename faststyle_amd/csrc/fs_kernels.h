@@ -18,6 +18,7 @@ struct fs_resize_item;   // include/faststyle_io.h
 struct fs_jpeg_item;
 struct fs_jpegenc_item;
 struct fs_cvresize_info;
+struct fs_yuv_desc;
 
 namespace fs {
 
@@ -681,6 +682,10 @@ int jpeg_forward_many(const unsigned char* src_base, size_t src_bytes, const ::f
 bool cvresize_plan_ok(const ::fs_cvresize_info& plan);
 int cvresize_u8(const ::fs_cvresize_info& plan, const unsigned char* tables, const unsigned char* src, int pixel_bytes, int N, int swap_rb,
                 unsigned char* dst, hipStream_t s);
+// planar YCbCr <-> packed RGB (fs_yuv.hip): whether a descriptor is what fs_yuv_plan fills, and the two launches (pixel_bytes 3 or 4)
+bool yuv_desc_ok(const ::fs_yuv_desc& desc);
+int yuv_to_rgb_u8(const ::fs_yuv_desc& desc, const unsigned char* yuv, int N, int pixel_bytes, int swap_rb, unsigned char* rgb, hipStream_t s);
+int rgb_to_yuv_u8(const ::fs_yuv_desc& desc, const unsigned char* rgb, int pixel_bytes, int swap_rb, int N, unsigned char* yuv, hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);
 // ... with the per-sample sums taken from records [N][T][C][2] (rec == nullptr: computed here into `scratch`), reduced in the apply kernel's

@@ -206,7 +206,24 @@ class CvResizeHost(object):
         return CvResizePlan(info, tables)
 
 
-class Engine(JpegHost, CvResizeHost):
+class YuvHost(object):
+    """The host call of the planar YCbCr kernels (csrc/fs_yuv.hip): the frame geometry.  It needs the library and no device."""
+
+    def __init__(self, lib=None):
+        self.lib = lib if lib is not None else L.load()
+
+    def yuv_plan(self, width, height, sampling=(2, 2), siting=0, matrix=0, full_range=False, components=3):
+        """fs_yuv_plan: the fs_yuv_desc of width x height frames -- sampling (hs, vs) of luma against chroma, siting 0 centre / 1 co-sited,
+        matrix 0 BT.601 / 1 BT.709 (or 'bt601' / 'bt709'), components 3 or 1 (mono).  A refused geometry raises FaststyleError."""
+        hs, vs = (int(v) for v in sampling)
+        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
+        desc = L.fs_yuv_desc()
+        L.check(self.lib, self.lib.fs_yuv_plan(int(width), int(height), hs, vs, int(components), int(siting), int(matrix), int(full_range),
+                                               ctypes.byref(desc)), "fs_yuv_plan")
+        return desc
+
+
+class Engine(JpegHost, CvResizeHost, YuvHost):
     # Workspaces are cached per shape (a backward must find the workspace its forward filled; a captured hipGraph replays raw
     # pointers into its own).  The cache is bounded by BYTES, least recently used first: stylizing a directory of mixed
     # resolutions must not pile up one multi-GB workspace per size.  Entries a live hipGraph replays into are pinned by
@@ -851,6 +868,36 @@ class Engine(JpegHost, CvResizeHost):
         out = self.mem.upload_u8(np.zeros(plan.dst_shape + (3,), np.uint8))
         self.cvresize_u8(self.mem.upload_u8(img), plan, out, swap_rb=swap_rb)
         return np.array(self.mem.to_numpy(out), copy=True)
+
+    # ------------------------------------------------------------------ planar YCbCr <-> packed RGB (csrc/fs_yuv.hip)
+    def _yuv_count(self, desc, yuv_dev, rgb_dev, what):
+        """(N, pixel_bytes) of a pair of device buffers: yuv_dev holds N frames of desc.frame_bytes, rgb_dev [N,]H,W,3|4."""
+        shape = tuple(int(d) for d in rgb_dev.shape)
+        pb = shape[-1]
+        N = int(np.prod(yuv_dev.shape)) // int(desc.frame_bytes)
+        if len(shape) not in (3, 4) or shape[-3:-1] != (int(desc.height), int(desc.width)) or N < 1 or \
+                N * int(desc.frame_bytes) != int(np.prod(yuv_dev.shape)) or int(np.prod(shape[:-3])) != N:
+            raise L.FaststyleError("%s: planes %s / pixels %s do not fit %dx%d frames of %d bytes" % (what, tuple(yuv_dev.shape), shape, desc.width,
+                                                                                                  desc.height, desc.frame_bytes))
+        return N, pb
+
+    def yuv_to_rgb_u8(self, yuv_dev, desc, out_dev, swap_rb=False):
+        """fs_yuv_to_rgb_u8: yuv_dev device uint8 [frame_bytes] or [N, frame_bytes] (the planes as YUV4MPEG2 stores them) -> out_dev device
+        uint8 [H,W,3|4] / [N,H,W,3|4] (4: RGBX); swap_rb: written B,G,R."""
+        self._sync_stream()
+        N, pb = self._yuv_count(desc, yuv_dev, out_dev, "yuv_to_rgb_u8")
+        L.check(self.lib, self.lib.fs_yuv_to_rgb_u8(self.ctx, ctypes.byref(desc), self.mem.ptr_u8(yuv_dev), N, pb, 1 if swap_rb else 0,
+                                                    self.mem.ptr_u8(out_dev)), "fs_yuv_to_rgb_u8")
+        return out_dev
+
+    def rgb_to_yuv_u8(self, rgb_dev, desc, out_dev, swap_rb=False):
+        """fs_rgb_to_yuv_u8: rgb_dev device uint8 [H,W,3|4] / [N,H,W,3|4] (swap_rb: the pixels are B,G,R) -> out_dev device uint8
+        [frame_bytes] / [N, frame_bytes]."""
+        self._sync_stream()
+        N, pb = self._yuv_count(desc, out_dev, rgb_dev, "rgb_to_yuv_u8")
+        L.check(self.lib, self.lib.fs_rgb_to_yuv_u8(self.ctx, ctypes.byref(desc), self.mem.ptr_u8(rgb_dev), pb, 1 if swap_rb else 0, N,
+                                                    self.mem.ptr_u8(out_dev)), "fs_rgb_to_yuv_u8")
+        return out_dev
 
     def synth_uniform(self, out, seed, rank, batch_index):
         """Uniform [0,255) float32 values into ``out``: Philox4x32-10 keyed by seed, counter (element block, batch_index, rank) (fs_synth_uniform)."""

@@ -20,6 +20,13 @@ fs_cvresize.hip; interpolation None: area when shrinking, cubic otherwise; swap_
 bytes of a baseline JPEG file of that geometry: fs_jpeg_parse / fs_jpeg_decode run on the host into a pinned coefficient buffer, and
 fs_jpeg_reconstruct_many, the resize, the net and the optional encoder run in the captured graph.  A file that does not fit raises
 FrameNotTaken before anything is enqueued; the caller decodes it with PIL and hands the pixels to the same stylizer.
+
+Raw video (faststyle_amd/y4m.py): with ``source=dict(height=, width=, yuv=dict(sampling=(hs, vs), siting=, matrix=, full_range=, components=))``
+the frames are planar 8-bit YCbCr as a YUV4MPEG2 stream stores them -- a flat uint8 array of frame_bytes, or [B, frame_bytes] -- and the device
+pass begins with fs_yuv_to_rgb_u8 (csrc/fs_yuv.hip): straight into the net's input when the source has the net's size, otherwise into an RGBX
+buffer that the resize reads; ``swap_rb`` of the source keeps its meaning.  Such a stylizer takes YCbCr frames only.  With
+``yuv_out=dict(sampling=, siting=, matrix=, full_range=, components=3)`` (not together with ``jpeg=``) the pass ends with fs_rgb_to_yuv_u8 on the u8
+frame and the stylizer returns the planes, a uint8 array of frame_bytes, instead of the pixels.
 """
 import ctypes
 
@@ -47,7 +54,7 @@ class FrameStylizer(object):
     KEEP_GRAPH = False     # tests: keep the captured hipGraph_t so that its node types can be inspected
 
     def __init__(self, eng, variables, height, width, upsample_method="resize", batch=1, swap_rb=True, use_graph=True,
-                 bf16=False, jpeg=None, jpeg_threads=4, source=None):
+                 bf16=False, jpeg=None, jpeg_threads=4, source=None, yuv_out=None):
         self.eng = eng
         self.variables = variables
         self.method = upsample_method
@@ -71,6 +78,13 @@ class FrameStylizer(object):
         self._pool = None
         if jpeg is not None:
             self._jpeg_setup(dict(jpeg), int(jpeg_threads))
+        self.yuv_out = None
+        self.yuv_out_desc = None         # with yuv_out=: the fs_yuv_desc of an output frame (what a y4m.Writer takes)
+        self._result = self._out_u8      # the device buffer __call__ downloads (without jpeg=)
+        if yuv_out is not None:
+            if jpeg is not None:
+                raise L.FaststyleError("jpeg= and yuv_out= are mutually exclusive: a stylizer returns one kind of frame")
+            self._yuv_out_setup(dict(yuv_out))
         self.source = None
         self.in_shape = self.shape       # the pixel frames __call__ takes, and the device buffer they are uploaded into
         self._pix_dst = self._in_u8
@@ -78,8 +92,26 @@ class FrameStylizer(object):
         self._src_jpeg = None
         self._graph_jpeg = None
         self._src_host = None
+        self._src_yuv = None
         if source is not None:
             self._source_setup(dict(source))
+
+    YUV_KEYS = ("sampling", "siting", "matrix", "full_range", "components")
+
+    def _yuv_desc(self, opt, width, height, what):
+        """The fs_yuv_desc of a yuv= / yuv_out= dict at a frame size; unknown keys raise."""
+        opt = dict(opt)
+        kw = {k: opt.pop(k) for k in self.YUV_KEYS if k in opt}
+        if opt:
+            raise L.FaststyleError("%s takes %s, got also %r" % (what, ", ".join(self.YUV_KEYS), opt))
+        return self.eng.yuv_plan(width, height, **kw), kw
+
+    def _yuv_out_setup(self, opt):
+        """The output side's colour conversion: the descriptor of one output frame and the device buffer of the batch's planes."""
+        B, Ho, Wo, _ = self.out_shape
+        self.yuv_out_desc, kw = self._yuv_desc(opt, Wo, Ho, "yuv_out")
+        self.yuv_out = kw
+        self._result = self.eng.mem.upload_u8(np.zeros((B, int(self.yuv_out_desc.frame_bytes)), np.uint8))
 
     def _source_setup(self, opt):
         """The input side's fixed parts: the resize plan from the source size (none when nothing is to be resized or swapped), the device buffer
@@ -91,11 +123,24 @@ class FrameStylizer(object):
         except KeyError:
             raise L.FaststyleError("source needs height and width, got %r" % opt)
         interpolation, swap, jp = opt.pop("interpolation", None), bool(opt.pop("swap_rb", False)), opt.pop("jpeg", None)
+        yuv = opt.pop("yuv", None)
         if opt:
-            raise L.FaststyleError("source takes height, width, interpolation, swap_rb and jpeg, got also %r" % opt)
+            raise L.FaststyleError("source takes height, width, interpolation, swap_rb, jpeg and yuv, got also %r" % opt)
         self.source = dict(height=Hs, width=Ws, interpolation=interpolation, swap_rb=swap, jpeg=None if jp is None else dict(jp))
-        self.in_shape = (B, Hs, Ws, 3)
         self._src_swap = swap
+        if yuv is not None:
+            if jp is not None:
+                raise L.FaststyleError("source jpeg= and yuv= are mutually exclusive: the frames of a stylizer have one form")
+            self._src_yuv, self.source["yuv"] = self._yuv_desc(yuv, Ws, Hs, "source yuv")
+            self.in_shape = (B, int(self._src_yuv.frame_bytes))
+            self._pix_dst = mem.upload_u8(np.zeros(self.in_shape, np.uint8))             # the planes as uploaded
+            if (Hs, Ws) != (H, W):                                                      # (a swap alone is the conversion's own)
+                self._src_plan = e.cvresize_plan(Hs, Ws, W / float(Ws), H / float(Hs), interpolation)
+                if self._src_plan.dst_shape != (H, W):
+                    raise L.FaststyleError("source %dx%d does not resize to %dx%d but to %dx%d" % ((Hs, Ws, H, W) + self._src_plan.dst_shape))
+                self._src_rgbx = mem.upload_u8(np.zeros((B, Hs, Ws, 4), np.uint8))
+            return
+        self.in_shape = (B, Hs, Ws, 3)
         if (Hs, Ws) != (H, W) or swap:
             self._src_plan = e.cvresize_plan(Hs, Ws, W / float(Ws), H / float(Hs), interpolation)
             if self._src_plan.dst_shape != (H, W):
@@ -202,6 +247,12 @@ class FrameStylizer(object):
                 e.cvresize_u8(self._src_rgbx, self._src_plan, self._in_u8, swap_rb=self._src_swap)
             else:
                 e.jpeg_reconstruct_many(self._src_coef, self._sitems, self._in_u8, items_dev=(self._sitems_dev, 0))
+        elif self._src_yuv is not None:                      # the planes of the frame(s) are in self._pix_dst
+            if self._src_plan is not None:
+                e.yuv_to_rgb_u8(self._pix_dst, self._src_yuv, self._src_rgbx)
+                e.cvresize_u8(self._src_rgbx, self._src_plan, self._in_u8, swap_rb=self._src_swap)
+            else:
+                e.yuv_to_rgb_u8(self._pix_dst, self._src_yuv, self._in_u8, swap_rb=self._src_swap)
         elif self._src_plan is not None:                     # source pixels are in self._pix_dst
             e.cvresize_u8(self._pix_dst, self._src_plan, self._in_u8, swap_rb=self._src_swap)
         e.u8_to_f32(self._in_u8, self._in_f32)
@@ -210,6 +261,8 @@ class FrameStylizer(object):
         e.f32_to_u8(self._y, self._out_u8, swap_rb=self.swap_rb)
         if self.jpeg is not None:
             e.jpeg_forward_many(self._out_u8, self._jitems, self._coef, items_dev=(self._jitems_dev, 0))
+        if self.yuv_out is not None:
+            e.rgb_to_yuv_u8(self._out_u8, self.yuv_out_desc, self._result)
 
     def _capture(self, jpeg_in=False):
         """Capture the device pass of pixel frames (self._graph) or of JPEG frames (self._graph_jpeg).  The warm-up runs the pass once on
@@ -269,8 +322,9 @@ class FrameStylizer(object):
 
     def __call__(self, frames_u8):
         """frames_u8: host uint8 [H,W,3] (or [B,H,W,3]) -> host uint8 stylized frame(s) of the net's output size; with jpeg=: the bytes of
-        its JPEG file (a list of them for a batch).  With source=: the frames have the source's size; with source jpeg=: a frame may be the
-        bytes of a JPEG file (a list of them for a batch)."""
+        its JPEG file (a list of them for a batch); with yuv_out=: its planes, uint8 [frame_bytes] (or [B, frame_bytes]).  With source=: the
+        frames have the source's size; with source jpeg=: a frame may be the bytes of a JPEG file (a list of them for a batch); with source
+        yuv=: a frame is its planes, uint8 [frame_bytes] (or [B, frame_bytes])."""
         mem = self.eng.mem
         files = as_jpeg_frames(frames_u8)
         if files is not None:                                    # JPEG bytes (source jpeg=): host Huffman pass, then everything on the device
@@ -279,7 +333,7 @@ class FrameStylizer(object):
             self._run(True)
         else:
             a = np.asarray(frames_u8)
-            single = a.ndim == 3
+            single = a.ndim == len(self.in_shape) - 1                # ([H,W,3] pixels, or with source yuv= the flat planes of one frame)
             if single:
                 a = a[np.newaxis]
             if a.shape != self.in_shape or a.dtype != np.uint8:
@@ -296,7 +350,7 @@ class FrameStylizer(object):
                 self._pool = ThreadPoolExecutor(self._jthreads)
             files = self._write_all(coef.ctypes.data, self._pool)
             return files[0] if single else files
-        out = np.array(mem.to_numpy(self._out_u8), copy=True)     # (synchronises; the device buffer is reused next frame)
+        out = np.array(mem.to_numpy(self._result), copy=True)     # (synchronises; the device buffer is reused next frame)
         return out[0] if single else out
 
 
@@ -324,7 +378,10 @@ class PipelinedStylizer(object):
 
     With jpeg=dict(quality=, subsampling=) every lane ends in the encoder's device half and downloads coefficients into a pinned buffer of its
     own; a pool of `jpeg_threads` host threads (default 4) waits for a lane's event and entropy-codes its frame while the next frames are on the
-    device (fs_jpeg_write holds no interpreter lock).  fetch() / run() then give bytes, in submission order."""
+    device (fs_jpeg_write holds no interpreter lock).  fetch() / run() then give bytes, in submission order.
+
+    source yuv= and yuv_out= (raw video, see the module docstring) pass through to the lanes: the planes go up from and come down into the
+    lanes' pinned buffers; order and depth are unchanged.  next_input() lends the next lane's pinned input buffer to a stream reader."""
 
     def __init__(self, eng, variables, height, width, depth=2, jpeg_threads=4, **kw):
         if not hasattr(eng.mem, "torch"):
@@ -337,7 +394,7 @@ class PipelinedStylizer(object):
         self.streams = [torch.cuda.Stream() for _ in self.lanes]
         self.events = [torch.cuda.Event() for _ in self.lanes]
         self.host_in = [torch.empty(ln.in_shape, dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
-        self.host_out = [torch.empty(ln.out_shape, dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
+        self.host_out = [torch.empty(tuple(ln._result.shape), dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
         self.jpeg = self.lanes[0].jpeg
         self._pool = None
         if self.jpeg is not None:
@@ -348,6 +405,7 @@ class PipelinedStylizer(object):
         self._n = 0
         self._single = collections.deque()
         self.source = self.lanes[0].source
+        self.yuv_out_desc = self.lanes[0].yuv_out_desc
         # JPEG frames (source jpeg=): run() decodes up to `_ahead` frames beyond the submitted ones (one per decode thread, `depth` at least), and
         # frame number n decodes into staging buffer n % (_ahead + depth) -- when frame n is decoded, frame n - _ahead has been submitted, so frame
         # n - _ahead - depth has been fetched and its upload from that buffer is complete
@@ -377,12 +435,13 @@ class PipelinedStylizer(object):
             staged = _decoded if _decoded is not None else self._decode(files, self._n)      # (FrameNotTaken: nothing is enqueued)
         else:
             a = np.asarray(frames_u8)
-            single = a.ndim == 3
+            single = a.ndim == len(ln.in_shape) - 1
             if single:
                 a = a[np.newaxis]
             if a.shape != ln.in_shape or a.dtype != np.uint8:
                 raise L.FaststyleError("frame shape %s dtype %s, stylizer was built for uint8 %s" % (a.shape, a.dtype, ln.in_shape))
-            self.host_in[k].copy_(torch.from_numpy(np.ascontiguousarray(a)))       # (host -> pinned host; the lane's previous frame was fetched: its buffers are free)
+            if a.ctypes.data != self.host_in[k].data_ptr():                        # (next_input()'s buffer, filled in place: nothing to copy)
+                self.host_in[k].copy_(torch.from_numpy(np.ascontiguousarray(a)))   # (host -> pinned host; the lane's previous frame was fetched: its buffers are free)
         st.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(st):
             if files is not None:
@@ -394,7 +453,7 @@ class PipelinedStylizer(object):
             if self.jpeg is not None:
                 self.host_coef[k].copy_(ln._coef, non_blocking=True)
             else:
-                self.host_out[k].copy_(ln._out_u8, non_blocking=True)
+                self.host_out[k].copy_(ln._result, non_blocking=True)
             self.events[k].record(st)
         if self.jpeg is not None:
             k = (k, self._pool.submit(self._encode, k))           # (the lane is reused only after fetch() has taken this result)
@@ -402,13 +461,26 @@ class PipelinedStylizer(object):
         self._single.append(single)
         self._n += 1
 
+    @property
+    def in_flight(self):
+        """Frames submitted and not yet fetched (at most `depth`)."""
+        return len(self._pending)
+
+    def next_input(self):
+        """The pinned input buffer of the lane the next submit() uses, as a numpy array of the lane's in_shape: a reader fills it in place
+        (y4m.Reader.read_frame_into) and hands it -- or its first row, for a single frame -- to submit(), which then copies nothing on the
+        host.  Valid while fewer than `depth` frames are in flight: the lane's previous upload has completed once its result was fetched."""
+        if len(self._pending) >= self.depth:
+            raise L.FaststyleError("PipelinedStylizer: %d frames in flight already -- fetch() one first" % self.depth)
+        return self.host_in[self._n % self.depth].numpy()
+
     def _encode(self, k):
         """On an encode thread: wait for lane k's download, then Huffman-code its frame(s)."""
         self.events[k].synchronize()
         return self.lanes[k]._write_all(self.host_coef[k].data_ptr())
 
     def fetch(self):
-        """The oldest submitted frame's result (host uint8; bytes with jpeg=), waiting for its lane only."""
+        """The oldest submitted frame's result (host uint8; bytes with jpeg=; the planes with yuv_out=), waiting for its lane only."""
         k = self._pending.popleft()
         single = self._single.popleft()
         if self.jpeg is not None:

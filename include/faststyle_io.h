@@ -282,6 +282,73 @@ int fs_cvresize_tables(const fs_cvresize_info* plan, void* tables, size_t cap);
 int fs_cvresize_u8(fs_ctx* ctx, const fs_cvresize_info* plan, const void* tables_dev, const unsigned char* src, int src_pixel_bytes, int N,
                    int swap_rb, unsigned char* dst);
 
+/* ---- Planar 8-bit YCbCr frames <-> packed RGB (csrc/fs_yuv.hip): the colour conversion of raw video streams (YUV4MPEG2, faststyle_amd/y4m.py),
+ * so that a frame crosses PCIe as its planes (1.5 B/px for 4:2:0) and needs no entropy coder on the host.  A host-only plan and two asynchronous
+ * device calls.  The arithmetic below is the contract (tests/test_yuv.py restates it in numpy and compares exactly); it is integer throughout.
+ *
+ * Layout: the Y plane (height rows of width samples), then Cb, then Cr (chroma_h rows of chroma_w samples each, chroma_w = ceil(width / hs),
+ * chroma_h = ceil(height / vs)), back to back without padding, as YUV4MPEG2 stores a frame; a mono frame (ncomp 1) is its Y plane alone.
+ *
+ * Chroma upsampling to one u8 value per pixel: bilinear interpolation at the sited positions, edge samples replicated (neighbour indices
+ * clamped), rounded half up once.  Every weight is dyadic, so each value is exact.  With C the chroma sample of the pixel's own cell
+ * (column x / hs, row y / vs):
+ *   centre siting (siting 0), a subsampled axis       near = C, far = the neighbour on the pixel's side of the cell (x or y even: the previous
+ *                                                     sample, odd: the next); one axis (3 near + far + 2) >> 2, both axes
+ *                                                     (9 a + 3 b + 3 c + d + 8) >> 4 with a near on both axes, d far on both;
+ *   co-sited horizontally (siting 1, hs 2)            even column: the sample itself; odd column: (l + r + 1) >> 1 of C and its right neighbour;
+ *   vertically (vs 2)                                 as centre siting, for either value of siting; with siting 1 the odd column of 4:2:0 is
+ *                                                     (3 ln + 3 rn + lf + rf + 4) >> 3 (n the near row, f the far row).
+ * (Not the IJG library's alternating-bias variant of fs_jpeg_reconstruct_many.)
+ *
+ * YCbCr -> RGB: with (Kr, Kb) = (0.299, 0.114) for BT.601 or (0.2126, 0.0722) for BT.709, Kg = 1 - Kr - Kb, and (sy, sc, oy) =
+ * (255/219, 255/224, 16) for limited range or (1, 1, 0) for full range, the real formulas
+ *   R = sy (Y - oy) + 2 (1 - Kr) sc (Cr - 128)
+ *   B = sy (Y - oy) + 2 (1 - Kb) sc (Cb - 128)
+ *   G = sy (Y - oy) - 2 (1 - Kb) Kb / Kg sc (Cb - 128) - 2 (1 - Kr) Kr / Kg sc (Cr - 128)
+ * are evaluated with each coefficient c replaced by floor(c * 65536 + 0.5) (BT.601 limited range: 76309 for sy), the sum in int32, plus 32768,
+ * arithmetic shift right by 16, clamped to [0, 255].  A mono frame reads as Cb = Cr = 128.
+ *
+ * RGB -> YCbCr, per pixel, to u8: the rows (Kr, Kg, Kb) / sy, (-Kr, -Kg, 1 - Kb) / (2 (1 - Kb)) / sc and (1 - Kr, -Kg, -Kb) / (2 (1 - Kr)) / sc,
+ * each coefficient rounded the same way, the offset (oy, 128, 128) added as offset << 16, plus 32768, shift right by 16, clamped to [0, 255]
+ * (full range reaches 256).
+ *
+ * Chroma downsampling of those u8 values, neighbour indices clamped to the image:
+ *   centre siting     2x2: (a + b + c + d + 2) >> 2 of the cell's four pixels; 2x1: (a + b + 1) >> 1;
+ *   co-sited          [1 2 1] / 4 about the even column m = 2 * column: (l + 2 m + r + 2) >> 2 for 2x1; for 2x2 that sum of the cell's two rows,
+ *                     plus 4, >> 3;
+ *   1x1               the value itself.  A mono frame gets its Y plane only. */
+
+/* One frame geometry, filled by fs_yuv_plan.  No implicit padding: 12 int32, then 7 uint64 (104 bytes). */
+typedef struct fs_yuv_desc {
+    int32_t width, height;
+    int32_t hs, vs;                    /* luma samples per chroma sample: 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0) */
+    int32_t ncomp;                     /* 3, or 1: mono */
+    int32_t siting;                    /* 0 centre (JPEG / MPEG-1), 1 horizontally co-sited with the even luma column (MPEG-2, 4:2:2) */
+    int32_t matrix;                    /* 0 BT.601, 1 BT.709 */
+    int32_t full_range;                /* 0: Y 16..235, chroma 16..240; 1: 0..255 */
+    int32_t chroma_w, chroma_h;        /* ceil(width / hs), ceil(height / vs); 0 for mono */
+    int32_t reserved[2];
+    uint64_t plane_offset[3];          /* within a frame, bytes */
+    uint64_t plane_bytes[3];
+    uint64_t frame_bytes;
+} fs_yuv_desc;
+
+/* Fills *desc.  Host only: no HIP call, no global state, no allocation.  Errors: -1 null desc / width or height outside [1, 32767],
+ * -2 a sampling other than 1x1, 2x1, 2x2, ncomp other than 3 or 1 (1 with 1x1 only), siting, matrix or full_range other than 0 or 1. */
+int fs_yuv_plan(int width, int height, int hs, int vs, int ncomp, int siting, int matrix, int full_range, fs_yuv_desc* desc);
+
+/* N frames at yuv, desc->frame_bytes apart -> N images of height x width pixels of pixel_bytes bytes at rgb, back to back: 3 = packed R,G,B,
+ * 4 = R,G,B,X with X written as 255 (what fs_cvresize_u8 reads); swap_rb != 0: the pixels are written B,G,R.  Asynchronous on the ctx stream,
+ * allocates nothing, can be captured into a hipGraph; grid.y is the image.  No value read from a frame reaches an address.  A refused call
+ * launches nothing.  Errors: -1 null argument / N outside [1, 65535] / a desc fs_yuv_plan did not fill, -2 pixel_bytes other than 3 or 4,
+ * -5 rgb of 4-byte pixels not 4-byte aligned (yuv and packed rgb may have any alignment: 4-byte aligned buffers of a width that is a multiple
+ * of 4 take the dword path, the others the byte path, with the same values). */
+int fs_yuv_to_rgb_u8(fs_ctx* ctx, const fs_yuv_desc* desc, const void* yuv, int N, int pixel_bytes, int swap_rb, unsigned char* rgb);
+
+/* The reverse: N images of pixel_bytes bytes per pixel at rgb (the fourth byte never read; swap_rb != 0: the source pixels are B,G,R) -> N
+ * frames at yuv.  As fs_yuv_to_rgb_u8 in every other respect, error codes included. */
+int fs_rgb_to_yuv_u8(fs_ctx* ctx, const fs_yuv_desc* desc, const unsigned char* rgb, int pixel_bytes, int swap_rb, int N, void* yuv);
+
 #ifdef __cplusplus
 }
 #endif

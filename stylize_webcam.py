@@ -12,6 +12,14 @@ library (faststyle_amd/stream.py, jpeg=): the bytes PIL would write for the pixe
 quality, 4:2:0.  ``--frame_size W H`` resizes every frame on the device with cv2.resize's resampling (INTER_AREA shrinking,
 INTER_CUBIC otherwise), and ``--input_decode native`` hands baseline .jpg frames to the library's decoder (Huffman pass on host
 threads, reconstruction on the GPU) instead of PIL; the results are the same files.
+
+Video without OpenCV: ``--video_in`` / ``--video_out`` read and write YUV4MPEG2 streams (faststyle_amd/y4m.py), the raw format ffmpeg, x264 and mpv
+speak on pipes; ``-`` is standard input / output:
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python stylize_webcam.py --model_path m.ckpt --video_in - --video_out - | ffmpeg -i - out.mp4
+    ffmpeg -f v4l2 -i /dev/video0 -f yuv4mpegpipe - | python stylize_webcam.py --model_path m.ckpt --video_in - --video_out - | ffplay -
+Chroma resampling and the YCbCr <-> RGB matrix (``--video_matrix``, BT.601 by default) run on the device inside each lane's graph; the host reads a
+frame's planes into pinned memory and writes the result's planes, nothing else.  The output stream has the input's frame rate, aspect, sampling,
+siting and range at the net's output size.  ``--video_in`` without ``--video_out`` writes 000000.png, 000001.png ... (or .jpg) to --output_dir.
 """
 import os
 import sys
@@ -136,6 +144,119 @@ def run_frames_dir(args):
         cur = nxt[0]
 
 
+def check_video_flags(args):
+    """The flag combinations --video_in / --video_out do not take: SystemExit with the reason, before anything is loaded."""
+    if args.video_out is not None and args.video_in is None:
+        raise SystemExit('--video_out needs --video_in: it writes the stylized frames of that stream')
+    if args.video_in is not None and args.frames_dir is not None:
+        raise SystemExit('--video_in and --frames_dir are mutually exclusive: frames come from one place')
+    if args.video_in is not None and args.resolution is not None:
+        raise SystemExit('--video_in and --resolution are mutually exclusive: --resolution is a PIL resize of image files; use --frame_size W H')
+
+
+def run_video(args):
+    """--video_in [--video_out]: a YUV4MPEG2 stream through the pipelined lanes.  The driver reads frame i + 1 into the next lane's pinned buffer
+    while frame i is on the device."""
+    from faststyle_amd import _lib, engine, stream, y4m
+    check_video_flags(args)
+    to_stdout = args.video_out == '-'
+    log = sys.stderr if to_stdout else sys.stdout
+
+    def say(text):
+        print(text, file=log)
+        log.flush()
+
+    fin = sys.stdin.buffer if args.video_in == '-' else open(args.video_in, 'rb')
+    fout = None
+    try:
+        try:
+            reader = y4m.Reader(fin)
+        except y4m.Y4MError as e:
+            raise SystemExit('--video_in %s: %s' % (args.video_in, e))
+        fmt = reader.format
+        Ws, Hs = fmt.width, fmt.height
+        colour = dict(sampling=fmt.sampling, siting=fmt.siting, matrix=args.video_matrix, full_range=fmt.full_range, components=fmt.components)
+        try:
+            engine.YuvHost().yuv_plan(Ws, Hs, **colour)                      # (a frame the kernels do not take: said before the model is loaded)
+        except _lib.FaststyleError as e:
+            raise SystemExit('--video_in %s: %s' % (args.video_in, e))
+        W, H = args.frame_size if args.frame_size is not None else (Ws, Hs)
+        say('Resolution is: {0} by {1}'.format(W, H))
+        say('Loading up model...')
+        eng, variables = _load(args)
+        # The channel quirk as in run_frames_dir: the net sees B,G,R (source swap_rb, what a cv2 capture delivers) and the output is swapped back --
+        # which is the frame of a lane that does not swap, so the lanes of a video or .jpg output are built with swap_rb=False.
+        kw = dict(source=dict(height=Hs, width=Ws, swap_rb=True, yuv=colour))
+        jpg = args.video_out is None and args.output_format == 'jpg'
+        if args.video_out is not None:
+            kw.update(swap_rb=False, yuv_out=colour)
+        elif jpg:
+            kw.update(swap_rb=False, jpeg=dict(quality=args.output_quality, subsampling=2))
+        depth = int(os.environ.get('FS_FRAMES_IN_FLIGHT', '2')) if hasattr(eng.mem, 'torch') else 1
+        if depth > 1:
+            st = stream.PipelinedStylizer(eng, variables, H, W, depth=depth, upsample_method=args.upsample_method, **kw)
+        else:
+            st = stream.FrameStylizer(eng, variables, H, W, args.upsample_method, **kw)
+        writer = None
+        if args.video_out is not None:
+            fout = sys.stdout.buffer if to_stdout else open(args.video_out, 'wb')
+            writer = y4m.Writer(fout, st.yuv_out_desc, rate=fmt.rate, aspect=fmt.aspect)
+        elif not os.path.isdir(args.output_dir):
+            os.makedirs(args.output_dir)
+        say('Begin filtering...')
+        done = [0]
+
+        def emit(out):
+            if writer is not None:
+                writer.write_frame(out)
+            elif jpg:
+                with open(os.path.join(args.output_dir, '%06d.jpg' % done[0]), 'wb') as f:
+                    f.write(out)
+            else:
+                from PIL import Image
+                Image.fromarray(out[:, :, ::-1]).save(os.path.join(args.output_dir, '%06d.png' % done[0]))
+            done[0] += 1
+
+        failed = None                                                        # a stream that breaks off: what was read is still written
+        try:
+            if depth > 1:
+                while failed is None:
+                    if st.in_flight >= depth:
+                        emit(st.fetch())
+                    buf = st.next_input()                                    # [1, frame_bytes], pinned
+                    try:
+                        if not reader.read_frame_into(buf):
+                            break
+                    except y4m.Y4MError as e:
+                        failed = e
+                        break
+                    st.submit(buf[0])
+                while st.in_flight:
+                    emit(st.fetch())
+            else:
+                buf = np.zeros(fmt.frame_bytes, np.uint8)
+                while failed is None:
+                    try:
+                        if not reader.read_frame_into(buf):
+                            break
+                    except y4m.Y4MError as e:
+                        failed = e
+                        break
+                    emit(st(buf))
+        finally:
+            st.release()
+        if writer is not None:
+            writer.flush()
+        say('%d frames' % done[0])
+        if failed is not None:
+            raise SystemExit('--video_in %s: %s' % (args.video_in, failed))
+    finally:
+        if args.video_in != '-':
+            fin.close()
+        if fout is not None and not to_stdout:
+            fout.close()
+
+
 def run_webcam(args):
     try:
         import cv2
@@ -170,7 +291,10 @@ def run_webcam(args):
 
 if __name__ == '__main__':
     args = setup_parser().parse_args()
-    if args.frames_dir is not None:
+    check_video_flags(args)
+    if args.video_in is not None:
+        run_video(args)
+    elif args.frames_dir is not None:
         run_frames_dir(args)
     else:
         run_webcam(args)

@@ -1,11 +1,14 @@
 #!/usr/bin/env python
 """Throughput of the TFRecord input pipeline alone (decode threads + GPU resize + HBM shuffle queue) on
-synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode | frames_in]
+synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode | frames_in | video]
 "frames_in": the frames-dir loop end to end (stylize_webcam.run_frames_dir, two frames in flight, --output_format jpg) at 720p over a directory of
 n JPEG frames: PIL decode against --input_decode native, and from 1080p sources PIL decode + PIL resize (--resolution) against native decode +
 device resize (--frame_size).  Every leg runs on the same device, legs alternate over the repeats, and a leg's rate is taken from the DIFFERENCE
 between its run over n frames and its run over n / 4 frames, so that engine start-up, checkpoint load and graph capture drop out; written to
 profiles/frames_in.json (or to the file named as a fourth argument).
+"video": the frames_in legs and, beside them in the same run with the same repeat and median scheme, the raw-video loop (stylize_webcam.run_video:
+--video_in / --video_out, 720p 4:2:0 YUV4MPEG2 from a file to a file, the same 16 frames as planes, the same frame counts); written to profiles/video_stream.json.  The video loop is several times faster than the
+others: give it enough frames (1280) that its timed difference is about a second.
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -78,8 +81,9 @@ def host_encode(n, th):
     return res
 
 
-def frames_in(n, repeats=3, out_json=None):
-    """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json."""
+def frames_in(n, repeats=3, out_json=None, video=False):
+    """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json (video: with the raw-video leg, to
+    profiles/video_stream.json)."""
     import contextlib
     import json
     import shutil
@@ -94,10 +98,17 @@ def frames_in(n, repeats=3, out_json=None):
     dirs = {}
     for tag, (w, h) in (("720p", (1280, 720)), ("1080p", (1920, 1080))):
         files = []
+        planes = []
         for k in range(16):      # 16 distinct natural-ish frames (upsampled noise), reused
             buf = io.BytesIO()
-            Image.fromarray(np.roll(base, 5 * k, axis=1)).resize((w, h), Image.BICUBIC).save(buf, "JPEG", quality=90)
+            im = Image.fromarray(np.roll(base, 5 * k, axis=1)).resize((w, h), Image.BICUBIC)
+            im.save(buf, "JPEG", quality=90)
             files.append(buf.getvalue())
+            if video and tag == "720p":      # the same frame as 4:2:0 planes (PIL's matrix, box-averaged chroma: the content only has to be plausible)
+                ycc = np.asarray(im.convert("YCbCr"), np.uint16)
+                sub = (ycc[0::2, 0::2, 1:] + ycc[0::2, 1::2, 1:] + ycc[1::2, 0::2, 1:] + ycc[1::2, 1::2, 1:] + 2) >> 2
+                planes.append(b"FRAME\n" + ycc[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 0].astype(np.uint8).tobytes() +
+                              sub[:, :, 1].astype(np.uint8).tobytes())
         for count in (n, n // 4):
             p = os.path.join(d, "%s_%d" % (tag, count))
             os.makedirs(p)
@@ -105,16 +116,37 @@ def frames_in(n, repeats=3, out_json=None):
                 with open(os.path.join(p, "f%05d.jpg" % k), "wb") as f:
                     f.write(files[k % 16])
             dirs[tag, count] = p
+        for count in (n, n // 4) if planes else ():
+            with open(os.path.join(d, "%s_%d.y4m" % (tag, count)), "wb") as f:
+                f.write(b"YUV4MPEG2 W%d H%d F30:1 Ip A1:1 C420jpeg XCOLORRANGE=FULL\n" % (w, h))
+                for k in range(count):
+                    f.write(planes[k % 16])
         print("frames_in: %s sources, %.0f KB/file" % (tag, np.mean([len(f) for f in files]) / 1e3))
     legs = [("pil_decode_720p", "720p", []),
             ("native_decode_720p", "720p", ["--input_decode", "native"]),
             ("pil_decode_pil_resize_1080p_to_720p", "1080p", ["--resolution", "1280", "720"]),
             ("native_decode_device_resize_1080p_to_720p", "1080p", ["--input_decode", "native", "--frame_size", "1280", "720"]),
             ("pil_decode_device_resize_1080p_to_720p", "1080p", ["--frame_size", "1280", "720"])]
+    if video:
+        legs.append(("video_y4m_720p", "720p", None))
     parser = stylize_webcam.setup_parser()
     out = os.path.join(d, "out")
 
+    def run_stream(tag, count):
+        """the raw-video loop over count frames, file to file"""
+        args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--video_in", os.path.join(d, "%s_%d.y4m" % (tag, count)),
+                                  "--video_out", out + ".y4m"])
+        with contextlib.redirect_stdout(io.StringIO()):
+            t0 = time.time()
+            stylize_webcam.run_video(args)
+            dt = time.time() - t0
+        assert os.path.getsize(out + ".y4m") > count * 1280 * 720 * 3 // 2
+        os.remove(out + ".y4m")
+        return dt
+
     def run(tag, count, flags):
+        if flags is None:
+            return run_stream(tag, count)
         args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--frames_dir", dirs[tag, count],
                                   "--output_dir", out, "--output_format", "jpg"] + flags)
         with contextlib.redirect_stdout(io.StringIO()):
@@ -134,12 +166,14 @@ def frames_in(n, repeats=3, out_json=None):
     res = {"frames": n, "frames_in_flight": 2, "host_threads": "1 driver + 4 decode / encode",
            "host_cores": os.cpu_count(), "omp_num_threads": os.environ.get("OMP_NUM_THREADS"), "output": "jpg quality 95 4:2:0",
            "method": "rate = (n - n/4) / (t(n) - t(n/4)), median of %d alternating repeats" % repeats, "legs": {}}
+    if video:
+        res["video"] = "720p 4:2:0 YUV4MPEG2 (full range, BT.601), file to file; 1 driver thread, no decode / encode threads"
     for name, _, _ in legs:
         rates = sorted((n - n // 4) / (a - b) for a, b in times[name])
         res["legs"][name] = {"frames_per_s": rates[len(rates) // 2], "all_repeats": rates, "seconds_n_and_quarter": times[name]}
         print("frames_in: %7.0f frames/s %s (repeats: %s)" % (rates[len(rates) // 2], name, ", ".join("%.0f" % r for r in rates)))
     shutil.rmtree(d)
-    dst = out_json or os.path.join(root, "profiles", "frames_in.json")
+    dst = out_json or os.path.join(root, "profiles", "video_stream.json" if video else "frames_in.json")
     with open(dst, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
@@ -150,8 +184,8 @@ def main():
     from PIL import Image
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     threads = int(sys.argv[2]) if len(sys.argv) > 2 else None
-    if len(sys.argv) > 3 and sys.argv[3] == "frames_in":
-        frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None)
+    if len(sys.argv) > 3 and sys.argv[3] in ("frames_in", "video"):
+        frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video")
         return
     if len(sys.argv) > 3 and sys.argv[3] == "host_encode":
         host_encode(n, threads or 4)
