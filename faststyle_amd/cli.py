@@ -97,4 +97,10 @@ def stylize_webcam_parser():
                                   "standard error) with the input's frame rate, aspect, sampling, siting and range; without it they go to --output_dir")),
         ('--video_matrix', dict(choices=['bt601', 'bt709'], default='bt601',
                                 help="(addition) YCbCr matrix of the --video_in / --video_out streams (the format does not record it)")),
+        ('--video_depth', dict(choices=['8', 'stream'], default='8',
+                               help="(addition) bits per sample taken from --video_in: '8' refuses deeper streams (C420p10 ...), 'stream' takes the "
+                                    "stream's own depth, 8 to 16 bits, and feeds 9 to 16 bits to the net without a u8 stage; not with --frame_size")),
+        ('--video_out_depth', dict(default=None, type=int, choices=list(range(8, 17)), metavar='N',
+                                   help="(addition) bits per sample of --video_out, 8..16 (default: the input's); above 8 the net's fp32 output "
+                                        "goes to the planes without a u8 stage")),
     ])

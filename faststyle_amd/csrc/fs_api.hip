@@ -211,6 +211,22 @@ int fs_rgb_to_yuv_u8(fs_ctx* ctx, const fs_yuv_desc* desc, const unsigned char* 
     const int rc = fs::rgb_to_yuv_u8(*desc, rgb, pixel_bytes, swap_rb ? 1 : 0, N, static_cast<unsigned char*>(yuv), ctx->stream);
     return rc ? fail(rc, "fs_rgb_to_yuv_u8: launch failed (%d)", rc) : 0;
 }
+int fs_yuv_deep_to_f32(fs_ctx* ctx, const fs_yuv_desc* desc, const void* yuv, int N, int swap_rb, float* dst) {
+    if (!ctx || !desc || !yuv || !dst) return fail(-1, "fs_yuv_deep_to_f32: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_yuv_deep_to_f32: N must be in [1, 65535], got %d", N);
+    if (!fs::yuv_deep_desc_ok(*desc)) return fail(-1, "fs_yuv_deep_to_f32: the descriptor (%dx%d, %dx%d sampling, %d bits) was not filled by fs_yuv_plan_deep", desc->width, desc->height, desc->hs, desc->vs, desc->reserved[0]);
+    if ((uintptr_t)yuv & 1) return fail(-5, "fs_yuv_deep_to_f32: planes of 16-bit samples must be 2-byte aligned");
+    const int rc = fs::yuv_deep_to_f32(*desc, static_cast<const unsigned char*>(yuv), N, swap_rb ? 1 : 0, dst, ctx->stream);
+    return rc ? fail(rc, "fs_yuv_deep_to_f32: launch failed (%d)", rc) : 0;
+}
+int fs_f32_to_yuv_deep(fs_ctx* ctx, const fs_yuv_desc* desc, const float* src, int swap_rb, int N, void* yuv) {
+    if (!ctx || !desc || !src || !yuv) return fail(-1, "fs_f32_to_yuv_deep: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_f32_to_yuv_deep: N must be in [1, 65535], got %d", N);
+    if (!fs::yuv_deep_desc_ok(*desc)) return fail(-1, "fs_f32_to_yuv_deep: the descriptor (%dx%d, %dx%d sampling, %d bits) was not filled by fs_yuv_plan_deep", desc->width, desc->height, desc->hs, desc->vs, desc->reserved[0]);
+    if ((uintptr_t)yuv & 1) return fail(-5, "fs_f32_to_yuv_deep: planes of 16-bit samples must be 2-byte aligned");
+    const int rc = fs::f32_to_yuv_deep(*desc, src, swap_rb ? 1 : 0, N, static_cast<unsigned char*>(yuv), ctx->stream);
+    return rc ? fail(rc, "fs_f32_to_yuv_deep: launch failed (%d)", rc) : 0;
+}
 int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
                   const int32_t* move_dst, int M, float* batch_out) {
     if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");

@@ -686,6 +686,10 @@ int cvresize_u8(const ::fs_cvresize_info& plan, const unsigned char* tables, con
 bool yuv_desc_ok(const ::fs_yuv_desc& desc);
 int yuv_to_rgb_u8(const ::fs_yuv_desc& desc, const unsigned char* yuv, int N, int pixel_bytes, int swap_rb, unsigned char* rgb, hipStream_t s);
 int rgb_to_yuv_u8(const ::fs_yuv_desc& desc, const unsigned char* rgb, int pixel_bytes, int swap_rb, int N, unsigned char* yuv, hipStream_t s);
+// planar YCbCr of 9 to 16 bits <-> fp32 RGB (fs_yuv16.hip): whether a descriptor is what fs_yuv_plan_deep fills, and the two launches
+bool yuv_deep_desc_ok(const ::fs_yuv_desc& desc);
+int yuv_deep_to_f32(const ::fs_yuv_desc& desc, const unsigned char* yuv, int N, int swap_rb, float* dst, hipStream_t s);
+int f32_to_yuv_deep(const ::fs_yuv_desc& desc, const float* src, int swap_rb, int N, unsigned char* yuv, hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);
 // ... with the per-sample sums taken from records [N][T][C][2] (rec == nullptr: computed here into `scratch`), reduced in the apply kernel's

@@ -212,12 +212,17 @@ class YuvHost(object):
     def __init__(self, lib=None):
         self.lib = lib if lib is not None else L.load()
 
-    def yuv_plan(self, width, height, sampling=(2, 2), siting=0, matrix=0, full_range=False, components=3):
+    def yuv_plan(self, width, height, sampling=(2, 2), siting=0, matrix=0, full_range=False, components=3, bits=8):
         """fs_yuv_plan: the fs_yuv_desc of width x height frames -- sampling (hs, vs) of luma against chroma, siting 0 centre / 1 co-sited,
-        matrix 0 BT.601 / 1 BT.709 (or 'bt601' / 'bt709'), components 3 or 1 (mono).  A refused geometry raises FaststyleError."""
+        matrix 0 BT.601 / 1 BT.709 (or 'bt601' / 'bt709'), components 3 or 1 (mono).  bits other than 8: fs_yuv_plan_deep, the frames of 9 to
+        16 bits per sample in 16-bit words (desc.reserved[0] = bits).  A refused geometry raises FaststyleError."""
         hs, vs = (int(v) for v in sampling)
         matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
         desc = L.fs_yuv_desc()
+        if int(bits) != 8:
+            L.check(self.lib, self.lib.fs_yuv_plan_deep(int(width), int(height), hs, vs, int(components), int(siting), int(matrix), int(full_range),
+                                                        int(bits), ctypes.byref(desc)), "fs_yuv_plan_deep")
+            return desc
         L.check(self.lib, self.lib.fs_yuv_plan(int(width), int(height), hs, vs, int(components), int(siting), int(matrix), int(full_range),
                                                ctypes.byref(desc)), "fs_yuv_plan")
         return desc
@@ -897,6 +902,29 @@ class Engine(JpegHost, CvResizeHost, YuvHost):
         N, pb = self._yuv_count(desc, out_dev, rgb_dev, "rgb_to_yuv_u8")
         L.check(self.lib, self.lib.fs_rgb_to_yuv_u8(self.ctx, ctypes.byref(desc), self.mem.ptr_u8(rgb_dev), pb, 1 if swap_rb else 0, N,
                                                     self.mem.ptr_u8(out_dev)), "fs_rgb_to_yuv_u8")
+        return out_dev
+
+    # ------------------------------------------------------------------ planar YCbCr of 9 to 16 bits <-> fp32 RGB (csrc/fs_yuv16.hip)
+    def yuv_deep_to_f32(self, yuv_dev, desc, out_f32, swap_rb=False):
+        """fs_yuv_deep_to_f32: yuv_dev device uint8 [frame_bytes] or [N, frame_bytes] (16-bit little-endian samples, desc of yuv_plan with
+        bits > 8) -> out_f32 device float32 [H,W,3] / [N,H,W,3] on the net's 0..255 scale; swap_rb: written B,G,R."""
+        self._sync_stream()
+        N, pb = self._yuv_count(desc, yuv_dev, out_f32, "yuv_deep_to_f32")
+        if pb != 3:
+            raise L.FaststyleError("yuv_deep_to_f32: the destination %s is not [..., 3]" % (tuple(out_f32.shape),))
+        L.check(self.lib, self.lib.fs_yuv_deep_to_f32(self.ctx, ctypes.byref(desc), self.mem.ptr_u8(yuv_dev), N, 1 if swap_rb else 0,
+                                                      self.mem.ptr(out_f32)), "fs_yuv_deep_to_f32")
+        return out_f32
+
+    def f32_to_yuv_deep(self, f32_dev, desc, out_dev, swap_rb=False):
+        """fs_f32_to_yuv_deep: f32_dev device float32 [H,W,3] / [N,H,W,3] (swap_rb: the channels are B,G,R) -> out_dev device uint8
+        [frame_bytes] / [N, frame_bytes], 16-bit little-endian samples."""
+        self._sync_stream()
+        N, pb = self._yuv_count(desc, out_dev, f32_dev, "f32_to_yuv_deep")
+        if pb != 3:
+            raise L.FaststyleError("f32_to_yuv_deep: the source %s is not [..., 3]" % (tuple(f32_dev.shape),))
+        L.check(self.lib, self.lib.fs_f32_to_yuv_deep(self.ctx, ctypes.byref(desc), self.mem.ptr(f32_dev), 1 if swap_rb else 0, N,
+                                                      self.mem.ptr_u8(out_dev)), "fs_f32_to_yuv_deep")
         return out_dev
 
     def synth_uniform(self, out, seed, rank, batch_index):

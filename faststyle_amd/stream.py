@@ -27,6 +27,12 @@ pass begins with fs_yuv_to_rgb_u8 (csrc/fs_yuv.hip): straight into the net's inp
 buffer that the resize reads; ``swap_rb`` of the source keeps its meaning.  Such a stylizer takes YCbCr frames only.  With
 ``yuv_out=dict(sampling=, siting=, matrix=, full_range=, components=3)`` (not together with ``jpeg=``) the pass ends with fs_rgb_to_yuv_u8 on the u8
 frame and the stylizer returns the planes, a uint8 array of frame_bytes, instead of the pixels.
+
+Deep video: either dict takes ``bits=N``, 9 to 16 bits per sample in little-endian 16-bit words (y4m.Reader(f, deep=True)); the frames are
+still flat uint8 arrays of frame_bytes, now two bytes per sample (an array of ``<u2`` samples is taken as well).  A deep source writes the
+net's fp32 input directly (fs_yuv_deep_to_f32, csrc/fs_yuv16.hip) and the pass has no fs_u8_to_f32; a deep ``yuv_out`` reads the net's fp32
+output directly (fs_f32_to_yuv_deep) and the pass has no fs_f32_to_u8: no u8 stage on that side.  Either end may be deep on its own, with
+the 8-bit kernels on the other.  A deep source has the net's size (the resize is u8 only); ``jpeg=`` behind a deep source works as before.
 """
 import ctypes
 
@@ -79,6 +85,7 @@ class FrameStylizer(object):
         if jpeg is not None:
             self._jpeg_setup(dict(jpeg), int(jpeg_threads))
         self.yuv_out = None
+        self._out_deep = False           # yuv_out= with bits above 8: the conversion reads the net's fp32 output itself
         self.yuv_out_desc = None         # with yuv_out=: the fs_yuv_desc of an output frame (what a y4m.Writer takes)
         self._result = self._out_u8      # the device buffer __call__ downloads (without jpeg=)
         if yuv_out is not None:
@@ -93,10 +100,11 @@ class FrameStylizer(object):
         self._graph_jpeg = None
         self._src_host = None
         self._src_yuv = None
+        self._src_deep = False           # source yuv= with bits above 8: the conversion writes the net's fp32 input itself
         if source is not None:
             self._source_setup(dict(source))
 
-    YUV_KEYS = ("sampling", "siting", "matrix", "full_range", "components")
+    YUV_KEYS = ("sampling", "siting", "matrix", "full_range", "components", "bits")
 
     def _yuv_desc(self, opt, width, height, what):
         """The fs_yuv_desc of a yuv= / yuv_out= dict at a frame size; unknown keys raise."""
@@ -111,6 +119,7 @@ class FrameStylizer(object):
         B, Ho, Wo, _ = self.out_shape
         self.yuv_out_desc, kw = self._yuv_desc(opt, Wo, Ho, "yuv_out")
         self.yuv_out = kw
+        self._out_deep = int(self.yuv_out_desc.reserved[0]) != 0
         self._result = self.eng.mem.upload_u8(np.zeros((B, int(self.yuv_out_desc.frame_bytes)), np.uint8))
 
     def _source_setup(self, opt):
@@ -132,6 +141,10 @@ class FrameStylizer(object):
             if jp is not None:
                 raise L.FaststyleError("source jpeg= and yuv= are mutually exclusive: the frames of a stylizer have one form")
             self._src_yuv, self.source["yuv"] = self._yuv_desc(yuv, Ws, Hs, "source yuv")
+            self._src_deep = int(self._src_yuv.reserved[0]) != 0
+            if self._src_deep and (Hs, Ws) != (H, W):
+                raise L.FaststyleError("a source of %d bits per sample has the net's size %dx%d, got %dx%d: the resize takes 8-bit frames only" %
+                                       (self._src_yuv.reserved[0], H, W, Hs, Ws))
             self.in_shape = (B, int(self._src_yuv.frame_bytes))
             self._pix_dst = mem.upload_u8(np.zeros(self.in_shape, np.uint8))             # the planes as uploaded
             if (Hs, Ws) != (H, W):                                                      # (a swap alone is the conversion's own)
@@ -248,16 +261,22 @@ class FrameStylizer(object):
             else:
                 e.jpeg_reconstruct_many(self._src_coef, self._sitems, self._in_u8, items_dev=(self._sitems_dev, 0))
         elif self._src_yuv is not None:                      # the planes of the frame(s) are in self._pix_dst
-            if self._src_plan is not None:
+            if self._src_deep:                               # 16-bit samples: straight to the net's fp32 input
+                e.yuv_deep_to_f32(self._pix_dst, self._src_yuv, self._in_f32, swap_rb=self._src_swap)
+            elif self._src_plan is not None:
                 e.yuv_to_rgb_u8(self._pix_dst, self._src_yuv, self._src_rgbx)
                 e.cvresize_u8(self._src_rgbx, self._src_plan, self._in_u8, swap_rb=self._src_swap)
             else:
                 e.yuv_to_rgb_u8(self._pix_dst, self._src_yuv, self._in_u8, swap_rb=self._src_swap)
         elif self._src_plan is not None:                     # source pixels are in self._pix_dst
             e.cvresize_u8(self._pix_dst, self._src_plan, self._in_u8, swap_rb=self._src_swap)
-        e.u8_to_f32(self._in_u8, self._in_f32)
+        if not self._src_deep:                               # (a deep source has written self._in_f32 itself)
+            e.u8_to_f32(self._in_u8, self._in_f32)
         self._y = e.tnet_forward(self.variables, self._in_f32, upsample_method=self.method, bf16=self.bf16, frozen=True,   # one checkpoint, many frames
                                  workspace=self._ws)
+        if self._out_deep:                                   # 16-bit samples: straight from the net's fp32 output
+            e.f32_to_yuv_deep(self._y, self.yuv_out_desc, self._result, swap_rb=self.swap_rb)
+            return
         e.f32_to_u8(self._y, self._out_u8, swap_rb=self.swap_rb)
         if self.jpeg is not None:
             e.jpeg_forward_many(self._out_u8, self._jitems, self._coef, items_dev=(self._jitems_dev, 0))
@@ -320,6 +339,22 @@ class FrameStylizer(object):
         except Exception:
             pass
 
+    def net_input(self):
+        """For tests and inspection: a host float32 copy [B,H,W,3] of the net's input tensor as the last pass left it (synchronises)."""
+        return np.array(self.eng.mem.to_numpy(self._in_f32), dtype=np.float32, copy=True)
+
+    def net_output(self):
+        """For tests and inspection: a host float32 copy [B,Ho,Wo,3] of the net's output tensor of the last pass (synchronises)."""
+        if self._y is None:
+            raise L.FaststyleError("net_output: this stylizer has not run a frame yet")
+        return np.array(self.eng.mem.to_numpy(self._y), dtype=np.float32, copy=True).reshape(self.out_shape)
+
+    def as_planes(self, a):
+        """A frame of a deep source given as 16-bit samples -> the bytes the stylizer takes (anything else: as it is)."""
+        if self._src_deep and a.dtype == np.uint16:
+            return np.ascontiguousarray(a, dtype="<u2").view(np.uint8)
+        return a
+
     def __call__(self, frames_u8):
         """frames_u8: host uint8 [H,W,3] (or [B,H,W,3]) -> host uint8 stylized frame(s) of the net's output size; with jpeg=: the bytes of
         its JPEG file (a list of them for a batch); with yuv_out=: its planes, uint8 [frame_bytes] (or [B, frame_bytes]).  With source=: the
@@ -332,7 +367,7 @@ class FrameStylizer(object):
             self._upload_jpeg(self.decode_frames(files, self._src_host))       # (raises FrameNotTaken before anything is enqueued)
             self._run(True)
         else:
-            a = np.asarray(frames_u8)
+            a = self.as_planes(np.asarray(frames_u8))
             single = a.ndim == len(self.in_shape) - 1                # ([H,W,3] pixels, or with source yuv= the flat planes of one frame)
             if single:
                 a = a[np.newaxis]
@@ -381,7 +416,8 @@ class PipelinedStylizer(object):
     device (fs_jpeg_write holds no interpreter lock).  fetch() / run() then give bytes, in submission order.
 
     source yuv= and yuv_out= (raw video, see the module docstring) pass through to the lanes: the planes go up from and come down into the
-    lanes' pinned buffers; order and depth are unchanged.  next_input() lends the next lane's pinned input buffer to a stream reader."""
+    lanes' pinned buffers, which are sized from the descriptors' frame_bytes (two bytes per sample with bits=N); order and depth are unchanged.
+    next_input() lends the next lane's pinned input buffer to a stream reader."""
 
     def __init__(self, eng, variables, height, width, depth=2, jpeg_threads=4, **kw):
         if not hasattr(eng.mem, "torch"):
@@ -434,7 +470,7 @@ class PipelinedStylizer(object):
             single = not isinstance(frames_u8, (list, tuple))
             staged = _decoded if _decoded is not None else self._decode(files, self._n)      # (FrameNotTaken: nothing is enqueued)
         else:
-            a = np.asarray(frames_u8)
+            a = ln.as_planes(np.asarray(frames_u8))
             single = a.ndim == len(ln.in_shape) - 1
             if single:
                 a = a[np.newaxis]

@@ -327,7 +327,7 @@ typedef struct fs_yuv_desc {
     int32_t matrix;                    /* 0 BT.601, 1 BT.709 */
     int32_t full_range;                /* 0: Y 16..235, chroma 16..240; 1: 0..255 */
     int32_t chroma_w, chroma_h;        /* ceil(width / hs), ceil(height / vs); 0 for mono */
-    int32_t reserved[2];
+    int32_t reserved[2];               /* 0, 0; fs_yuv_plan_deep: reserved[0] = bits per sample */
     uint64_t plane_offset[3];          /* within a frame, bytes */
     uint64_t plane_bytes[3];
     uint64_t frame_bytes;
@@ -348,6 +348,58 @@ int fs_yuv_to_rgb_u8(fs_ctx* ctx, const fs_yuv_desc* desc, const void* yuv, int 
 /* The reverse: N images of pixel_bytes bytes per pixel at rgb (the fourth byte never read; swap_rb != 0: the source pixels are B,G,R) -> N
  * frames at yuv.  As fs_yuv_to_rgb_u8 in every other respect, error codes included. */
 int fs_rgb_to_yuv_u8(fs_ctx* ctx, const fs_yuv_desc* desc, const unsigned char* rgb, int pixel_bytes, int swap_rb, int N, void* yuv);
+
+/* ---- Planar YCbCr frames of 9 to 16 bits per sample <-> the net's fp32 tensors (csrc/fs_yuv16.hip): deep video (C420p10, C422p10, C444p12,
+ * C420p16, Cmono16 ... of YUV4MPEG2) goes straight to the transformation net's [N, H, W, 3] fp32 input, and the net's fp32 output straight to
+ * such planes, one kernel each way and no u8 stage on either side.  A host-only plan and two asynchronous device calls.  The arithmetic below
+ * is the contract (tests/test_yuv_deep.py restates it in numpy and compares exactly); it is integer throughout.
+ *
+ * Samples: d = bits per sample, 9 <= d <= 16; k = d - 8, m = 2^d - 1.  A sample is an unsigned little-endian 16-bit word; a stored value above
+ * m is read as m.  No sample value reaches an address.
+ *
+ * Layout: that of the 8-bit frames above with two bytes per sample: Y, Cb, Cr back to back, chroma ceil(width / hs) x ceil(height / vs), a mono
+ * frame its Y plane alone.
+ *
+ * RGB scale: RGB lives on the net's 0..255 scale in unsigned 8.8 fixed point: an integer F in [0, 65280], value F / 256.
+ *
+ * Chroma resampling: exactly the integer formulas stated above for the 8-bit frames -- the same taps, clamping, rounding and siting rules --
+ * applied to the d-bit values.  Every sum fits int32.
+ *
+ * Scale factors and offsets: (Kr, Kb) as above, Kg = 1 - Kr - Kb.  Limited range: sy = 65280 / (219 * 2^k), sc = 65280 / (224 * 2^k),
+ * oy = 16 * 2^k.  Full range: sy = sc = 65280 / m, oy = 0.  The chroma offset is 2^(d-1) in both.  A mono frame reads as Cb = Cr = 2^(d-1).
+ *
+ * Planes -> RGB: the real formulas of the 8-bit contract,
+ *   R = sy (Y - oy) + 2 (1 - Kr) sc (Cr - 2^(d-1))
+ *   B = sy (Y - oy) + 2 (1 - Kb) sc (Cb - 2^(d-1))
+ *   G = sy (Y - oy) - 2 (1 - Kb) Kb / Kg sc (Cb - 2^(d-1)) - 2 (1 - Kr) Kr / Kg sc (Cr - 2^(d-1))
+ * with these sy, sc, oy, each coefficient c replaced by floor(c * 2^24 + 0.5) (d = 10, limited range: 1250247329 for sy), the sum in int64, plus
+ * 2^23, arithmetic shift right by 24, clamped to [0, 65280]: that is F.  The net's input is (float)F * 0.00390625f, which is exact (a power of
+ * two, F < 2^24).  Channel order R,G,B, or B,G,R with swap_rb.
+ *
+ * Net output -> planes: for each channel q = the float clamped to [0, 255], NaN -> 0; F = (int)(q * 256.0f) -- the product is exact, the
+ * conversion truncates: numpy's astype carried to 8.8, so that F >> 8 is what fs_f32_to_u8 writes.  Y, Cb, Cr per pixel come from the rows
+ * (Kr, Kg, Kb) / sy, (-Kr, -Kg, 1 - Kb) / (2 (1 - Kb)) / sc and (1 - Kr, -Kg, -Kb) / (2 (1 - Kr)) / sc applied to (F_R, F_G, F_B) with the
+ * sy, sc above: coefficients floor(c * 2^24 + 0.5), int64 sums, the offset (oy, 2^(d-1), 2^(d-1)) added as offset << 24, plus 2^23, shift
+ * right by 24, clamped to [0, m].  The per-pixel d-bit chroma is downsampled with the integer formulas above.
+ *
+ * Both directions are within 1 unit of floor(exact + 0.5) of the float64 formulas and equal to it in over 99.8 % of random samples; every
+ * intermediate sum stays below 2^42. */
+
+/* Fills *desc as fs_yuv_plan does, with every byte size and offset doubled and reserved[0] = bits.  Host only: no HIP call, no global state,
+ * no allocation.  Errors: those of fs_yuv_plan, and -2 for bits outside [9, 16] (8 is not deep: fs_yuv_plan).  fs_yuv_to_rgb_u8 and
+ * fs_rgb_to_yuv_u8 refuse such a desc with -1, as the two calls below refuse one of fs_yuv_plan. */
+int fs_yuv_plan_deep(int width, int height, int hs, int vs, int ncomp, int siting, int matrix, int full_range, int bits, fs_yuv_desc* desc);
+
+/* N frames at yuv, desc->frame_bytes apart -> [N, height, width, 3] fp32 at dst on the net's 0..255 scale (swap_rb != 0: written B,G,R).
+ * Asynchronous on the ctx stream, allocates nothing, can be captured into a hipGraph; grid.y is the image.  A refused call launches nothing.
+ * Errors: -1 null argument / N outside [1, 65535] / a desc that fs_yuv_plan_deep does not reproduce byte for byte, -5 yuv not 2-byte aligned
+ * (a width that is a multiple of 4 with frames of a multiple of 8 bytes, yuv 8-byte and dst 16-byte aligned takes 8- and 16-byte accesses,
+ * anything else single samples and floats, with the same values). */
+int fs_yuv_deep_to_f32(fs_ctx* ctx, const fs_yuv_desc* desc, const void* yuv, int N, int swap_rb, float* dst);
+
+/* The reverse: [N, height, width, 3] fp32 at src (swap_rb != 0: the source channels are B,G,R) -> N frames at yuv.  As fs_yuv_deep_to_f32 in
+ * every other respect, error codes included. */
+int fs_f32_to_yuv_deep(fs_ctx* ctx, const fs_yuv_desc* desc, const float* src, int swap_rb, int N, void* yuv);
 
 #ifdef __cplusplus
 }

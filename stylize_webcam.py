@@ -20,6 +20,9 @@ speak on pipes; ``-`` is standard input / output:
 Chroma resampling and the YCbCr <-> RGB matrix (``--video_matrix``, BT.601 by default) run on the device inside each lane's graph; the host reads a
 frame's planes into pinned memory and writes the result's planes, nothing else.  The output stream has the input's frame rate, aspect, sampling,
 siting and range at the net's output size.  ``--video_in`` without ``--video_out`` writes 000000.png, 000001.png ... (or .jpg) to --output_dir.
+Deep video: ``--video_depth stream`` takes the stream at its own depth (C420p10, C422p10, C444p12 ... up to 16 bits; the default ``8`` refuses
+them) and ``--video_out_depth N`` writes N bits (default: the input's); above 8 bits the planes go straight to and from the net's fp32 tensors,
+without a u8 stage on that side.  ``--frame_size`` does not take a deep input.
 """
 import os
 import sys
@@ -170,15 +173,23 @@ def run_video(args):
     fout = None
     try:
         try:
-            reader = y4m.Reader(fin)
+            reader = y4m.Reader(fin, deep=args.video_depth == 'stream')
         except y4m.Y4MError as e:
             raise SystemExit('--video_in %s: %s' % (args.video_in, e))
         fmt = reader.format
         Ws, Hs = fmt.width, fmt.height
         colour = dict(sampling=fmt.sampling, siting=fmt.siting, matrix=args.video_matrix, full_range=fmt.full_range, components=fmt.components)
+        colour_in = dict(colour, bits=fmt.bits) if fmt.bits != 8 else colour       # (an 8-bit stream runs exactly as without --video_depth)
+        out_bits = fmt.bits if args.video_out_depth is None else args.video_out_depth
+        colour_out = dict(colour, bits=out_bits) if out_bits != 8 else colour
+        if fmt.bits != 8 and args.frame_size is not None:
+            raise SystemExit('--video_in %s: --frame_size does not take a stream of %d bits per sample: the resize is 8-bit only' %
+                             (args.video_in, fmt.bits))
         try:
-            engine.YuvHost().yuv_plan(Ws, Hs, **colour)                      # (a frame the kernels do not take: said before the model is loaded)
-        except _lib.FaststyleError as e:
+            engine.YuvHost().yuv_plan(Ws, Hs, **colour_in)                   # (a frame the kernels do not take: said before the model is loaded)
+            if args.video_out is not None and out_bits != 8:
+                y4m.header(Ws, Hs, fmt.sampling, fmt.siting, fmt.components, fmt.full_range, bits=out_bits)    # (a layout without a deep tag)
+        except (_lib.FaststyleError, y4m.Y4MError) as e:
             raise SystemExit('--video_in %s: %s' % (args.video_in, e))
         W, H = args.frame_size if args.frame_size is not None else (Ws, Hs)
         say('Resolution is: {0} by {1}'.format(W, H))
@@ -186,10 +197,10 @@ def run_video(args):
         eng, variables = _load(args)
         # The channel quirk as in run_frames_dir: the net sees B,G,R (source swap_rb, what a cv2 capture delivers) and the output is swapped back --
         # which is the frame of a lane that does not swap, so the lanes of a video or .jpg output are built with swap_rb=False.
-        kw = dict(source=dict(height=Hs, width=Ws, swap_rb=True, yuv=colour))
+        kw = dict(source=dict(height=Hs, width=Ws, swap_rb=True, yuv=colour_in))
         jpg = args.video_out is None and args.output_format == 'jpg'
         if args.video_out is not None:
-            kw.update(swap_rb=False, yuv_out=colour)
+            kw.update(swap_rb=False, yuv_out=colour_out)
         elif jpg:
             kw.update(swap_rb=False, jpeg=dict(quality=args.output_quality, subsampling=2))
         depth = int(os.environ.get('FS_FRAMES_IN_FLIGHT', '2')) if hasattr(eng.mem, 'torch') else 1

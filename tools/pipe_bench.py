@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the TFRecord input pipeline alone (decode threads + GPU resize + HBM shuffle queue) on
-synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode | frames_in | video]
+synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode | frames_in | video [out.json [depth]]]
 "frames_in": the frames-dir loop end to end (stylize_webcam.run_frames_dir, two frames in flight, --output_format jpg) at 720p over a directory of
 n JPEG frames: PIL decode against --input_decode native, and from 1080p sources PIL decode + PIL resize (--resolution) against native decode +
 device resize (--frame_size).  Every leg runs on the same device, legs alternate over the repeats, and a leg's rate is taken from the DIFFERENCE
@@ -9,6 +9,10 @@ profiles/frames_in.json (or to the file named as a fourth argument).
 "video": the frames_in legs and, beside them in the same run with the same repeat and median scheme, the raw-video loop (stylize_webcam.run_video:
 --video_in / --video_out, 720p 4:2:0 YUV4MPEG2 from a file to a file, the same 16 frames as planes, the same frame counts); written to profiles/video_stream.json.  The video loop is several times faster than the
 others: give it enough frames (1280) that its timed difference is about a second.
+"video" with a depth as the fifth argument (pipe_bench.py 1280 4 video profiles/video_deep.json 10): only the raw-video loop, as two legs that
+alternate in the one run -- the 8-bit stream above and the same frames as a stream of that many bits per sample (C420p10 ..., --video_depth
+stream, two bytes per sample in and out) -- plus the device time of one 720p launch of the two deep kernels and of the 8-bit kernel pairs they
+replace (HIP events around the replay of a graph of 200 launches each); written to profiles/video_deep.json with the digest of the kernel sources.
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -81,9 +85,52 @@ def host_encode(n, th):
     return res
 
 
-def frames_in(n, repeats=3, out_json=None, video=False):
+def kernel_times(bits, W=1280, H=720, launches=200):
+    """-> dict of device microseconds per 720p 4:2:0 launch (HIP events around the replay of a graph that holds `launches` of them, after a warm-up): the two deep
+    kernels, and the 8-bit conversions with the u8 <-> f32 launches of a lane beside them."""
+    import torch
+    eng = engine.Engine()
+    mem = eng.mem
+    d8, dd = eng.yuv_plan(W, H, full_range=True), eng.yuv_plan(W, H, full_range=True, bits=bits)
+    rng = np.random.default_rng(1)
+    p8 = mem.upload_u8(rng.integers(0, 256, (1, int(d8.frame_bytes)), dtype=np.uint8))
+    pd = mem.upload_u8(rng.integers(0, 2 ** bits, (1, int(dd.frame_bytes) // 2)).astype("<u2").view(np.uint8))
+    u8 = mem.upload_u8(np.zeros((1, H, W, 3), np.uint8))
+    f32 = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+
+    def timed(fn):
+        # the launches are captured into one graph and the replay is timed: launched one by one from Python they would measure the interpreter
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            fn()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            for _ in range(launches):
+                fn()
+        g.replay()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        g.replay()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3 / launches
+
+    res = {"yuv_deep_to_f32": timed(lambda: eng.yuv_deep_to_f32(pd, dd, f32, swap_rb=True)),
+           "yuv_to_rgb_u8_then_u8_to_f32": timed(lambda: (eng.yuv_to_rgb_u8(p8, d8, u8, swap_rb=True), eng.u8_to_f32(u8, f32))),
+           "f32_to_yuv_deep": timed(lambda: eng.f32_to_yuv_deep(f32, dd, pd)),
+           "f32_to_u8_then_rgb_to_yuv_u8": timed(lambda: (eng.f32_to_u8(f32, u8), eng.rgb_to_yuv_u8(u8, d8, p8)))}
+    for k, v in res.items():
+        print("video: %8.1f us per 720p launch: %s" % (v, k))
+    return res
+
+
+def frames_in(n, repeats=3, out_json=None, video=False, depth=None):
     """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json (video: with the raw-video leg, to
-    profiles/video_stream.json)."""
+    profiles/video_stream.json; video with a depth: the 8-bit and the deep raw-video legs alone, to profiles/video_deep.json)."""
     import contextlib
     import json
     import shutil
@@ -97,8 +144,11 @@ def frames_in(n, repeats=3, out_json=None, video=False):
     base = rng.integers(0, 256, (135, 240, 3), dtype=np.uint8)
     dirs = {}
     for tag, (w, h) in (("720p", (1280, 720)), ("1080p", (1920, 1080))):
+        if depth and tag != "720p":          # (the two video legs alone: no 1080p sources, no directories of JPEG frames)
+            continue
         files = []
         planes = []
+        deep_planes = []
         for k in range(16):      # 16 distinct natural-ish frames (upsampled noise), reused
             buf = io.BytesIO()
             im = Image.fromarray(np.roll(base, 5 * k, axis=1)).resize((w, h), Image.BICUBIC)
@@ -109,7 +159,10 @@ def frames_in(n, repeats=3, out_json=None, video=False):
                 sub = (ycc[0::2, 0::2, 1:] + ycc[0::2, 1::2, 1:] + ycc[1::2, 0::2, 1:] + ycc[1::2, 1::2, 1:] + 2) >> 2
                 planes.append(b"FRAME\n" + ycc[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 0].astype(np.uint8).tobytes() +
                               sub[:, :, 1].astype(np.uint8).tobytes())
-        for count in (n, n // 4):
+                if depth:                    # ... and as samples of `depth` bits: the 8-bit value's bits repeated below it, so that the low bits are used
+                    deep = [((p.astype(np.uint32) * 257) >> (16 - depth)).astype("<u2") for p in (ycc[:, :, 0], sub[:, :, 0], sub[:, :, 1])]
+                    deep_planes.append(b"FRAME\n" + b"".join(p.tobytes() for p in deep))
+        for count in () if depth else (n, n // 4):
             p = os.path.join(d, "%s_%d" % (tag, count))
             os.makedirs(p)
             for k in range(count):
@@ -121,6 +174,11 @@ def frames_in(n, repeats=3, out_json=None, video=False):
                 f.write(b"YUV4MPEG2 W%d H%d F30:1 Ip A1:1 C420jpeg XCOLORRANGE=FULL\n" % (w, h))
                 for k in range(count):
                     f.write(planes[k % 16])
+            if deep_planes:
+                with open(os.path.join(d, "%s_%d_p%d.y4m" % (tag, count, depth)), "wb") as f:
+                    f.write(b"YUV4MPEG2 W%d H%d F30:1 Ip A1:1 C420p%d XCOLORRANGE=FULL\n" % (w, h, depth))
+                    for k in range(count):
+                        f.write(deep_planes[k % 16])
         print("frames_in: %s sources, %.0f KB/file" % (tag, np.mean([len(f) for f in files]) / 1e3))
     legs = [("pil_decode_720p", "720p", []),
             ("native_decode_720p", "720p", ["--input_decode", "native"]),
@@ -129,24 +187,27 @@ def frames_in(n, repeats=3, out_json=None, video=False):
             ("pil_decode_device_resize_1080p_to_720p", "1080p", ["--frame_size", "1280", "720"])]
     if video:
         legs.append(("video_y4m_720p", "720p", None))
+    if depth:
+        legs = [("video_y4m_720p", "720p", None), ("video_y4m_720p_%dbit" % depth, "720p", depth)]
     parser = stylize_webcam.setup_parser()
     out = os.path.join(d, "out")
 
-    def run_stream(tag, count):
-        """the raw-video loop over count frames, file to file"""
-        args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--video_in", os.path.join(d, "%s_%d.y4m" % (tag, count)),
-                                  "--video_out", out + ".y4m"])
+    def run_stream(tag, count, bits=None):
+        """the raw-video loop over count frames, file to file (bits: the deep stream, taken and written at its own depth)"""
+        src = "%s_%d_p%d.y4m" % (tag, count, bits) if bits else "%s_%d.y4m" % (tag, count)
+        args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--video_in", os.path.join(d, src),
+                                  "--video_out", out + ".y4m"] + (["--video_depth", "stream"] if bits else []))
         with contextlib.redirect_stdout(io.StringIO()):
             t0 = time.time()
             stylize_webcam.run_video(args)
             dt = time.time() - t0
-        assert os.path.getsize(out + ".y4m") > count * 1280 * 720 * 3 // 2
+        assert os.path.getsize(out + ".y4m") > count * 1280 * 720 * 3 // 2 * (2 if bits else 1)
         os.remove(out + ".y4m")
         return dt
 
     def run(tag, count, flags):
-        if flags is None:
-            return run_stream(tag, count)
+        if flags is None or isinstance(flags, int):
+            return run_stream(tag, count, flags)
         args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--frames_dir", dirs[tag, count],
                                   "--output_dir", out, "--output_format", "jpg"] + flags)
         with contextlib.redirect_stdout(io.StringIO()):
@@ -157,7 +218,7 @@ def frames_in(n, repeats=3, out_json=None, video=False):
         shutil.rmtree(out)
         return dt
 
-    run("720p", n // 4, [])                                       # warm-up: library load, first kernels
+    run("720p", n // 4, None if depth else [])                    # warm-up: library load, first kernels
     times = {name: [] for name, _, _ in legs}
     for _ in range(repeats):                                      # legs alternate: a drifting clock touches all of them alike
         for name, tag, flags in legs:
@@ -168,12 +229,21 @@ def frames_in(n, repeats=3, out_json=None, video=False):
            "method": "rate = (n - n/4) / (t(n) - t(n/4)), median of %d alternating repeats" % repeats, "legs": {}}
     if video:
         res["video"] = "720p 4:2:0 YUV4MPEG2 (full range, BT.601), file to file; 1 driver thread, no decode / encode threads"
+    if depth:
+        res["output"] = "YUV4MPEG2 at the input's depth"
+        res["host_threads"] = "1 driver"
+        res["deep_bits"] = depth
+        res["bytes_per_frame_in_and_out"] = {"video_y4m_720p": 1280 * 720 * 3 // 2, "video_y4m_720p_%dbit" % depth: 1280 * 720 * 3}
+        from faststyle_amd import build as fsbuild
+        res["source_digest"] = fsbuild.source_digest()
     for name, _, _ in legs:
         rates = sorted((n - n // 4) / (a - b) for a, b in times[name])
         res["legs"][name] = {"frames_per_s": rates[len(rates) // 2], "all_repeats": rates, "seconds_n_and_quarter": times[name]}
         print("frames_in: %7.0f frames/s %s (repeats: %s)" % (rates[len(rates) // 2], name, ", ".join("%.0f" % r for r in rates)))
     shutil.rmtree(d)
-    dst = out_json or os.path.join(root, "profiles", "video_stream.json" if video else "frames_in.json")
+    if depth:
+        res["kernel_us_per_720p_launch"] = kernel_times(depth)
+    dst = out_json or os.path.join(root, "profiles", "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
     with open(dst, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
@@ -185,7 +255,8 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     threads = int(sys.argv[2]) if len(sys.argv) > 2 else None
     if len(sys.argv) > 3 and sys.argv[3] in ("frames_in", "video"):
-        frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video")
+        depth = int(sys.argv[5]) if len(sys.argv) > 5 and sys.argv[3] == "video" else None
+        frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video", depth=depth)
         return
     if len(sys.argv) > 3 and sys.argv[3] == "host_encode":
         host_encode(n, threads or 4)
