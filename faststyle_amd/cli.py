@@ -103,4 +103,14 @@ def stylize_webcam_parser():
         ('--video_out_depth', dict(default=None, type=int, choices=list(range(8, 17)), metavar='N',
                                    help="(addition) bits per sample of --video_out, 8..16 (default: the input's); above 8 the net's fp32 output "
                                         "goes to the planes without a u8 stage")),
+        ('--style_strength', dict(default=None, type=float, metavar='S',
+                                  help="(addition) blend every stylized frame back towards its source on the device: 0 the source, 1 the net's "
+                                       "output (default: no such stage); with --frames_dir, --video_in and the camera, every input and output flag")),
+        ('--preserve_color', dict(action='store_true',
+                                  help="(addition) keep the source's colours and take the stylized luminance only (alone: at strength 1)")),
+        ('--color_matrix', dict(choices=['bt601', 'bt709'], default=None,
+                                help="(addition) luma weights of --preserve_color (default: --video_matrix with --video_in, else bt601)")),
+        ('--mask_path', dict(default=None, metavar='FILE',
+                             help="(addition) a grey image of the net's input size (after --frame_size): 0 keeps the source pixel, 255 stylizes it, "
+                                  "values between blend")),
     ])

@@ -227,6 +227,19 @@ int fs_f32_to_yuv_deep(fs_ctx* ctx, const fs_yuv_desc* desc, const float* src, i
     const int rc = fs::f32_to_yuv_deep(*desc, src, swap_rb ? 1 : 0, N, static_cast<unsigned char*>(yuv), ctx->stream);
     return rc ? fail(rc, "fs_f32_to_yuv_deep: launch failed (%d)", rc) : 0;
 }
+int fs_compose_f32(fs_ctx* ctx, const float* src, int H, int W, const float* net, int Ho, int Wo, int N, int strength_q8, int keep_color, int matrix,
+                   int bgr, const unsigned char* mask, float* dst) {
+    if (!ctx || !src || !net || !dst) return fail(-1, "fs_compose_f32: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_compose_f32: N must be in [1, 65535], got %d", N);
+    if (H < 1 || W < 1 || Ho < H || Ho - H > 3 || Wo < W || Wo - W > 3)
+        return fail(-1, "fs_compose_f32: a %dx%d source does not belong to a %dx%d net output (at least the source's size, at most 3 more)", H, W, Ho, Wo);
+    if (strength_q8 < 0 || strength_q8 > 256) return fail(-2, "fs_compose_f32: strength_q8 must be in [0, 256], got %d", strength_q8);
+    if (matrix != 0 && matrix != 1) return fail(-2, "fs_compose_f32: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
+    if (bgr < 0 || bgr > 3) return fail(-2, "fs_compose_f32: bgr must be in [0, 3] (1: channel 0 of net is blue, 2: src the other way round), got %d", bgr);
+    if (((uintptr_t)src | (uintptr_t)net | (uintptr_t)dst) & 3) return fail(-5, "fs_compose_f32: src, net and dst must be 4-byte aligned");
+    const int rc = fs::compose_f32(src, H, W, net, Ho, Wo, N, strength_q8, keep_color ? 1 : 0, matrix, bgr & 1, bgr >> 1, mask, dst, ctx->stream);
+    return rc ? fail(rc, "fs_compose_f32: launch failed (%d)", rc) : 0;
+}
 int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
                   const int32_t* move_dst, int M, float* batch_out) {
     if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");

@@ -690,6 +690,9 @@ int rgb_to_yuv_u8(const ::fs_yuv_desc& desc, const unsigned char* rgb, int pixel
 bool yuv_deep_desc_ok(const ::fs_yuv_desc& desc);
 int yuv_deep_to_f32(const ::fs_yuv_desc& desc, const unsigned char* yuv, int N, int swap_rb, float* dst, hipStream_t s);
 int f32_to_yuv_deep(const ::fs_yuv_desc& desc, const float* src, int swap_rb, int N, unsigned char* yuv, hipStream_t s);
+// the net's output blended towards its input on the 8.8 scale (fs_compose.hip): the launch (argument checks are in fs_api.hip)
+int compose_f32(const float* src, int H, int W, const float* net, int Ho, int Wo, int N, int strength_q8, int keep_color, int matrix, int bgr,
+                int src_swap, const unsigned char* mask, float* dst, hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);
 // ... with the per-sample sums taken from records [N][T][C][2] (rec == nullptr: computed here into `scratch`), reduced in the apply kernel's

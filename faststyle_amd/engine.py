@@ -927,6 +927,26 @@ class Engine(JpegHost, CvResizeHost, YuvHost):
                                                       self.mem.ptr_u8(out_dev)), "fs_f32_to_yuv_deep")
         return out_dev
 
+    # ------------------------------------------------------------------ strength, colour preservation, mask (csrc/fs_compose.hip)
+    def compose_f32(self, src, net, dst, strength_q8=256, keep_color=False, matrix="bt601", bgr=False, mask=None, src_swapped=False):
+        """fs_compose_f32: src device float32 [H,W,3] / [N,H,W,3] (the net's input), net and dst device float32 [Ho,Wo,3] / [N,Ho,Wo,3] (the
+        net's output and the composed tensor; dst may be net) -> dst = src + (net - src) * strength_q8 / 256 * mask on the 8.8 scale, under
+        keep_color with the luma delta (matrix 'bt601' / 'bt709' or 0 / 1; bgr: channel 0 of net is blue) on every channel.  mask: device
+        uint8 [H,W].  src_swapped: src holds R and B the other way round than net and is read with them exchanged (the call's bgr + 2)."""
+        self._sync_stream()
+        ss, ns = tuple(int(d) for d in src.shape), tuple(int(d) for d in net.shape)
+        if len(ss) not in (3, 4) or len(ns) != len(ss) or ss[-1] != 3 or ns[-1] != 3 or tuple(int(d) for d in dst.shape) != ns or \
+                (len(ss) == 4 and ss[0] != ns[0]) or (mask is not None and tuple(int(d) for d in mask.shape) != ss[-3:-1]):
+            raise L.FaststyleError("compose_f32: source %s / net output %s / destination %s / mask %s do not belong together" %
+                                   (ss, ns, tuple(dst.shape), None if mask is None else tuple(mask.shape)))
+        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
+        L.check(self.lib, self.lib.fs_compose_f32(self.ctx, self.mem.ptr(src), ss[-3], ss[-2], self.mem.ptr(net), ns[-3], ns[-2],
+                                                  ss[0] if len(ss) == 4 else 1, int(strength_q8), 1 if keep_color else 0, int(matrix),
+                                                  (1 if bgr else 0) + (2 if src_swapped else 0),
+                                                  None if mask is None else self.mem.ptr_u8(mask), self.mem.ptr(dst)),
+                "fs_compose_f32")
+        return dst
+
     def synth_uniform(self, out, seed, rank, batch_index):
         """Uniform [0,255) float32 values into ``out``: Philox4x32-10 keyed by seed, counter (element block, batch_index, rank) (fs_synth_uniform)."""
         self._sync_stream()

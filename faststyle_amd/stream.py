@@ -33,6 +33,15 @@ still flat uint8 arrays of frame_bytes, now two bytes per sample (an array of ``
 net's fp32 input directly (fs_yuv_deep_to_f32, csrc/fs_yuv16.hip) and the pass has no fs_u8_to_f32; a deep ``yuv_out`` reads the net's fp32
 output directly (fs_f32_to_yuv_deep) and the pass has no fs_f32_to_u8: no u8 stage on that side.  Either end may be deep on its own, with
 the 8-bit kernels on the other.  A deep source has the net's size (the resize is u8 only); ``jpeg=`` behind a deep source works as before.
+
+Strength, colour preservation, a region mask: with ``compose=dict(strength=1.0, keep_color=False, matrix='bt601', mask=None)`` one launch
+behind the forward pass (fs_compose_f32, csrc/fs_compose.hip, inside the graph) blends the net's fp32 output back towards the net's fp32
+input, which is still resident, into a tensor of the lane's own, and every output conversion above reads that tensor instead: ``strength`` in
+[0, 1] (quantised to 1 / 256), ``keep_color`` the stylized luma under the source's colours (``matrix`` names the luma weights), ``mask`` a host
+uint8 [H, W] at the net's input size, 0 keeps the source and 255 takes the blend.  The launch is told that the tensors are B,G,R exactly
+when the lane's output conversion swaps.  ``source_swapped=True`` says that the frames reach the net with R and B the other way round than
+its output is shown -- the reference's channel handling, which the command-line tools keep -- so that the source is read with the two
+exchanged and shows through in its own colours.  Without ``compose=`` nothing is allocated or launched.
 """
 import ctypes
 
@@ -60,7 +69,7 @@ class FrameStylizer(object):
     KEEP_GRAPH = False     # tests: keep the captured hipGraph_t so that its node types can be inspected
 
     def __init__(self, eng, variables, height, width, upsample_method="resize", batch=1, swap_rb=True, use_graph=True,
-                 bf16=False, jpeg=None, jpeg_threads=4, source=None, yuv_out=None):
+                 bf16=False, jpeg=None, jpeg_threads=4, source=None, yuv_out=None, compose=None):
         self.eng = eng
         self.variables = variables
         self.method = upsample_method
@@ -103,6 +112,37 @@ class FrameStylizer(object):
         self._src_deep = False           # source yuv= with bits above 8: the conversion writes the net's fp32 input itself
         if source is not None:
             self._source_setup(dict(source))
+        self.compose = None              # with compose=: dict(strength_q8=, keep_color=, matrix=, mask=, source_swapped=) as the launch takes them
+        self._composed = None            # ... and the composed tensor every output conversion then reads instead of the net's output
+        self._mask = None
+        if compose is not None:
+            self._compose_setup(dict(compose))
+
+    COMPOSE_KEYS = ("strength", "keep_color", "matrix", "mask", "source_swapped")
+
+    def _compose_setup(self, opt):
+        """The compose stage's fixed parts: the quantised strength, the mask on the device (once) and the lane's own composed tensor."""
+        kw = {k: opt.pop(k) for k in self.COMPOSE_KEYS if k in opt}
+        if opt:
+            raise L.FaststyleError("compose takes %s, got also %r" % (", ".join(self.COMPOSE_KEYS), opt))
+        try:
+            s = float(kw.get("strength", 1.0))
+        except (TypeError, ValueError):
+            raise L.FaststyleError("compose strength %r is not a number" % (kw["strength"],))
+        if not 0.0 <= s <= 1.0:                                  # (NaN fails both comparisons)
+            raise L.FaststyleError("compose strength must be in [0, 1], got %r" % s)
+        matrix = {"bt601": 0, "bt709": 1, 0: 0, 1: 1}.get(kw.get("matrix", "bt601"))
+        if matrix is None:
+            raise L.FaststyleError("compose matrix is 'bt601' or 'bt709', got %r" % (kw["matrix"],))
+        mask = kw.get("mask")
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 or mask.shape != self.shape[1:3]:
+                raise L.FaststyleError("compose mask shape %s dtype %s, the net's input takes uint8 %s" % (mask.shape, mask.dtype, self.shape[1:3]))
+            self._mask = self.eng.mem.upload_u8(mask)
+        self.compose = dict(strength_q8=int(np.floor(s * 256.0 + 0.5)), keep_color=bool(kw.get("keep_color", False)), matrix=matrix,
+                            mask=mask is not None, source_swapped=bool(kw.get("source_swapped", False)))
+        self._composed = self.eng.mem.empty(self.out_shape)
 
     YUV_KEYS = ("sampling", "siting", "matrix", "full_range", "components", "bits")
 
@@ -274,10 +314,15 @@ class FrameStylizer(object):
             e.u8_to_f32(self._in_u8, self._in_f32)
         self._y = e.tnet_forward(self.variables, self._in_f32, upsample_method=self.method, bf16=self.bf16, frozen=True,   # one checkpoint, many frames
                                  workspace=self._ws)
+        y = self._y
+        if self.compose is not None:                         # strength / colour / mask: every conversion below reads the composed tensor
+            c = self.compose                                 # (the tensors are B,G,R exactly when the output conversion swaps)
+            y = e.compose_f32(self._in_f32, self._y, self._composed, strength_q8=c["strength_q8"], keep_color=c["keep_color"], matrix=c["matrix"],
+                              bgr=self.swap_rb, mask=self._mask, src_swapped=c["source_swapped"])
         if self._out_deep:                                   # 16-bit samples: straight from the net's fp32 output
-            e.f32_to_yuv_deep(self._y, self.yuv_out_desc, self._result, swap_rb=self.swap_rb)
+            e.f32_to_yuv_deep(y, self.yuv_out_desc, self._result, swap_rb=self.swap_rb)
             return
-        e.f32_to_u8(self._y, self._out_u8, swap_rb=self.swap_rb)
+        e.f32_to_u8(y, self._out_u8, swap_rb=self.swap_rb)
         if self.jpeg is not None:
             e.jpeg_forward_many(self._out_u8, self._jitems, self._coef, items_dev=(self._jitems_dev, 0))
         if self.yuv_out is not None:
@@ -349,6 +394,15 @@ class FrameStylizer(object):
             raise L.FaststyleError("net_output: this stylizer has not run a frame yet")
         return np.array(self.eng.mem.to_numpy(self._y), dtype=np.float32, copy=True).reshape(self.out_shape)
 
+    def composed_output(self):
+        """For tests and inspection: a host float32 copy [B,Ho,Wo,3] of the composed tensor of the last pass (synchronises); a stylizer built
+        without compose= has none."""
+        if self._composed is None:
+            raise L.FaststyleError("composed_output: this stylizer was built without compose=")
+        if self._y is None:
+            raise L.FaststyleError("composed_output: this stylizer has not run a frame yet")
+        return np.array(self.eng.mem.to_numpy(self._composed), dtype=np.float32, copy=True)
+
     def as_planes(self, a):
         """A frame of a deep source given as 16-bit samples -> the bytes the stylizer takes (anything else: as it is)."""
         if self._src_deep and a.dtype == np.uint16:
@@ -417,7 +471,7 @@ class PipelinedStylizer(object):
 
     source yuv= and yuv_out= (raw video, see the module docstring) pass through to the lanes: the planes go up from and come down into the
     lanes' pinned buffers, which are sized from the descriptors' frame_bytes (two bytes per sample with bits=N); order and depth are unchanged.
-    next_input() lends the next lane's pinned input buffer to a stream reader."""
+    next_input() lends the next lane's pinned input buffer to a stream reader.  compose= passes through as well; every lane uploads the mask."""
 
     def __init__(self, eng, variables, height, width, depth=2, jpeg_threads=4, **kw):
         if not hasattr(eng.mem, "torch"):

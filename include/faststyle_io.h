@@ -401,6 +401,45 @@ int fs_yuv_deep_to_f32(fs_ctx* ctx, const fs_yuv_desc* desc, const void* yuv, in
  * every other respect, error codes included. */
 int fs_f32_to_yuv_deep(fs_ctx* ctx, const fs_yuv_desc* desc, const float* src, int swap_rb, int N, void* yuv);
 
+/* ---- Style strength, colour preservation and a region mask (csrc/fs_compose.hip): the net's fp32 output blended back towards the net's fp32
+ * input, one elementwise launch between the forward pass and whichever output conversion follows (fs_f32_to_u8, fs_jpeg_forward_many,
+ * fs_rgb_to_yuv_u8, fs_f32_to_yuv_deep: each consumes the composed tensor unchanged).  The arithmetic below is the contract
+ * (tests/test_compose.py restates it in numpy and compares exactly); it is integer throughout, on the unsigned 8.8 scale of the deep video
+ * block above, so no float tolerance and no contraction question arises.
+ *
+ * Inputs per image: src [H, W, 3] fp32, the net's input; net [Ho, Wo, 3] fp32, the net's output, H <= Ho <= H + 3 and W <= Wo <= W + 3
+ * (fs_tnet_out_shape gives Ho = 4 ceil(ceil(H / 2) / 2): the output is up to 3 rows and columns larger and aligned top-left); optionally mask
+ * [H, W] u8, shared by the N images.  Source and mask are read at (min(y, H - 1), min(x, W - 1)).  No value read from a tensor or the mask
+ * reaches an address.
+ *
+ * For output pixel (y, x) and channel c:
+ *   to 8.8     to88(v): q = v clamped to [0, 255], NaN -> 0; (int)(q * 256.0f) -- exactly fs_f32_to_yuv_deep's conversion.
+ *              A_c = to88(src), B_c = to88(net).
+ *   luma       (kr, kg, kb) = (19595, 38470, 7471) for BT.601, (13933, 46871, 4732) for BT.709; each triple sums to 65536.
+ *              L(X) = (kr X_R + kg X_G + kb X_B + 32768) >> 16, in int64.  bgr 1: channel 0 is blue (the meaning of swap_rb in
+ *              fs_f32_to_yuv_deep: "the source channels are B,G,R").
+ *   orders     bgr 0 and 1 take src and net in one channel order.  The frame tools keep the reference's channel handling -- the net is FED
+ *              B,G,R and its output is SHOWN as R,G,B -- so there the source must be read the other way round to show through in its own
+ *              colours: bgr + 2 (2: net R,G,B and src B,G,R; 3: net B,G,R and src R,G,B) reads src with channels 0 and 2 exchanged, A_c =
+ *              to88(src channel 2 - c), and is bgr in every other respect.
+ *   delta      plain: D_c = B_c - A_c.  keep_color: D_c = L(B) - L(A) for the three channels -- one delta added to R, G and B moves Y by
+ *              that delta and leaves Cb and Cr where they were, so no YCbCr round trip is needed and the result holds for every output kind.
+ *   weight     m = the mask byte, 255 without a mask; m' = m + (m >> 7), in 0..256 with 255 -> 256; w = strength_q8 * m', in [0, 65536].
+ *   result     F_c = clamp(A_c + (((int64)D_c * w + 32768) >> 16), 0, 65280), the shift arithmetic (a floor); the output is
+ *              (float)F_c * 0.00390625f, which is exact.
+ * Hence: strength_q8 256 without a mask in plain mode gives F = B, and a u8 / JPEG / 8-bit YCbCr conversion behind it writes byte for byte
+ * what it writes for the net's tensor (F >> 8 is what fs_f32_to_u8 writes); strength_q8 0 or a mask byte 0 gives F = A; net == src (bgr 0 or 1) gives
+ * F = A in every mode; under keep_color, where no clamp acts, F_c - F_c' = A_c - A_c' for every channel pair. */
+
+/* N images: src [N, H, W, 3], net [N, Ho, Wo, 3], mask [H, W] or null, dst [N, Ho, Wo, 3]; dst may be net (a thread reads its pixels before it
+ * writes them).  matrix: 0 BT.601, 1 BT.709, as in fs_yuv_plan.  Asynchronous on the ctx stream, allocates nothing, can be captured into a
+ * hipGraph; grid.y is the image.  A refused call launches nothing.  Errors: -1 null src / net / dst, N outside [1, 65535], H or W below 1, Ho
+ * outside [H, H + 3] or Wo outside [W, W + 3]; -2 strength_q8 outside [0, 256], a matrix other than 0 or 1, bgr outside [0, 3]; -5 src, net or dst not 4-byte
+ * aligned (W == Wo a multiple of 4 with the three tensors 16-byte aligned takes 16-byte accesses, and a 4-byte aligned mask dwords; anything
+ * else single floats and bytes, with the same values). */
+int fs_compose_f32(fs_ctx* ctx, const float* src, int H, int W, const float* net, int Ho, int Wo, int N, int strength_q8, int keep_color,
+                   int matrix, int bgr, const unsigned char* mask, float* dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,12 @@ siting and range at the net's output size.  ``--video_in`` without ``--video_out
 Deep video: ``--video_depth stream`` takes the stream at its own depth (C420p10, C422p10, C444p12 ... up to 16 bits; the default ``8`` refuses
 them) and ``--video_out_depth N`` writes N bits (default: the input's); above 8 bits the planes go straight to and from the net's fp32 tensors,
 without a u8 stage on that side.  ``--frame_size`` does not take a deep input.
+
+How much of the style lands: ``--style_strength S`` (0 the source, 1 the net's output) blends every stylized frame back towards its source,
+``--preserve_color`` keeps the source's colours under the stylized luminance (``--color_matrix`` names the luma weights; the default is
+--video_matrix with --video_in, else bt601), and ``--mask_path FILE`` (a grey image of the net's input size: 0 keeps the source pixel, 255
+stylizes it) restricts either to a region -- one more launch inside each lane's graph, on the net's fp32 tensors (faststyle_amd/stream.py,
+compose=), with every input and output flag above.  Without any of the four nothing changes; ``--style_strength 1`` alone writes the same bytes.
 """
 import os
 import sys
@@ -46,6 +52,34 @@ def _load(args):
     return eng, variables
 
 
+def compose_options(args, matrix='bt601'):
+    """--style_strength / --preserve_color / --color_matrix / --mask_path -> the compose= dict of the lanes (faststyle_amd/stream.py), None when
+    none of them is given; matrix: what --color_matrix defaults to.  A strength outside [0, 1] or an unreadable mask is a SystemExit here,
+    before anything is loaded.  Every path of this script feeds the net B,G,R and shows its output as R,G,B (the reference's channel
+    handling, kept as it is): the stage is told so (source_swapped) and the source shows through in its own colours; the lanes of a run with
+    the stage do not swap on the way out, and the host swaps where a lane without it would have."""
+    if args.style_strength is None and not args.preserve_color and args.color_matrix is None and args.mask_path is None:
+        return None
+    s = 1.0 if args.style_strength is None else args.style_strength
+    if not 0.0 <= s <= 1.0:
+        raise SystemExit('--style_strength %r is outside [0, 1]' % s)
+    opt = dict(strength=s, keep_color=args.preserve_color, matrix=args.color_matrix or matrix, source_swapped=True)
+    if args.mask_path is not None:
+        from PIL import Image
+        try:
+            opt['mask'] = np.array(Image.open(args.mask_path).convert('L'), dtype=np.uint8)
+        except (IOError, OSError) as e:
+            raise SystemExit('--mask_path %s: %s' % (args.mask_path, e))
+    return opt
+
+
+def check_mask_size(args, compose, W, H):
+    """SystemExit unless the mask (if any) has the net's input size W x H."""
+    if compose is not None and 'mask' in compose and compose['mask'].shape != (H, W):
+        raise SystemExit('--mask_path %s is %d by %d, the net takes frames of %d by %d' %
+                         ((args.mask_path,) + compose['mask'].shape[::-1] + (W, H)))
+
+
 def run_frames_dir(args):
     from PIL import Image
     from faststyle_amd import stream
@@ -54,6 +88,13 @@ def run_frames_dir(args):
     names = sorted(f for f in os.listdir(args.frames_dir) if f.lower().endswith(('.jpg', '.jpeg', '.png')))
     if not names:
         raise SystemExit('no frames under %s' % args.frames_dir)
+    compose = compose_options(args)
+    if compose is not None and 'mask' in compose:                # (the first frame's size, before the model is loaded; later sizes: build())
+        size = args.frame_size or args.resolution
+        if size is None:
+            with Image.open(os.path.join(args.frames_dir, names[0])) as im:
+                size = im.size
+        check_mask_size(args, compose, *size)
     eng, variables = _load(args)
     if not os.path.isdir(args.output_dir):
         os.makedirs(args.output_dir)
@@ -67,6 +108,8 @@ def run_frames_dir(args):
     # of a lane that does not swap, so the encoder is given that one (swap_rb=False) and its bytes go to disk as they are.
     jpg = args.output_format == 'jpg'
     kw = dict(swap_rb=False, jpeg=dict(quality=args.output_quality, subsampling=2)) if jpg else {}
+    if compose is not None:                                      # (compose_options: such lanes do not swap; the .png is then the frame as it comes)
+        kw = dict(kw, swap_rb=False, compose=compose)
 
     def save(n, img_out):
         if jpg:
@@ -74,7 +117,7 @@ def run_frames_dir(args):
                 f.write(img_out)
             return
         # cv2.imshow / VideoWriter interpret that array as BGR; save exactly what they would show
-        Image.fromarray(img_out[:, :, ::-1]).save(os.path.join(args.output_dir, os.path.splitext(n)[0] + '.png'))
+        Image.fromarray(img_out if compose is not None else img_out[:, :, ::-1]).save(os.path.join(args.output_dir, os.path.splitext(n)[0] + '.png'))
 
     # --frame_size W H: every frame is resized to W x H on the device, with cv2.resize's resampling (stream.py, source=).  --input_decode native: the
     # .jpg / .jpeg frames the library's decoder takes go in as file bytes (RGB; the lane swaps R and B on the device, source swap_rb: the BGR of a
@@ -111,6 +154,7 @@ def run_frames_dir(args):
             source = dict(height=Hs, width=Ws) if args.frame_size is not None else None
         W, H = args.frame_size if args.frame_size is not None else (Ws, Hs)
         print('Resolution is: {0} by {1}'.format(W, H))
+        check_mask_size(args, compose, W, H)
         more = dict(kw, source=source) if source is not None else kw
         if depth > 1:
             return stream.PipelinedStylizer(eng, variables, H, W, depth=depth, upsample_method=args.upsample_method, **more)
@@ -162,6 +206,7 @@ def run_video(args):
     while frame i is on the device."""
     from faststyle_amd import _lib, engine, stream, y4m
     check_video_flags(args)
+    compose = compose_options(args, args.video_matrix)
     to_stdout = args.video_out == '-'
     log = sys.stderr if to_stdout else sys.stdout
 
@@ -192,6 +237,7 @@ def run_video(args):
         except (_lib.FaststyleError, y4m.Y4MError) as e:
             raise SystemExit('--video_in %s: %s' % (args.video_in, e))
         W, H = args.frame_size if args.frame_size is not None else (Ws, Hs)
+        check_mask_size(args, compose, W, H)
         say('Resolution is: {0} by {1}'.format(W, H))
         say('Loading up model...')
         eng, variables = _load(args)
@@ -203,6 +249,8 @@ def run_video(args):
             kw.update(swap_rb=False, yuv_out=colour_out)
         elif jpg:
             kw.update(swap_rb=False, jpeg=dict(quality=args.output_quality, subsampling=2))
+        if compose is not None:                                              # (compose_options: such lanes do not swap; the .png is then the frame as it comes)
+            kw.update(swap_rb=False, compose=compose)
         depth = int(os.environ.get('FS_FRAMES_IN_FLIGHT', '2')) if hasattr(eng.mem, 'torch') else 1
         if depth > 1:
             st = stream.PipelinedStylizer(eng, variables, H, W, depth=depth, upsample_method=args.upsample_method, **kw)
@@ -225,7 +273,7 @@ def run_video(args):
                     f.write(out)
             else:
                 from PIL import Image
-                Image.fromarray(out[:, :, ::-1]).save(os.path.join(args.output_dir, '%06d.png' % done[0]))
+                Image.fromarray(out if compose is not None else out[:, :, ::-1]).save(os.path.join(args.output_dir, '%06d.png' % done[0]))
             done[0] += 1
 
         failed = None                                                        # a stream that breaks off: what was read is still written
@@ -275,6 +323,7 @@ def run_webcam(args):
         raise SystemExit('stylize_webcam.py needs OpenCV (cv2) for camera capture and display, as the reference does; '
                          'it is not installed here.  Use --frames_dir to filter a directory of frames.')
     from faststyle_amd import stream
+    compose = compose_options(args)
     cap = cv2.VideoCapture(0)
     if args.resolution is not None:
         x_length, y_length = args.resolution
@@ -282,15 +331,21 @@ def run_webcam(args):
         cap.set(cv2.CAP_PROP_FRAME_HEIGHT, y_length)
     x_new, y_new = int(cap.get(cv2.CAP_PROP_FRAME_WIDTH)), int(cap.get(cv2.CAP_PROP_FRAME_HEIGHT))
     print('Resolution is: {0} by {1}'.format(x_new, y_new))
+    check_mask_size(args, compose, x_new, y_new)
     print('Loading up model...')
     eng, variables = _load(args)
-    st = stream.FrameStylizer(eng, variables, y_new, x_new, args.upsample_method)
+    if compose is not None:                                  # (compose_options: the lane does not swap, the loop below does)
+        st = stream.FrameStylizer(eng, variables, y_new, x_new, args.upsample_method, swap_rb=False, compose=compose)
+    else:
+        st = stream.FrameStylizer(eng, variables, y_new, x_new, args.upsample_method)
     fourcc = cv2.VideoWriter_fourcc(*'XVID')
     out = cv2.VideoWriter('output.avi', fourcc, 15.0, (x_new, y_new))
     print('Begin filtering...')
     while True:
         ret, frame = cap.read()
         img_out = st(np.ascontiguousarray(frame))
+        if compose is not None:
+            img_out = np.ascontiguousarray(img_out[:, :, ::-1])
         out.write(img_out)
         cv2.imshow('frame', img_out)
         if cv2.waitKey(1) & 0xFF == ord('q'):
@@ -300,8 +355,8 @@ def run_webcam(args):
     cv2.destroyAllWindows()
 
 
-if __name__ == '__main__':
-    args = setup_parser().parse_args()
+def main(argv=None):
+    args = setup_parser().parse_args(argv)
     check_video_flags(args)
     if args.video_in is not None:
         run_video(args)
@@ -309,3 +364,7 @@ if __name__ == '__main__':
         run_frames_dir(args)
     else:
         run_webcam(args)
+
+
+if __name__ == '__main__':
+    main()

@@ -13,6 +13,10 @@ others: give it enough frames (1280) that its timed difference is about a second
 alternate in the one run -- the 8-bit stream above and the same frames as a stream of that many bits per sample (C420p10 ..., --video_depth
 stream, two bytes per sample in and out) -- plus the device time of one 720p launch of the two deep kernels and of the 8-bit kernel pairs they
 replace (HIP events around the replay of a graph of 200 launches each); written to profiles/video_deep.json with the digest of the kernel sources.
+"video" with "compose" as the fifth argument (pipe_bench.py 1280 4 video profiles/video_compose.json compose): only the raw-video loop, as two legs
+that alternate in the one run -- the 8-bit stream above without and with --style_strength 0.7 --preserve_color -- plus the device time of one 720p
+launch of compose_kernel (the same graph-of-200 scheme; wide path, with and without a mask, and the narrow path); written to
+profiles/video_compose.json with the digest of the kernel sources.
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -85,10 +89,33 @@ def host_encode(n, th):
     return res
 
 
+def kernel_timed(fn, launches=200):
+    """Device microseconds per call of fn: the launches are captured into one graph and the replay is timed with HIP events, after a warm-up --
+    launched one by one from Python they would measure the interpreter."""
+    import torch
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+        for _ in range(launches):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    g.replay()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / launches
+
+
 def kernel_times(bits, W=1280, H=720, launches=200):
     """-> dict of device microseconds per 720p 4:2:0 launch (HIP events around the replay of a graph that holds `launches` of them, after a warm-up): the two deep
     kernels, and the 8-bit conversions with the u8 <-> f32 launches of a lane beside them."""
-    import torch
     eng = engine.Engine()
     mem = eng.mem
     d8, dd = eng.yuv_plan(W, H, full_range=True), eng.yuv_plan(W, H, full_range=True, bits=bits)
@@ -98,27 +125,7 @@ def kernel_times(bits, W=1280, H=720, launches=200):
     u8 = mem.upload_u8(np.zeros((1, H, W, 3), np.uint8))
     f32 = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
 
-    def timed(fn):
-        # the launches are captured into one graph and the replay is timed: launched one by one from Python they would measure the interpreter
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            fn()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            for _ in range(launches):
-                fn()
-        g.replay()
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        g.replay()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3 / launches
-
+    timed = lambda fn: kernel_timed(fn, launches)
     res = {"yuv_deep_to_f32": timed(lambda: eng.yuv_deep_to_f32(pd, dd, f32, swap_rb=True)),
            "yuv_to_rgb_u8_then_u8_to_f32": timed(lambda: (eng.yuv_to_rgb_u8(p8, d8, u8, swap_rb=True), eng.u8_to_f32(u8, f32))),
            "f32_to_yuv_deep": timed(lambda: eng.f32_to_yuv_deep(f32, dd, pd)),
@@ -128,9 +135,31 @@ def kernel_times(bits, W=1280, H=720, launches=200):
     return res
 
 
-def frames_in(n, repeats=3, out_json=None, video=False, depth=None):
+def compose_kernel_times(W=1280, H=720, launches=200):
+    """-> dict of device microseconds per 720p launch of compose_kernel (fs_compose_f32), timed as kernel_times does: keep_color at strength 0.7 on
+    the wide path without and with a mask, plain mode, and the narrow path (the source one float off 16-byte alignment)."""
+    eng = engine.Engine()
+    mem = eng.mem
+    rng = np.random.default_rng(2)
+    src = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    net = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    dst = mem.empty((1, H, W, 3))
+    mask = mem.upload_u8(rng.integers(0, 256, (H, W), dtype=np.uint8))
+    off = mem.view(mem.from_numpy(np.zeros(H * W * 3 + 4, np.float32)), 1, (1, H, W, 3))
+    kw = dict(strength_q8=179, keep_color=True, bgr=False, src_swapped=True)
+    res = {"compose_keep_color": kernel_timed(lambda: eng.compose_f32(src, net, dst, **kw)),
+           "compose_keep_color_mask": kernel_timed(lambda: eng.compose_f32(src, net, dst, mask=mask, **kw)),
+           "compose_plain": kernel_timed(lambda: eng.compose_f32(src, net, dst, strength_q8=179)),
+           "compose_keep_color_narrow_path": kernel_timed(lambda: eng.compose_f32(off, net, dst, **kw))}
+    for k, v in res.items():
+        print("video: %8.1f us per 720p launch: %s" % (v, k))
+    return res
+
+
+def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False):
     """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json (video: with the raw-video leg, to
-    profiles/video_stream.json; video with a depth: the 8-bit and the deep raw-video legs alone, to profiles/video_deep.json)."""
+    profiles/video_stream.json; video with a depth: the 8-bit and the deep raw-video legs alone, to profiles/video_deep.json; video with
+    compose: the 8-bit raw-video leg without and with the compose stage, to profiles/video_compose.json)."""
     import contextlib
     import json
     import shutil
@@ -144,7 +173,7 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None):
     base = rng.integers(0, 256, (135, 240, 3), dtype=np.uint8)
     dirs = {}
     for tag, (w, h) in (("720p", (1280, 720)), ("1080p", (1920, 1080))):
-        if depth and tag != "720p":          # (the two video legs alone: no 1080p sources, no directories of JPEG frames)
+        if (depth or compose) and tag != "720p":          # (the two video legs alone: no 1080p sources, no directories of JPEG frames)
             continue
         files = []
         planes = []
@@ -162,7 +191,7 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None):
                 if depth:                    # ... and as samples of `depth` bits: the 8-bit value's bits repeated below it, so that the low bits are used
                     deep = [((p.astype(np.uint32) * 257) >> (16 - depth)).astype("<u2") for p in (ycc[:, :, 0], sub[:, :, 0], sub[:, :, 1])]
                     deep_planes.append(b"FRAME\n" + b"".join(p.tobytes() for p in deep))
-        for count in () if depth else (n, n // 4):
+        for count in () if depth or compose else (n, n // 4):
             p = os.path.join(d, "%s_%d" % (tag, count))
             os.makedirs(p)
             for k in range(count):
@@ -189,14 +218,16 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None):
         legs.append(("video_y4m_720p", "720p", None))
     if depth:
         legs = [("video_y4m_720p", "720p", None), ("video_y4m_720p_%dbit" % depth, "720p", depth)]
+    if compose:
+        legs = [("video_y4m_720p", "720p", None), ("video_y4m_720p_strength_0.7_preserve_color", "720p", ("--style_strength", "0.7", "--preserve_color"))]
     parser = stylize_webcam.setup_parser()
     out = os.path.join(d, "out")
 
-    def run_stream(tag, count, bits=None):
-        """the raw-video loop over count frames, file to file (bits: the deep stream, taken and written at its own depth)"""
+    def run_stream(tag, count, bits=None, extra=()):
+        """the raw-video loop over count frames, file to file (bits: the deep stream, taken and written at its own depth; extra: more flags)"""
         src = "%s_%d_p%d.y4m" % (tag, count, bits) if bits else "%s_%d.y4m" % (tag, count)
         args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--video_in", os.path.join(d, src),
-                                  "--video_out", out + ".y4m"] + (["--video_depth", "stream"] if bits else []))
+                                  "--video_out", out + ".y4m"] + (["--video_depth", "stream"] if bits else []) + list(extra))
         with contextlib.redirect_stdout(io.StringIO()):
             t0 = time.time()
             stylize_webcam.run_video(args)
@@ -208,6 +239,8 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None):
     def run(tag, count, flags):
         if flags is None or isinstance(flags, int):
             return run_stream(tag, count, flags)
+        if isinstance(flags, tuple):
+            return run_stream(tag, count, extra=flags)
         args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--frames_dir", dirs[tag, count],
                                   "--output_dir", out, "--output_format", "jpg"] + flags)
         with contextlib.redirect_stdout(io.StringIO()):
@@ -218,7 +251,7 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None):
         shutil.rmtree(out)
         return dt
 
-    run("720p", n // 4, None if depth else [])                    # warm-up: library load, first kernels
+    run("720p", n // 4, None if depth or compose else [])                    # warm-up: library load, first kernels
     times = {name: [] for name, _, _ in legs}
     for _ in range(repeats):                                      # legs alternate: a drifting clock touches all of them alike
         for name, tag, flags in legs:
@@ -236,6 +269,11 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None):
         res["bytes_per_frame_in_and_out"] = {"video_y4m_720p": 1280 * 720 * 3 // 2, "video_y4m_720p_%dbit" % depth: 1280 * 720 * 3}
         from faststyle_amd import build as fsbuild
         res["source_digest"] = fsbuild.source_digest()
+    if compose:
+        res["output"] = "YUV4MPEG2, 8 bits"
+        res["host_threads"] = "1 driver"
+        from faststyle_amd import build as fsbuild
+        res["source_digest"] = fsbuild.source_digest()
     for name, _, _ in legs:
         rates = sorted((n - n // 4) / (a - b) for a, b in times[name])
         res["legs"][name] = {"frames_per_s": rates[len(rates) // 2], "all_repeats": rates, "seconds_n_and_quarter": times[name]}
@@ -243,7 +281,9 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None):
     shutil.rmtree(d)
     if depth:
         res["kernel_us_per_720p_launch"] = kernel_times(depth)
-    dst = out_json or os.path.join(root, "profiles", "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
+    if compose:
+        res["kernel_us_per_720p_launch"] = compose_kernel_times()
+    dst = out_json or os.path.join(root, "profiles", "video_compose.json" if compose else "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
     with open(dst, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
@@ -255,8 +295,9 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     threads = int(sys.argv[2]) if len(sys.argv) > 2 else None
     if len(sys.argv) > 3 and sys.argv[3] in ("frames_in", "video"):
-        depth = int(sys.argv[5]) if len(sys.argv) > 5 and sys.argv[3] == "video" else None
-        frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video", depth=depth)
+        fifth = sys.argv[5] if len(sys.argv) > 5 and sys.argv[3] == "video" else None
+        frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video",
+                  depth=int(fifth) if fifth not in (None, "compose") else None, compose=fifth == "compose")
         return
     if len(sys.argv) > 3 and sys.argv[3] == "host_encode":
         host_encode(n, threads or 4)
