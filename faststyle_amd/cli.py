@@ -113,4 +113,12 @@ def stylize_webcam_parser():
         ('--mask_path', dict(default=None, metavar='FILE',
                              help="(addition) a grey image of the net's input size (after --frame_size): 0 keeps the source pixel, 255 stylizes it, "
                                   "values between blend")),
+        ('--temporal_strength', dict(default=argparse.SUPPRESS, type=float, metavar='S',
+                                     help="(addition) stabilise the frames over time on the device: blend every frame towards the previous stabilised "
+                                          "frame, fetched along block motion vectors, where the source matched; 0 nothing, 1 all of it (default: no "
+                                          "such stage); with --frames_dir, --video_in and the camera")),
+        ('--temporal_radius', dict(default=argparse.SUPPRESS, type=int, metavar='R', help="(addition) search radius of the motion vectors in pixels, 0..7 (default 7)")),
+        ('--temporal_sensitivity', dict(default=argparse.SUPPRESS, type=int, metavar='K',
+                                        help="(addition) how fast a source mismatch turns the blend off, 1..256: none of it is left at a luma "
+                                             "difference of 256 / K (default 16)")),
     ])

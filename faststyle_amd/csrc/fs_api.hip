@@ -240,6 +240,27 @@ int fs_compose_f32(fs_ctx* ctx, const float* src, int H, int W, const float* net
     const int rc = fs::compose_f32(src, H, W, net, Ho, Wo, N, strength_q8, keep_color ? 1 : 0, matrix, bgr & 1, bgr >> 1, mask, dst, ctx->stream);
     return rc ? fail(rc, "fs_compose_f32: launch failed (%d)", rc) : 0;
 }
+int fs_temporal_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius,
+                    int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma,
+                    unsigned short* out88, signed char* mv, float* dst) {
+    if (!ctx || !src || !cur || !luma || !out88 || !mv || !dst) return fail(-1, "fs_temporal_f32: null argument");
+    if ((prev_luma == nullptr) != (prev_out88 == nullptr))
+        return fail(-1, "fs_temporal_f32: prev_luma and prev_out88 are both given or both null (no previous frame)");
+    if (prev_luma == luma || prev_out88 == out88)
+        return fail(-1, "fs_temporal_f32: the previous frame's state is read at displaced positions and cannot be the state written");
+    if (H < 1 || W < 1 || Ho < H || Ho - H > 3 || Wo < W || Wo - W > 3)
+        return fail(-1, "fs_temporal_f32: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", H, W, Ho, Wo);
+    if (strength_q8 < 0 || strength_q8 > 256) return fail(-2, "fs_temporal_f32: strength_q8 must be in [0, 256], got %d", strength_q8);
+    if (sensitivity < 1 || sensitivity > 256) return fail(-2, "fs_temporal_f32: sensitivity must be in [1, 256], got %d", sensitivity);
+    if (radius < 0 || radius > 7) return fail(-2, "fs_temporal_f32: radius must be in [0, 7], got %d", radius);
+    if (matrix != 0 && matrix != 1) return fail(-2, "fs_temporal_f32: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
+    if (src_bgr != 0 && src_bgr != 1) return fail(-2, "fs_temporal_f32: src_bgr must be 0 or 1, got %d", src_bgr);
+    if (((uintptr_t)src | (uintptr_t)cur | (uintptr_t)dst) & 3) return fail(-5, "fs_temporal_f32: src, cur and dst must be 4-byte aligned");
+    if (((uintptr_t)prev_out88 | (uintptr_t)out88) & 1) return fail(-5, "fs_temporal_f32: prev_out88 and out88 must be 2-byte aligned");
+    const int rc = fs::temporal_f32(src, H, W, cur, Ho, Wo, strength_q8, sensitivity, radius, matrix, src_bgr, prev_luma, prev_out88, luma, out88, mv,
+                                    dst, ctx->stream);
+    return rc ? fail(rc, "fs_temporal_f32: launch failed (%d)", rc) : 0;
+}
 int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
                   const int32_t* move_dst, int M, float* batch_out) {
     if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");

@@ -693,6 +693,11 @@ int f32_to_yuv_deep(const ::fs_yuv_desc& desc, const float* src, int swap_rb, in
 // the net's output blended towards its input on the 8.8 scale (fs_compose.hip): the launch (argument checks are in fs_api.hip)
 int compose_f32(const float* src, int H, int W, const float* net, int Ho, int Wo, int N, int strength_q8, int keep_color, int matrix, int bgr,
                 int src_swap, const unsigned char* mask, float* dst, hipStream_t s);
+// temporal stabilisation (fs_temporal.hip): luma of the source, block-matching search against the previous luma, blend towards the previous
+// stabilised output along the vectors -- three launches (argument checks are in fs_api.hip)
+int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius, int matrix, int src_bgr,
+                 const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma, unsigned short* out88, signed char* mv,
+                 float* dst, hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);
 // ... with the per-sample sums taken from records [N][T][C][2] (rec == nullptr: computed here into `scratch`), reduced in the apply kernel's

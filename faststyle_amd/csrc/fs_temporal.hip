@@ -1,0 +1,237 @@
+// Temporal stabilisation between the forward pass (or compose) and the output conversions (include/faststyle_io.h, whose comment is the
+// arithmetic contract): a byte luma of the net's input on the output grid, a block-matching motion search between this luma and the previous
+// frame's, and a per-pixel blend of the new output towards the previous stabilised output fetched along the block's vector, weighted by how
+// well the source matched there.  faststyle_amd/stream.py (temporal=) keeps the two state slots and runs the three launches behind compose.
+//   luma   -- elementwise, the thread layout of compose_kernel: four pixels of an output row.
+//   search -- one workgroup of 256 threads per 16x16 block, one thread per candidate (dy, dx) in [-R, R]^2 (225 at R = 7).  The block's luma
+//             (16 rows of 16 bytes, zero outside the frame) and the previous luma's (16 + 2R)^2 window go to LDS with the clamped coordinates
+//             applied, so the inner loop has no bounds logic; a ragged block runs `rows` rows (uniform) and masks the window's dwords beyond
+//             `cols` (uniform), where the block's own bytes are zero already.  A candidate reads, per row, the five aligned dwords that hold
+//             its sixteen bytes, shifts them into place and adds four packed-byte SADs against the block's dwords (the same address in every
+//             lane: a broadcast).  Window pitch 32 bytes = 8 banks: the lanes of a 32-lane group are candidates of at most 4 consecutive dy
+//             (15 apart is one row down) and of dword columns 0 ... 3 + k, so they touch 4 rows x 8 banks, each bank once per distinct
+//             address -- conflict-free by the rule that ds_read_b32 banks are (a / 4) mod 32 per 32-lane half.  The 256 keys are reduced by an
+//             LDS min tree.
+//   blend  -- elementwise, four pixels of an output row (they lie in one block: one vector per thread).
+// No value read from a tensor reaches an address except through mv, which the search bounds by R and the blend clamps again together with
+// the displaced coordinates.  The arithmetic is integer throughout.
+#include "../../include/faststyle_io.h"
+
+#include "fs_kernels.h"
+
+namespace fs {
+namespace {
+
+constexpr int TB = 16;                      // block edge
+constexpr int TRMAX = 7;                    // largest search radius
+constexpr int TPITCH = 32;                  // bytes per LDS window row: 16 + 2 * 7 = 30 used, the five-dword read of column 14 ends at byte 31
+constexpr int TWROWS = TB + 2 * TRMAX;      // 30
+
+// the float on the 8.8 scale, as compose_kernel's: clamped to [0, 255] (NaN: 0), times 256 (exact), truncated
+__device__ __forceinline__ int temporal_f88(float v) { return (int)(fminf(fmaxf(v, 0.f), 255.f) * 256.0f); }
+
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// acc + the four absolute byte differences of a and b
+__device__ __forceinline__ unsigned sad4(unsigned a, unsigned b, unsigned acc) {
+#ifndef FS_EMULATOR
+    return __builtin_amdgcn_sad_u8(a, b, acc);
+#else
+    for (int k = 0; k < 4; ++k) {
+        const int x = (int)((a >> (8 * k)) & 0xFFu), y = (int)((b >> (8 * k)) & 0xFFu);
+        acc += (unsigned)(x > y ? x - y : y - x);
+    }
+    return acc;
+#endif
+}
+
+struct LumaArgs {
+    int H, W, Ho, Wo;
+    int k0, k1, k2;                         // luma weights by 2^16 of the channels as stored (k0 is kb when channel 0 is blue)
+};
+
+// Thread i: row y = i / groups, pixels x0 = 4 * (i % groups) ... x0 + 3 (groups = ceil(Wo / 4)); the source is read at (min(y, H - 1), min(x, W - 1)).
+__global__ __launch_bounds__(256) void temporal_luma_kernel(const LumaArgs A, const float* __restrict__ src, unsigned char* __restrict__ luma) {
+    const int groups = (A.Wo + 3) >> 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)groups * A.Ho) return;
+    const int y = (int)(i / groups), x0 = (int)(i - (long long)y * groups) * 4;
+    const int ys = y < A.H ? y : A.H - 1;
+    const float* srow = src + (size_t)ys * A.W * 3;
+    unsigned char* lrow = luma + (size_t)y * A.Wo;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = x0 + k;
+        if (x >= A.Wo) break;
+        const int xs = x < A.W ? x : A.W - 1;
+        const int A0 = temporal_f88(srow[(size_t)xs * 3]), A1 = temporal_f88(srow[(size_t)xs * 3 + 1]), A2 = temporal_f88(srow[(size_t)xs * 3 + 2]);
+        const long long Y = ((long long)A.k0 * A0 + (long long)A.k1 * A1 + (long long)A.k2 * A2 + 32768) >> 16;       // 0 ... 65280
+        lrow[x] = (unsigned char)(Y >> 8);
+    }
+}
+
+// One workgroup per block (blockIdx.y, blockIdx.x).  prev == nullptr (no previous frame): every vector is (0, 0).
+__global__ __launch_bounds__(256) void temporal_search_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int Ho,
+                                                              int Wo, int R, signed char* __restrict__ mv) {
+    __shared__ unsigned win[TWROWS * (TPITCH / 4)];         // the previous luma's window, row pitch 8 dwords
+    __shared__ unsigned blk[TB * (TB / 4)];                 // the block's luma, 4 dwords per row, zero outside the frame
+    __shared__ unsigned keys[256];
+    const int t = (int)threadIdx.x;
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    signed char* out = mv + ((size_t)by * gridDim.x + bx) * 2;
+    if (prev8 == nullptr) {                                 // (uniform per launch)
+        if (t == 0) { out[0] = 0; out[1] = 0; }
+        return;
+    }
+    const int y0 = by * TB, x0 = bx * TB;
+    const int rows = Ho - y0 < TB ? Ho - y0 : TB, cols = Wo - x0 < TB ? Wo - x0 : TB;        // at least 1 each
+    const int n = 2 * R + 1;
+    if (t < (TB + 2 * R) * (TPITCH / 4)) {                  // window row t / 8, dword t % 8: frame rows y0 - R ..., columns x0 - R ...
+        const int wr = t >> 3, wc = (t & 7) * 4;
+        const unsigned char* prow = prev8 + (size_t)clampi(y0 - R + wr, Ho - 1) * Wo;
+        unsigned v = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) v |= (unsigned)prow[clampi(x0 - R + wc + b, Wo - 1)] << (8 * b);
+        win[t] = v;
+    }
+    if (t < TB * (TB / 4)) {                                // block row t / 4, dword t % 4
+        const int r = t >> 2, c = (t & 3) * 4;
+        unsigned v = 0;
+        if (r < rows) {
+            const unsigned char* crow = cur8 + (size_t)(y0 + r) * Wo + x0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (c + b < cols) v |= (unsigned)crow[c + b] << (8 * b);
+        }
+        blk[t] = v;
+    }
+    __syncthreads();
+    unsigned key = 0xFFFFFFFFu;
+    if (t < n * n) {
+        const int dyi = t / n, dxi = t - dyi * n;           // dy + R, dx + R: the window's row and column of the candidate's first pixel
+        const int dy = dyi - R, dx = dxi - R;
+        unsigned m[4];                                      // the bytes of dword k that lie inside the block
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int inside = cols - 4 * k;
+            m[k] = inside >= 4 ? 0xFFFFFFFFu : (inside <= 0 ? 0u : (1u << (8 * inside)) - 1u);
+        }
+        const int sh = (dxi & 3) * 8;
+        const unsigned* wp = win + dyi * (TPITCH / 4) + (dxi >> 2);          // (dxi >> 2) + 4 <= 7: inside the row
+        unsigned sad = 0;
+        for (int r = 0; r < rows; ++r) {
+            const unsigned* w = wp + r * (TPITCH / 4);
+            const unsigned* c = blk + r * 4;
+            unsigned lo = w[0];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned hi = w[k + 1];
+                const unsigned a = (unsigned)((((unsigned long long)hi << 32) | lo) >> sh);
+                sad = sad4(a & m[k], c[k], sad);
+                lo = hi;
+            }
+        }
+        const int mag = (dy < 0 ? -dy : dy) + (dx < 0 ? -dx : dx);
+        const unsigned cost = sad + (unsigned)(((rows * cols) >> 5) * mag);              // below 2^17
+        key = (cost << 12) | ((unsigned)mag << 8) | ((unsigned)(dy + 7) << 4) | (unsigned)(dx + 7);
+    }
+    keys[t] = key;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+            const unsigned a = keys[t], b = keys[t + s];
+            keys[t] = a < b ? a : b;
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const unsigned k = keys[0];
+        out[0] = (signed char)((int)((k >> 4) & 15u) - 7);
+        out[1] = (signed char)((int)(k & 15u) - 7);
+    }
+}
+
+struct BlendArgs {
+    int Ho, Wo, nbx;
+    int strength_q8, sensitivity, R;
+};
+
+// Thread i: row y, pixels x0 ... x0 + 3 as in the luma kernel.  dst may be cur: a thread reads its own pixels before it writes them, and no
+// other thread reads them (hence no __restrict__ on the two).  prev8 / prev88 are read at displaced positions: they are not luma / out88.
+__global__ __launch_bounds__(256) void temporal_blend_kernel(const BlendArgs A, const float* cur, const unsigned char* __restrict__ cur8,
+                                                             const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
+                                                             const signed char* __restrict__ mv, float* dst, unsigned short* __restrict__ out88) {
+    const int groups = (A.Wo + 3) >> 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)groups * A.Ho) return;
+    const int y = (int)(i / groups), x0 = (int)(i - (long long)y * groups) * 4;
+    const size_t row = (size_t)y * A.Wo;
+    int qy = y, dx = 0;
+    if (prev8 != nullptr) {                                 // (uniform per launch)
+        const signed char* v = mv + ((size_t)(y >> 4) * A.nbx + (x0 >> 4)) * 2;
+        const int dy = (int)v[0] < -A.R ? -A.R : ((int)v[0] > A.R ? A.R : (int)v[0]);    // (the search wrote them within R; held to it again)
+        dx = (int)v[1] < -A.R ? -A.R : ((int)v[1] > A.R ? A.R : (int)v[1]);
+        qy = clampi(y + dy, A.Ho - 1);
+    }
+    const int n = A.Wo - x0 < 4 ? A.Wo - x0 : 4;
+    const size_t at0 = (row + x0) * 3;
+    float b[12];                                            // every read of cur before the first write of dst: the two may be one tensor
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int xn = k < n ? k : n - 1;                   // (beyond the row's end: the last pixel again, never stored)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b[3 * k + c] = cur[at0 + 3 * xn + c];
+    }
+    int F[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int xn = x0 + (k < n ? k : n - 1);
+        const int B0 = temporal_f88(b[3 * k]), B1 = temporal_f88(b[3 * k + 1]), B2 = temporal_f88(b[3 * k + 2]);
+        F[3 * k] = B0; F[3 * k + 1] = B1; F[3 * k + 2] = B2;
+        if (prev8 != nullptr) {
+            const size_t q = (size_t)qy * A.Wo + clampi(xn + dx, A.Wo - 1);
+            const int d = (int)cur8[row + xn] - (int)prev8[q];
+            const int e = d < 0 ? -d : d;
+            const int conf = 256 - e * A.sensitivity;
+            const long long w = (long long)A.strength_q8 * (conf > 0 ? conf : 0);        // 0 ... 65536
+            const int P0 = prev88[q * 3], P1 = prev88[q * 3 + 1], P2 = prev88[q * 3 + 2];
+            F[3 * k] = B0 + (int)(((long long)(P0 - B0) * w + 32768) >> 16);
+            F[3 * k + 1] = B1 + (int)(((long long)(P1 - B1) * w + 32768) >> 16);
+            F[3 * k + 2] = B2 + (int)(((long long)(P2 - B2) * w + 32768) >> 16);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < n) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                dst[at0 + 3 * k + c] = (float)F[3 * k + c] * 0.00390625f;
+                out88[at0 + 3 * k + c] = (unsigned short)F[3 * k + c];
+            }
+        }
+}
+
+}  // namespace
+
+// arguments: checked by the caller (fs_api.hip: fs_temporal_f32)
+int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius, int matrix, int src_bgr,
+                 const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma, unsigned short* out88, signed char* mv,
+                 float* dst, hipStream_t s) {
+    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
+    LumaArgs LA;
+    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
+    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
+    const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
+    const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
+    hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, src, luma);
+    const int nby = (Ho + TB - 1) / TB, nbx = (Wo + TB - 1) / TB;
+    hipLaunchKernelGGL(temporal_search_kernel, dim3((unsigned)nbx, (unsigned)nby), block, 0, s, (const unsigned char*)luma, prev_luma, Ho, Wo, radius, mv);
+    BlendArgs BA;
+    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = nbx;
+    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = radius;
+    hipLaunchKernelGGL(temporal_blend_kernel, egrid, block, 0, s, BA, cur, (const unsigned char*)luma, prev_luma, prev_out88, (const signed char*)mv, dst,
+                       out88);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace fs

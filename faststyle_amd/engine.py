@@ -947,6 +947,39 @@ class Engine(JpegHost, CvResizeHost, YuvHost):
                 "fs_compose_f32")
         return dst
 
+    # ------------------------------------------------------------------ temporal stabilisation (csrc/fs_temporal.hip)
+    def temporal_state(self, Ho, Wo):
+        """One state slot of fs_temporal_f32 for an Ho x Wo output, as device uint8 buffers (the memory backend's): (luma [Ho,Wo], out88
+        [Ho,Wo,3,2] -- little-endian u16 on the 8.8 scale --, mv [nby,nbx,2] -- signed char (dy, dx) per 16 x 16 block)."""
+        Ho, Wo = int(Ho), int(Wo)
+        up = self.mem.upload_u8
+        return (up(np.zeros((Ho, Wo), np.uint8)), up(np.zeros((Ho, Wo, 3, 2), np.uint8)), up(np.zeros(((Ho + 15) // 16, (Wo + 15) // 16, 2), np.uint8)))
+
+    def temporal_f32(self, src, cur, dst, state, prev=None, strength_q8=256, sensitivity=16, radius=7, matrix="bt601", src_bgr=False):
+        """fs_temporal_f32: src device float32 [H,W,3] (the net's input), cur and dst device float32 [Ho,Wo,3] (the tensor the output
+        conversions would read and the stabilised one; dst may be cur; a leading axis of 1 is taken), state the slot written (temporal_state's
+        triple), prev the slot the previous frame wrote (None: no previous frame) -> dst = cur blended towards prev's output along the
+        block vectors found between the two lumas; matrix 'bt601' / 'bt709' or 0 / 1, src_bgr: channel 0 of src is blue."""
+        self._sync_stream()
+        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
+        if len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,):
+            ss, cs, ds = ss[1:], cs[1:], ds[1:]
+        if len(ss) != 3 or len(cs) != 3 or ss[2] != 3 or cs[2] != 3 or ds != cs:
+            raise L.FaststyleError("temporal_f32: source %s / current %s / destination %s do not belong together (one image per call)" %
+                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
+        Ho, Wo = cs[:2]
+        want = ((Ho, Wo), (Ho, Wo, 3, 2), ((Ho + 15) // 16, (Wo + 15) // 16, 2))
+        for name, slot in (("state", state), ("prev", prev)):
+            if slot is not None and (len(slot) != 3 or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
+                raise L.FaststyleError("temporal_f32: %s is not the slot of a %dx%d output (temporal_state)" % (name, Ho, Wo))
+        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
+        p8 = self.mem.ptr_u8
+        L.check(self.lib, self.lib.fs_temporal_f32(self.ctx, self.mem.ptr(src), ss[0], ss[1], self.mem.ptr(cur), Ho, Wo, int(strength_q8),
+                                                   int(sensitivity), int(radius), int(matrix), 1 if src_bgr else 0,
+                                                   None if prev is None else p8(prev[0]), None if prev is None else p8(prev[1]),
+                                                   p8(state[0]), p8(state[1]), p8(state[2]), self.mem.ptr(dst)), "fs_temporal_f32")
+        return dst
+
     def synth_uniform(self, out, seed, rank, batch_index):
         """Uniform [0,255) float32 values into ``out``: Philox4x32-10 keyed by seed, counter (element block, batch_index, rank) (fs_synth_uniform)."""
         self._sync_stream()

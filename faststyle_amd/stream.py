@@ -42,6 +42,17 @@ uint8 [H, W] at the net's input size, 0 keeps the source and 255 takes the blend
 when the lane's output conversion swaps.  ``source_swapped=True`` says that the frames reach the net with R and B the other way round than
 its output is shown -- the reference's channel handling, which the command-line tools keep -- so that the source is read with the two
 exchanged and shows through in its own colours.  Without ``compose=`` nothing is allocated or launched.
+
+Temporal stabilisation: with ``temporal=dict(strength=, sensitivity=16, radius=7, matrix='bt601', source_bgr=<the lane's swap_rb>)`` three
+launches behind compose (fs_temporal_f32, csrc/fs_temporal.hip) blend the tensor the output conversions would read towards the previous
+frame's stabilised output, fetched along 16 x 16 block vectors found between the byte lumas of the two source frames and weighted by how well
+the source matched there; every output conversion then reads the lane's stabilised tensor.  ``strength`` in [0, 1] is quantised as compose's,
+``sensitivity`` K in [1, 256] takes the weight to zero at a luma difference of 256 / K, ``radius`` in [0, 7] bounds the search, ``matrix``
+names the luma weights and ``source_bgr`` says that channel 0 of the net's input is blue.  One frame per pass (batch 1).  The lane keeps two
+state slots (luma, the output on the 8.8 scale, the vectors): frame n reads slot (n - 1) & 1 and writes slot n & 1.  The slot parity changes
+pointers and "no previous frame" is a launch argument, so such a lane's pass is captured in pieces: the head (input conversions, forward,
+compose) as before, and the tail (the stage and the output conversions) once per parity and once for a first frame, each when it first
+occurs.  ``reset()`` forgets the previous frame.  Without ``temporal=`` nothing is allocated or launched and the one graph is captured whole.
 """
 import ctypes
 
@@ -69,7 +80,7 @@ class FrameStylizer(object):
     KEEP_GRAPH = False     # tests: keep the captured hipGraph_t so that its node types can be inspected
 
     def __init__(self, eng, variables, height, width, upsample_method="resize", batch=1, swap_rb=True, use_graph=True,
-                 bf16=False, jpeg=None, jpeg_threads=4, source=None, yuv_out=None, compose=None):
+                 bf16=False, jpeg=None, jpeg_threads=4, source=None, yuv_out=None, compose=None, temporal=None, _temporal_slots=None):
         self.eng = eng
         self.variables = variables
         self.method = upsample_method
@@ -117,6 +128,43 @@ class FrameStylizer(object):
         self._mask = None
         if compose is not None:
             self._compose_setup(dict(compose))
+        self.temporal = None             # with temporal=: dict(strength_q8=, sensitivity=, radius=, matrix=, source_bgr=) as the launch takes them
+        self._stab = None                # ... the stabilised tensor every output conversion then reads
+        self._tslots = None              # ... the two state slots (Engine.temporal_state), shared by the lanes of a PipelinedStylizer
+        self._tn = 0                     # ... frames since construction or reset(): frame n reads slot (n - 1) & 1 and writes slot n & 1
+        self._cur = None                 # ... the head's result: the net's output or the composed tensor
+        self._tail_graphs = {}           # ... captured tails by the parity written (None: a first frame's)
+        if temporal is not None:
+            self._temporal_setup(dict(temporal), _temporal_slots)
+
+    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr")
+
+    def _temporal_setup(self, opt, slots):
+        """The temporal stage's fixed parts: the quantised strength, the checked parameters, the state slots and the stabilised tensor."""
+        kw = {k: opt.pop(k) for k in self.TEMPORAL_KEYS if k in opt}
+        if opt:
+            raise L.FaststyleError("temporal takes %s, got also %r" % (", ".join(self.TEMPORAL_KEYS), opt))
+        if self.shape[0] != 1:
+            raise L.FaststyleError("temporal takes one frame per pass, this stylizer has a batch of %d" % self.shape[0])
+
+        def number(name, default, lo, hi, whole):
+            try:
+                v = float(kw.get(name, default))
+            except (TypeError, ValueError):
+                raise L.FaststyleError("temporal %s %r is not a number" % (name, kw[name]))
+            if not lo <= v <= hi or (whole and v != int(v)):     # (NaN fails both comparisons)
+                raise L.FaststyleError("temporal %s must be %s in [%d, %d], got %r" % (name, "a whole number" if whole else "a number", lo, hi, v))
+            return v
+
+        s = number("strength", 1.0, 0, 1, False)
+        matrix = {"bt601": 0, "bt709": 1, 0: 0, 1: 1}.get(kw.get("matrix", "bt601"))
+        if matrix is None:
+            raise L.FaststyleError("temporal matrix is 'bt601' or 'bt709', got %r" % (kw["matrix"],))
+        self.temporal = dict(strength_q8=int(np.floor(s * 256.0 + 0.5)), sensitivity=int(number("sensitivity", 16, 1, 256, True)),
+                             radius=int(number("radius", 7, 0, 7, True)), matrix=matrix, source_bgr=bool(kw.get("source_bgr", self.swap_rb)))
+        Ho, Wo = self.out_shape[1:3]
+        self._tslots = slots if slots is not None else [self.eng.temporal_state(Ho, Wo) for _ in range(2)]
+        self._stab = self.eng.mem.empty(self.out_shape)
 
     COMPOSE_KEYS = ("strength", "keep_color", "matrix", "mask", "source_swapped")
 
@@ -319,6 +367,14 @@ class FrameStylizer(object):
             c = self.compose                                 # (the tensors are B,G,R exactly when the output conversion swaps)
             y = e.compose_f32(self._in_f32, self._y, self._composed, strength_q8=c["strength_q8"], keep_color=c["keep_color"], matrix=c["matrix"],
                               bgr=self.swap_rb, mask=self._mask, src_swapped=c["source_swapped"])
+        if self.temporal is not None:                        # the output conversions belong to the tail (_tail), which reads this
+            self._cur = y
+            return
+        self._outputs(y)
+
+    def _outputs(self, y):
+        """The output conversions of y: the net's output, the composed or the stabilised tensor."""
+        e = self.eng
         if self._out_deep:                                   # 16-bit samples: straight from the net's fp32 output
             e.f32_to_yuv_deep(y, self.yuv_out_desc, self._result, swap_rb=self.swap_rb)
             return
@@ -328,29 +384,45 @@ class FrameStylizer(object):
         if self.yuv_out is not None:
             e.rgb_to_yuv_u8(self._out_u8, self.yuv_out_desc, self._result)
 
-    def _capture(self, jpeg_in=False):
-        """Capture the device pass of pixel frames (self._graph) or of JPEG frames (self._graph_jpeg).  The warm-up runs the pass once on
-        whatever the input buffers hold, and the JPEG pass consumes its coefficients: callers capture BEFORE they upload a JPEG frame."""
+    def _tail(self, n):
+        """The temporal stage of frame n since construction or reset(), and the output conversions of the stabilised tensor.  It writes
+        slot n & 1 and reads slot (n - 1) & 1, so running it twice on one frame (the warm-up of a capture, then the replay) changes nothing."""
+        t = self.temporal
+        self.eng.temporal_f32(self._in_f32, self._cur, self._stab, self._tslots[n & 1], prev=None if n == 0 else self._tslots[(n - 1) & 1],
+                              strength_q8=t["strength_q8"], sensitivity=t["sensitivity"], radius=t["radius"], matrix=t["matrix"],
+                              src_bgr=t["source_bgr"])
+        self._outputs(self._stab)
+
+    def _captured(self, launches):
+        """A graph of what ``launches`` enqueues, after one run of it outside capture (one-time initialisation)."""
         torch = self.eng.mem.torch
-        self.eng.invalidate_frozen()                       # the warm-up below rebuilds the filters in self._ws whatever the library remembers
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                      # warm-up outside capture (one-time initialisation)
-            self._device_pass(jpeg_in)
+        with torch.cuda.stream(side):
+            launches()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph(keep_graph=True) if self.KEEP_GRAPH else torch.cuda.CUDAGraph()
         # thread_local: calls made by OTHER threads (e.g. the RCCL watchdog of a data-parallel run) must not
         # invalidate this thread's capture
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._device_pass(jpeg_in)
+            launches()
+        return g
+
+    def _capture(self, jpeg_in=False):
+        """Capture the device pass of pixel frames (self._graph) or of JPEG frames (self._graph_jpeg).  The warm-up runs the pass once on
+        whatever the input buffers hold, and the JPEG pass consumes its coefficients: callers capture BEFORE they upload a JPEG frame."""
+        self.eng.invalidate_frozen()                       # the warm-up rebuilds the filters in self._ws whatever the library remembers
+        g = self._captured(lambda: self._device_pass(jpeg_in))
         if jpeg_in:
             self._graph_jpeg = g
         else:
             self._graph = g                                # (replays raw pointers into self._ws, which lives as long as this object)
 
-    def _run(self, jpeg_in=False):
-        """The device pass of the frame(s) just uploaded: the captured graph's replay, or eager."""
+    def _run(self, jpeg_in=False, before_tail=None):
+        """The device pass of the frame(s) just uploaded: the captured graph's replay, or eager.  With temporal= that pass is the head, and
+        the tail follows: eager, or the replay of the graph of its kind (a first frame's, or the parity's), captured when first needed.
+        before_tail: called between the two (a PipelinedStylizer's wait for the previous frame's tail on another stream)."""
         if not self._use_graph:
             self._device_pass(jpeg_in)
         elif jpeg_in:
@@ -359,6 +431,25 @@ class FrameStylizer(object):
             if self._graph is None:
                 self._capture()
             self._graph.replay()
+        if self.temporal is None:
+            return
+        if before_tail is not None:
+            before_tail()
+        n = self._tn
+        if not self._use_graph:
+            self._tail(n)
+        else:
+            kind = None if n == 0 else n & 1
+            if kind not in self._tail_graphs:
+                self._tail_graphs[kind] = self._captured(lambda: self._tail(n))
+            self._tail_graphs[kind].replay()
+        self._tn = n + 1
+
+    def reset(self):
+        """Forget the previous frame: the next one is stabilised as a first frame (temporal= only)."""
+        if self.temporal is None:
+            raise L.FaststyleError("reset: this stylizer was built without temporal=")
+        self._tn = 0
 
     def _upload_jpeg(self, staging):
         """Decoded coefficients (decode_frames' staging) -> the device coefficient buffer, on the current stream."""
@@ -374,6 +465,7 @@ class FrameStylizer(object):
         """Drop the captured graph (and the encode threads)."""
         self._graph = None
         self._graph_jpeg = None
+        self._tail_graphs = {}
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
@@ -402,6 +494,23 @@ class FrameStylizer(object):
         if self._y is None:
             raise L.FaststyleError("composed_output: this stylizer has not run a frame yet")
         return np.array(self.eng.mem.to_numpy(self._composed), dtype=np.float32, copy=True)
+
+    def stabilised_output(self):
+        """For tests and inspection: a host float32 copy [1,Ho,Wo,3] of the stabilised tensor of the last pass (synchronises); a stylizer
+        built without temporal= has none."""
+        if self._stab is None:
+            raise L.FaststyleError("stabilised_output: this stylizer was built without temporal=")
+        if self._y is None:
+            raise L.FaststyleError("stabilised_output: this stylizer has not run a frame yet")
+        return np.array(self.eng.mem.to_numpy(self._stab), dtype=np.float32, copy=True)
+
+    def motion_vectors(self):
+        """For tests and inspection: the block vectors (dy, dx) of the last pass, host int8 [ceil(Ho / 16), ceil(Wo / 16), 2] (synchronises)."""
+        if self._tslots is None:
+            raise L.FaststyleError("motion_vectors: this stylizer was built without temporal=")
+        if self._tn == 0:
+            raise L.FaststyleError("motion_vectors: this stylizer has not run a frame since it was built or reset")
+        return np.array(self.eng.mem.to_numpy(self._tslots[(self._tn - 1) & 1][2]), dtype=np.uint8, copy=True).view(np.int8)
 
     def as_planes(self, a):
         """A frame of a deep source given as 16-bit samples -> the bytes the stylizer takes (anything else: as it is)."""
@@ -471,7 +580,13 @@ class PipelinedStylizer(object):
 
     source yuv= and yuv_out= (raw video, see the module docstring) pass through to the lanes: the planes go up from and come down into the
     lanes' pinned buffers, which are sized from the descriptors' frame_bytes (two bytes per sample with bits=N); order and depth are unchanged.
-    next_input() lends the next lane's pinned input buffer to a stream reader.  compose= passes through as well; every lane uploads the mask."""
+    next_input() lends the next lane's pinned input buffer to a stream reader.  compose= passes through as well; every lane uploads the mask.
+
+    temporal= passes through too.  The recursion orders the tails, not the heads: the two state slots are shared by the lanes and indexed by
+    frame parity (with depth 3 a lane meets both), and frame n's tail waits, between its head's and its tail's replay, for an event recorded
+    right behind frame n - 1's tail on the other lane's stream; the forward passes of two frames still overlap, and frame n + 1 overwrites
+    the slot frame n reads only behind that chain.  Results equal the one-lane results, in order, for any depth.  reset() forgets the
+    previous frame and is allowed with nothing in flight."""
 
     def __init__(self, eng, variables, height, width, depth=2, jpeg_threads=4, **kw):
         if not hasattr(eng.mem, "torch"):
@@ -480,9 +595,15 @@ class PipelinedStylizer(object):
         torch = eng.mem.torch
         self.torch = torch
         self.depth = int(depth)
-        self.lanes = [FrameStylizer(eng, variables, height, width, **kw) for _ in range(self.depth)]
+        self.lanes = []
+        for _ in range(self.depth):                              # (temporal=: the first lane allocates the state slots, the others share them)
+            more = dict(kw, _temporal_slots=self.lanes[0]._tslots) if self.lanes and kw.get("temporal") is not None else kw
+            self.lanes.append(FrameStylizer(eng, variables, height, width, **more))
         self.streams = [torch.cuda.Stream() for _ in self.lanes]
         self.events = [torch.cuda.Event() for _ in self.lanes]
+        self.temporal = self.lanes[0].temporal
+        self._tail_done = [torch.cuda.Event() for _ in self.lanes] if self.temporal is not None else None
+        self._tframe = 0                                         # (temporal=) frames since construction or reset()
         self.host_in = [torch.empty(ln.in_shape, dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
         self.host_out = [torch.empty(tuple(ln._result.shape), dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
         self.jpeg = self.lanes[0].jpeg
@@ -532,14 +653,23 @@ class PipelinedStylizer(object):
                 raise L.FaststyleError("frame shape %s dtype %s, stylizer was built for uint8 %s" % (a.shape, a.dtype, ln.in_shape))
             if a.ctypes.data != self.host_in[k].data_ptr():                        # (next_input()'s buffer, filled in place: nothing to copy)
                 self.host_in[k].copy_(torch.from_numpy(np.ascontiguousarray(a)))   # (host -> pinned host; the lane's previous frame was fetched: its buffers are free)
+        before_tail = None
+        if self.temporal is not None:                             # this frame's tail follows the previous frame's, wherever that one ran
+            ln._tn = self._tframe
+            if self._tframe > 0:
+                done = self._tail_done[(self._n - 1) % self.depth]
+                before_tail = lambda: st.wait_event(done)
         st.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(st):
             if files is not None:
                 ln._upload_jpeg(staged)
-                ln._run(True)
+                ln._run(True, before_tail)
             else:
                 ln._pix_dst.copy_(self.host_in[k], non_blocking=True)
-                ln._run()
+                ln._run(False, before_tail)
+            if self.temporal is not None:
+                self._tail_done[k].record(st)
+                self._tframe += 1
             if self.jpeg is not None:
                 self.host_coef[k].copy_(ln._coef, non_blocking=True)
             else:
@@ -555,6 +685,14 @@ class PipelinedStylizer(object):
     def in_flight(self):
         """Frames submitted and not yet fetched (at most `depth`)."""
         return len(self._pending)
+
+    def reset(self):
+        """Forget the previous frame (temporal= only); with nothing in flight."""
+        if self.temporal is None:
+            raise L.FaststyleError("reset: this stylizer was built without temporal=")
+        if self._pending:
+            raise L.FaststyleError("reset: %d frames in flight -- fetch() them first" % len(self._pending))
+        self._tframe = 0
 
     def next_input(self):
         """The pinned input buffer of the lane the next submit() uses, as a numpy array of the lane's in_shape: a reader fills it in place

@@ -440,6 +440,49 @@ int fs_f32_to_yuv_deep(fs_ctx* ctx, const fs_yuv_desc* desc, const float* src, i
 int fs_compose_f32(fs_ctx* ctx, const float* src, int H, int W, const float* net, int Ho, int Wo, int N, int strength_q8, int keep_color,
                    int matrix, int bgr, const unsigned char* mask, float* dst);
 
+/* ---- Temporal stabilisation (csrc/fs_temporal.hip): a recursive, motion-compensated blend of the tensor the output conversions would read
+ * towards the previous frame's stabilised output, three launches behind the forward pass (or fs_compose_f32).  The arithmetic below is the
+ * contract (tests/test_temporal.py restates it in numpy and compares for equality); it is integer throughout, on compose's unsigned 8.8 scale.
+ *
+ * Inputs, one image per call: src [H, W, 3] fp32, the net's input; cur [Ho, Wo, 3] fp32, the net's output or the composed tensor, H <= Ho <=
+ * H + 3 and W <= Wo <= W + 3, aligned top-left.  to88 is compose's.  clampy(v) = min(max(v, 0), Ho - 1), clampx likewise with Wo.
+ *
+ *   luma       cur8 [Ho, Wo] u8: A_c = to88(src[min(y, H - 1)][min(x, W - 1)][c]); Y = (k0 A_0 + k1 A_1 + k2 A_2 + 32768) >> 16 in int64 with
+ *              compose's weight triples (matrix 0 BT.601, 1 BT.709), k0 the blue weight when src_bgr says channel 0 of src is blue;
+ *              cur8 = Y >> 8.
+ *   blocks     16 x 16, anchored top-left: nby = ceil(Ho / 16), nbx = ceil(Wo / 16); a ragged block holds only its pixels inside the frame,
+ *              npix of them.
+ *   search     needs the previous frame's luma prev8; radius R in [0, 7].  For every (dy, dx) in [-R, R]^2:
+ *                SAD  = sum over the block's pixels (y, x) of |cur8[y][x] - prev8[clampy(y + dy)][clampx(x + dx)]|
+ *                cost = SAD + (npix >> 5) (|dy| + |dx|)                                  (below 2^17)
+ *                key  = cost << 12 | (|dy| + |dx|) << 8 | (dy + 7) << 4 | (dx + 7)       (29 bits)
+ *              and the smallest key wins: mv[by][bx] = (dy, dx), two signed char.  The motion penalty keeps flat and noisy blocks at rest;
+ *              the key orders every tie: smaller motion first, then smaller dy, then smaller dx.  Without a previous frame, or with R = 0,
+ *              every vector is (0, 0).
+ *   blend      pixel p = (y, x) of block b, (dy, dx) = mv[b], q = (clampy(y + dy), clampx(x + dx)):
+ *                e    = |cur8[p] - prev8[q]|
+ *                conf = max(0, 256 - e K), the sensitivity K in [1, 256]
+ *                w    = strength_q8 conf, in [0, 65536]
+ *                B_c  = to88(cur[p][c]);  P_c = prev88[q][c], the previous frame's stabilised output as u16 on the 8.8 scale
+ *                F_c  = B_c + (((int64)(P_c - B_c) w + 32768) >> 16), the shift arithmetic (a floor)
+ *                dst[p][c] = (float)F_c * 2^-8 (exact);  out88[p][c] = F_c
+ *              Without a previous frame F_c = B_c.  F_c is a convex combination of B_c and P_c, both in [0, 65280] (w / 65536 lies in
+ *              [0, 1], and the rounding cannot pass either end), so no clamp is needed.
+ * Hence: strength_q8 0, the first frame, or e K >= 256 everywhere give F = to88(cur), and a u8 / JPEG / 8-bit or deep YCbCr conversion behind
+ * the stage writes byte for byte what it writes without it; strength_q8 256 with e = 0 gives F = P exactly.
+ *
+ * prev_luma / prev_out88: the luma / out88 a previous call wrote, both null for "no previous frame"; luma [Ho, Wo] u8, out88 [Ho, Wo, 3] u16 and
+ * mv [nby, nbx, 2] signed char are written for the next call.  dst may be cur (a thread reads its own pixels before it writes them); prev_luma
+ * and prev_out88 are read at displaced positions and may not be luma / out88.  No value read from a tensor reaches an address except through
+ * mv, which the search bounds by R and the blend holds to R again before it clamps q.  Asynchronous on the ctx stream, allocates nothing, can
+ * be captured into a hipGraph.  A refused call launches nothing.  Errors: -1 null src / cur / luma / out88 / mv / dst, exactly one of the two
+ * prev pointers null, prev_luma == luma or prev_out88 == out88, H or W below 1, Ho outside [H, H + 3] or Wo outside [W, W + 3]; -2 strength_q8
+ * outside [0, 256], sensitivity outside [1, 256], radius outside [0, 7], matrix or src_bgr other than 0 or 1; -5 src, cur or dst not 4-byte
+ * aligned, prev_out88 or out88 not 2-byte aligned. */
+int fs_temporal_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius,
+                    int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma,
+                    unsigned short* out88, signed char* mv, float* dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,12 @@ How much of the style lands: ``--style_strength S`` (0 the source, 1 the net's o
 --video_matrix with --video_in, else bt601), and ``--mask_path FILE`` (a grey image of the net's input size: 0 keeps the source pixel, 255
 stylizes it) restricts either to a region -- one more launch inside each lane's graph, on the net's fp32 tensors (faststyle_amd/stream.py,
 compose=), with every input and output flag above.  Without any of the four nothing changes; ``--style_strength 1`` alone writes the same bytes.
+
+Less flicker: ``--temporal_strength S`` (0 nothing, 1 all of it) blends every frame towards the previous stabilised frame, fetched along
+16 x 16 block motion vectors found between the two source frames (``--temporal_radius R``, 0..7 pixels) and only where the source matched
+there (``--temporal_sensitivity K``, 1..256: nothing is blended at a luma difference of 256 / K) -- three more launches per frame, on the
+net's fp32 tensors, behind the stage above (faststyle_amd/stream.py, temporal=).  The luma weights follow --color_matrix / --video_matrix.
+With --frames_dir a change of frame size starts over.  Without the flag nothing changes; ``--temporal_strength 0`` writes the same bytes.
 """
 import os
 import sys
@@ -73,6 +79,23 @@ def compose_options(args, matrix='bt601'):
     return opt
 
 
+def temporal_options(args, matrix='bt601'):
+    """--temporal_strength / --temporal_radius / --temporal_sensitivity -> the temporal= dict of the lanes (faststyle_amd/stream.py), None
+    without --temporal_strength; matrix: what --color_matrix defaults to.  A value outside its range is a SystemExit here, before anything is
+    loaded.  Every path of this script feeds the net B,G,R: the stage is told so (source_bgr)."""
+    s = getattr(args, 'temporal_strength', None)                # (the three flags are absent from the namespace unless given)
+    radius, sensitivity = getattr(args, 'temporal_radius', 7), getattr(args, 'temporal_sensitivity', 16)
+    if not 0 <= radius <= 7:
+        raise SystemExit('--temporal_radius %d is outside [0, 7]' % radius)
+    if not 1 <= sensitivity <= 256:
+        raise SystemExit('--temporal_sensitivity %d is outside [1, 256]' % sensitivity)
+    if s is None:
+        return None
+    if not 0.0 <= s <= 1.0:
+        raise SystemExit('--temporal_strength %r is outside [0, 1]' % s)
+    return dict(strength=s, sensitivity=sensitivity, radius=radius, matrix=args.color_matrix or matrix, source_bgr=True)
+
+
 def check_mask_size(args, compose, W, H):
     """SystemExit unless the mask (if any) has the net's input size W x H."""
     if compose is not None and 'mask' in compose and compose['mask'].shape != (H, W):
@@ -89,6 +112,7 @@ def run_frames_dir(args):
     if not names:
         raise SystemExit('no frames under %s' % args.frames_dir)
     compose = compose_options(args)
+    temporal = temporal_options(args)
     if compose is not None and 'mask' in compose:                # (the first frame's size, before the model is loaded; later sizes: build())
         size = args.frame_size or args.resolution
         if size is None:
@@ -110,6 +134,8 @@ def run_frames_dir(args):
     kw = dict(swap_rb=False, jpeg=dict(quality=args.output_quality, subsampling=2)) if jpg else {}
     if compose is not None:                                      # (compose_options: such lanes do not swap; the .png is then the frame as it comes)
         kw = dict(kw, swap_rb=False, compose=compose)
+    if temporal is not None:                                     # (a run of frames of another size builds a new stylizer: it starts over)
+        kw = dict(kw, temporal=temporal)
 
     def save(n, img_out):
         if jpg:
@@ -207,6 +233,7 @@ def run_video(args):
     from faststyle_amd import _lib, engine, stream, y4m
     check_video_flags(args)
     compose = compose_options(args, args.video_matrix)
+    temporal = temporal_options(args, args.video_matrix)
     to_stdout = args.video_out == '-'
     log = sys.stderr if to_stdout else sys.stdout
 
@@ -251,6 +278,8 @@ def run_video(args):
             kw.update(swap_rb=False, jpeg=dict(quality=args.output_quality, subsampling=2))
         if compose is not None:                                              # (compose_options: such lanes do not swap; the .png is then the frame as it comes)
             kw.update(swap_rb=False, compose=compose)
+        if temporal is not None:
+            kw.update(temporal=temporal)
         depth = int(os.environ.get('FS_FRAMES_IN_FLIGHT', '2')) if hasattr(eng.mem, 'torch') else 1
         if depth > 1:
             st = stream.PipelinedStylizer(eng, variables, H, W, depth=depth, upsample_method=args.upsample_method, **kw)
@@ -324,6 +353,7 @@ def run_webcam(args):
                          'it is not installed here.  Use --frames_dir to filter a directory of frames.')
     from faststyle_amd import stream
     compose = compose_options(args)
+    temporal = temporal_options(args)
     cap = cv2.VideoCapture(0)
     if args.resolution is not None:
         x_length, y_length = args.resolution
@@ -334,10 +364,11 @@ def run_webcam(args):
     check_mask_size(args, compose, x_new, y_new)
     print('Loading up model...')
     eng, variables = _load(args)
+    more = dict(temporal=temporal) if temporal is not None else {}
     if compose is not None:                                  # (compose_options: the lane does not swap, the loop below does)
-        st = stream.FrameStylizer(eng, variables, y_new, x_new, args.upsample_method, swap_rb=False, compose=compose)
+        st = stream.FrameStylizer(eng, variables, y_new, x_new, args.upsample_method, swap_rb=False, compose=compose, **more)
     else:
-        st = stream.FrameStylizer(eng, variables, y_new, x_new, args.upsample_method)
+        st = stream.FrameStylizer(eng, variables, y_new, x_new, args.upsample_method, **more)
     fourcc = cv2.VideoWriter_fourcc(*'XVID')
     out = cv2.VideoWriter('output.avi', fourcc, 15.0, (x_new, y_new))
     print('Begin filtering...')

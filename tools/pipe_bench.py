@@ -17,6 +17,10 @@ replace (HIP events around the replay of a graph of 200 launches each); written 
 that alternate in the one run -- the 8-bit stream above without and with --style_strength 0.7 --preserve_color -- plus the device time of one 720p
 launch of compose_kernel (the same graph-of-200 scheme; wide path, with and without a mask, and the narrow path); written to
 profiles/video_compose.json with the digest of the kernel sources.
+"video" with "temporal" as the fifth argument (pipe_bench.py 1280 4 video profiles/video_temporal.json temporal): the same two-leg scheme without and
+with --temporal_strength 0.6, plus the device time of one 720p call of fs_temporal_f32 (its three launches back to back, the graph-of-200 scheme:
+with a previous frame at radius 7 and 3, and a first frame); written to profiles/video_temporal.json.  "temporal_kernels" as the third argument runs
+those graphs alone: under a kernel trace that run gives the time of each of the three kernels back to back.
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -156,10 +160,33 @@ def compose_kernel_times(W=1280, H=720, launches=200):
     return res
 
 
-def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False):
+def temporal_kernel_times(W=1280, H=720, launches=200):
+    """-> dict of device microseconds per 720p call of fs_temporal_f32 (luma, search and blend kernel back to back), timed as kernel_times does:
+    a frame moved by (2, -3) against its predecessor at radius 7 and 3, and a first frame (no search, no blend)."""
+    eng = engine.Engine()
+    mem = eng.mem
+    rng = np.random.default_rng(3)
+    small = rng.uniform(0, 255, (H // 8, W // 8, 3)).astype(np.float32)
+    a = np.ascontiguousarray(np.kron(small, np.ones((8, 8, 1), np.float32)) + rng.uniform(-4, 4, (H, W, 3)).astype(np.float32))
+    src0, src1 = mem.from_numpy(a[None]), mem.from_numpy(np.roll(a, (2, -3), axis=(0, 1))[None])
+    cur = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    dst = mem.empty((1, H, W, 3))
+    s0, s1 = eng.temporal_state(H, W), eng.temporal_state(H, W)
+    eng.temporal_f32(src0, cur, dst, s0)                          # the previous frame's state
+    kw = dict(strength_q8=154, sensitivity=16, src_bgr=True)
+    res = {"temporal_radius_7": kernel_timed(lambda: eng.temporal_f32(src1, cur, dst, s1, prev=s0, radius=7, **kw), launches),
+           "temporal_radius_3": kernel_timed(lambda: eng.temporal_f32(src1, cur, dst, s1, prev=s0, radius=3, **kw), launches),
+           "temporal_first_frame": kernel_timed(lambda: eng.temporal_f32(src1, cur, dst, s1, radius=7, **kw), launches)}
+    for k, v in res.items():
+        print("video: %8.1f us per 720p call (three launches): %s" % (v, k))
+    return res
+
+
+def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False, temporal=False):
     """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json (video: with the raw-video leg, to
     profiles/video_stream.json; video with a depth: the 8-bit and the deep raw-video legs alone, to profiles/video_deep.json; video with
-    compose: the 8-bit raw-video leg without and with the compose stage, to profiles/video_compose.json)."""
+    compose / temporal: the 8-bit raw-video leg without and with that stage, to profiles/video_compose.json / video_temporal.json)."""
+    compose_flag, compose = compose, compose or temporal          # (the two stages share the two-leg scheme)
     import contextlib
     import json
     import shutil
@@ -220,6 +247,8 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=Fals
         legs = [("video_y4m_720p", "720p", None), ("video_y4m_720p_%dbit" % depth, "720p", depth)]
     if compose:
         legs = [("video_y4m_720p", "720p", None), ("video_y4m_720p_strength_0.7_preserve_color", "720p", ("--style_strength", "0.7", "--preserve_color"))]
+    if temporal:
+        legs = [("video_y4m_720p", "720p", None), ("video_y4m_720p_temporal_strength_0.6", "720p", ("--temporal_strength", "0.6"))]
     parser = stylize_webcam.setup_parser()
     out = os.path.join(d, "out")
 
@@ -281,9 +310,11 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=Fals
     shutil.rmtree(d)
     if depth:
         res["kernel_us_per_720p_launch"] = kernel_times(depth)
-    if compose:
+    if compose_flag:
         res["kernel_us_per_720p_launch"] = compose_kernel_times()
-    dst = out_json or os.path.join(root, "profiles", "video_compose.json" if compose else "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
+    if temporal:
+        res["kernel_us_per_720p_call_of_three_launches"] = temporal_kernel_times()
+    dst = out_json or os.path.join(root, "profiles", "video_temporal.json" if temporal else "video_compose.json" if compose else "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
     with open(dst, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
@@ -297,7 +328,10 @@ def main():
     if len(sys.argv) > 3 and sys.argv[3] in ("frames_in", "video"):
         fifth = sys.argv[5] if len(sys.argv) > 5 and sys.argv[3] == "video" else None
         frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video",
-                  depth=int(fifth) if fifth not in (None, "compose") else None, compose=fifth == "compose")
+                  depth=int(fifth) if fifth not in (None, "compose", "temporal") else None, compose=fifth == "compose", temporal=fifth == "temporal")
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "temporal_kernels":
+        temporal_kernel_times()
         return
     if len(sys.argv) > 3 and sys.argv[3] == "host_encode":
         host_encode(n, threads or 4)
