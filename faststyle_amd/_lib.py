@@ -27,6 +27,8 @@ FS_SRC_PLAIN, FS_SRC_REFLECT, FS_SRC_DILATE2 = 0, 1, 2
 FS_PROFILE_FAMILIES = 23
 FS_CV_INTER_CUBIC, FS_CV_INTER_AREA = 2, 3                                       # cv2.INTER_CUBIC, cv2.INTER_AREA
 FS_CVRESIZE_PATH_CUBIC, FS_CVRESIZE_PATH_AREA_FAST, FS_CVRESIZE_PATH_AREA = 0, 1, 2
+FS_RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2, "lanczos": 3}         # FS_RESAMPLE_* of include/faststyle_io.h
+FS_RESAMPLE_TILE_W, FS_RESAMPLE_LDS_ROWS = 64, 85
 
 
 def profile_family_names(lib):
@@ -80,6 +82,14 @@ class fs_cvresize_info(Structure):
                 ("interpolation", ctypes.c_int32), ("path", ctypes.c_int32), ("factor_x", ctypes.c_int32), ("factor_y", ctypes.c_int32),
                 ("x_taps", ctypes.c_int32), ("y_taps", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2),
                 ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("x_offset", c_uint64), ("y_offset", c_uint64), ("table_bytes", c_uint64)]
+
+
+class fs_resample_info(Structure):
+    """include/faststyle_io.h: what fs_resample_plan reports."""
+    _fields_ = [("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32), ("dst_h", ctypes.c_int32), ("dst_w", ctypes.c_int32),
+                ("filter", ctypes.c_int32), ("x_ksize", ctypes.c_int32), ("y_ksize", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("tile_h", ctypes.c_int32), ("tile_rows", ctypes.c_int32), ("lds_rows", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("x_offset", c_uint64), ("y_offset", c_uint64), ("table_bytes", c_uint64)]
 
 
 class fs_yuv_desc(Structure):
@@ -202,6 +212,9 @@ PROTOTYPES = {
     "fs_compose_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fs_temporal_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fs_resample_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_resample_info)]),
+    "fs_resample_tables": (c_int, [POINTER(fs_resample_info), c_void_p, c_size_t]),
+    "fs_resample_f32": (c_int, [c_void_p, POINTER(fs_resample_info), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "fs_u8_to_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "fs_f32_to_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
 }

@@ -121,4 +121,13 @@ def stylize_webcam_parser():
         ('--temporal_sensitivity', dict(default=argparse.SUPPRESS, type=int, metavar='K',
                                         help="(addition) how fast a source mismatch turns the blend off, 1..256: none of it is left at a luma "
                                              "difference of 256 / K (default 16)")),
+        ('--output_size', dict(default=argparse.SUPPRESS, nargs='+', metavar='W H|source',
+                               help="(addition) deliver every frame at W x H, or with 'source' at the stream's or first frame's own size, whatever "
+                                    "size the net runs at (--frame_size): Pillow's mode-F resampling of the net's fp32 output on the device, ahead of "
+                                    "every output conversion; with --frames_dir, --video_in and the camera")),
+        ('--output_filter', dict(default=argparse.SUPPRESS, choices=['box', 'bilinear', 'bicubic', 'lanczos'], metavar='F',
+                                 help="(addition) filter of --output_size: box, bilinear, bicubic (default) or lanczos")),
+        ('--frame_filter', dict(default=argparse.SUPPRESS, choices=['box', 'bilinear', 'bicubic', 'lanczos'], metavar='F',
+                                help="(addition) with --video_depth stream, a --video_in of 9 to 16 bits and --frame_size: resample the stream's fp32 "
+                                     "frames to W x H with this filter on the device (without it --frame_size refuses such a stream)")),
     ])

@@ -261,6 +261,19 @@ int fs_temporal_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cu
                                     dst, ctx->stream);
     return rc ? fail(rc, "fs_temporal_f32: launch failed (%d)", rc) : 0;
 }
+int fs_resample_f32(fs_ctx* ctx, const fs_resample_info* plan, const void* tables_dev, const float* src, int src_rows, int src_pitch, int N, float* dst) {
+    if (!ctx || !plan || !src || !dst) return fail(-1, "fs_resample_f32: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_resample_f32: N must be in [1, 65535], got %d", N);
+    if (!fs::resample_plan_ok(*plan)) return fail(-1, "fs_resample_f32: the plan (%dx%d -> %dx%d) was not filled by fs_resample_plan", plan->src_h, plan->src_w, plan->dst_h, plan->dst_w);
+    if (src_rows < plan->src_h || src_pitch < plan->src_w || src_rows > 32767 || src_pitch > 32767)
+        return fail(-1, "fs_resample_f32: images of %d rows with a pitch of %d pixels do not hold the plan's %dx%d source (at most 32767 each)", src_rows, src_pitch, plan->src_h, plan->src_w);
+    if (src == dst) return fail(-1, "fs_resample_f32: dst must not be src");
+    if (plan->table_bytes && !tables_dev) return fail(-1, "fs_resample_f32: null tables for a plan with %llu table bytes", (unsigned long long)plan->table_bytes);
+    if (((uintptr_t)src | (uintptr_t)dst) & 3) return fail(-5, "fs_resample_f32: src and dst must be 4-byte aligned");
+    if (plan->table_bytes && ((uintptr_t)tables_dev & 15)) return fail(-5, "fs_resample_f32: tables_dev must be 16-byte aligned");
+    const int rc = fs::resample_f32(*plan, static_cast<const unsigned char*>(tables_dev), src, src_rows, src_pitch, N, dst, ctx->stream);
+    return rc ? fail(rc, "fs_resample_f32: launch failed (%d)", rc) : 0;
+}
 int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
                   const int32_t* move_dst, int M, float* batch_out) {
     if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");

@@ -18,6 +18,7 @@ struct fs_resize_item;   // include/faststyle_io.h
 struct fs_jpeg_item;
 struct fs_jpegenc_item;
 struct fs_cvresize_info;
+struct fs_resample_info;
 struct fs_yuv_desc;
 
 namespace fs {
@@ -698,6 +699,11 @@ int compose_f32(const float* src, int H, int W, const float* net, int Ho, int Wo
 int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius, int matrix, int src_bgr,
                  const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma, unsigned short* out88, signed char* mv,
                  float* dst, hipStream_t s);
+// resampling between fp32 tensors (fs_resample.hip): whether a plan is what fs_resample_plan fills, and the one launch (argument checks are in
+// fs_api.hip)
+bool resample_plan_ok(const ::fs_resample_info& plan);
+int resample_f32(const ::fs_resample_info& plan, const unsigned char* tables, const float* src, int src_rows, int src_pitch, int N, float* dst,
+                 hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);
 // ... with the per-sample sums taken from records [N][T][C][2] (rec == nullptr: computed here into `scratch`), reduced in the apply kernel's

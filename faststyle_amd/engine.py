@@ -206,6 +206,56 @@ class CvResizeHost(object):
         return CvResizePlan(info, tables)
 
 
+class ResamplePlan(object):
+    """One planned fp32 resampling (fs_resample_plan): ``info`` the library's fs_resample_info, ``tables`` its per-axis tables on the host
+    (uint8), and -- once an engine has run it -- the device copy of the tables, uploaded once per plan."""
+
+    def __init__(self, info, tables, filter):
+        self.info = info
+        self.tables = tables
+        self.tables_dev = None
+        self.filter = filter
+        self.src_shape = (int(info.src_h), int(info.src_w))
+        self.dst_shape = (int(info.dst_h), int(info.dst_w))
+        self.tile_h = int(info.tile_h)
+
+    def axis_table(self, axis):
+        """One axis table ('x' or 'y') as (xmin [n_dst] int32, cnt [n_dst] int32, w [n_dst, ksize] float64); None for an axis that keeps
+        its length."""
+        i = self.info
+        n_dst, off, ksize = (i.dst_w, i.x_offset, i.x_ksize) if axis == "x" else (i.dst_h, i.y_offset, i.y_ksize)
+        if ksize == 0:
+            return None
+        rows = self.tables[off:off + n_dst * (8 + 8 * ksize)].view(np.dtype([("xmin", "<i4"), ("cnt", "<i4"), ("w", "<f8", (ksize,))]))
+        return rows["xmin"].copy(), rows["cnt"].copy(), rows["w"].copy()
+
+
+class ResampleHost(object):
+    """The host calls of the fp32 resampler (csrc/fs_resample.hip): plan and tables.  They need the library and no device."""
+
+    def __init__(self, lib=None):
+        self.lib = lib if lib is not None else L.load()
+
+    def resample_plan(self, Hs, Ws, Hd, Wd, filter="bicubic"):
+        """fs_resample_plan + fs_resample_tables of Pillow's Image.resize((Wd, Hd), filter) on mode-F images of Hs x Ws: a ResamplePlan.
+        filter: 'box', 'bilinear', 'bicubic' or 'lanczos'.  A refused request raises FaststyleError."""
+        code = L.FS_RESAMPLE_FILTERS.get(filter)
+        if code is None:
+            raise L.FaststyleError("resample filter is one of %s, got %r" % (", ".join(sorted(L.FS_RESAMPLE_FILTERS)), filter))
+        try:
+            sizes = [int(v) for v in (Hs, Ws, Hd, Wd)]
+            if any(a != b for a, b in zip(sizes, (Hs, Ws, Hd, Wd))):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise L.FaststyleError("resample sizes must be whole numbers, got %r" % ((Hs, Ws, Hd, Wd),))
+        info = L.fs_resample_info()
+        L.check(self.lib, self.lib.fs_resample_plan(sizes[0], sizes[1], sizes[2], sizes[3], code, ctypes.byref(info)), "fs_resample_plan")
+        tables = np.zeros(int(info.table_bytes) // 8, np.float64).view(np.uint8)          # (8-byte aligned)
+        L.check(self.lib, self.lib.fs_resample_tables(ctypes.byref(info), ctypes.c_void_p(tables.ctypes.data) if tables.size else None,
+                                                      tables.nbytes), "fs_resample_tables")
+        return ResamplePlan(info, tables, filter)
+
+
 class YuvHost(object):
     """The host call of the planar YCbCr kernels (csrc/fs_yuv.hip): the frame geometry.  It needs the library and no device."""
 
@@ -228,7 +278,7 @@ class YuvHost(object):
         return desc
 
 
-class Engine(JpegHost, CvResizeHost, YuvHost):
+class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
     # Workspaces are cached per shape (a backward must find the workspace its forward filled; a captured hipGraph replays raw
     # pointers into its own).  The cache is bounded by BYTES, least recently used first: stylizing a directory of mixed
     # resolutions must not pile up one multi-GB workspace per size.  Entries a live hipGraph replays into are pinned by
@@ -945,6 +995,24 @@ class Engine(JpegHost, CvResizeHost, YuvHost):
                                                   (1 if bgr else 0) + (2 if src_swapped else 0),
                                                   None if mask is None else self.mem.ptr_u8(mask), self.mem.ptr(dst)),
                 "fs_compose_f32")
+        return dst
+
+    # ------------------------------------------------------------------ resampling between fp32 tensors (csrc/fs_resample.hip)
+    def resample_f32(self, src, plan, dst):
+        """fs_resample_f32: src device float32 [Hs,Ws,3] / [N,Hs,Ws,3] -> dst device float32 [Hd,Wd,3] / [N,Hd,Wd,3], Pillow's resize of
+        mode-F images per channel with the plan's filter.  The crop form: a source [N,R,P,3] / [R,P,3] with R >= Hs and P >= Ws, whose
+        top-left Hs x Ws is read and whose margin never is.  The plan's tables go to the device on its first use."""
+        self._sync_stream()
+        ss, ds = tuple(int(d) for d in src.shape), tuple(int(d) for d in dst.shape)
+        Hs, Ws = plan.src_shape
+        if len(ss) not in (3, 4) or len(ds) != len(ss) or ss[-1] != 3 or ds[-3:] != plan.dst_shape + (3,) or ss[-3] < Hs or ss[-2] < Ws or \
+                (len(ss) == 4 and ss[0] != ds[0]):
+            raise L.FaststyleError("resample_f32: source %s / destination %s do not fit the plan %s -> %s" % (ss, ds, plan.src_shape, plan.dst_shape))
+        if plan.tables_dev is None and plan.tables.size:
+            plan.tables_dev = self.mem.upload_u8(plan.tables)
+        tab = self.mem.ptr_u8(plan.tables_dev) if plan.tables_dev is not None else None
+        L.check(self.lib, self.lib.fs_resample_f32(self.ctx, ctypes.byref(plan.info), tab, self.mem.ptr(src), ss[-3], ss[-2],
+                                                   ss[0] if len(ss) == 4 else 1, self.mem.ptr(dst)), "fs_resample_f32")
         return dst
 
     # ------------------------------------------------------------------ temporal stabilisation (csrc/fs_temporal.hip)

@@ -53,6 +53,16 @@ state slots (luma, the output on the 8.8 scale, the vectors): frame n reads slot
 pointers and "no previous frame" is a launch argument, so such a lane's pass is captured in pieces: the head (input conversions, forward,
 compose) as before, and the tail (the stage and the output conversions) once per parity and once for a first frame, each when it first
 occurs.  ``reset()`` forgets the previous frame.  Without ``temporal=`` nothing is allocated or launched and the one graph is captured whole.
+
+Delivery at another size: with ``deliver=dict(height=, width=, filter='bicubic')`` one launch ahead of the output conversions (fs_resample_f32,
+csrc/fs_resample.hip) resamples the top-left H x W of the tensor they would read -- the net's output, the composed or the stabilised tensor --
+into a delivery tensor of the lane's own, in Pillow's mode-F arithmetic (``filter`` 'box', 'bilinear', 'bicubic' or 'lanczos'), and every
+output conversion reads that tensor: the u8 frame, the JPEG file and the YCbCr planes have the delivery size (``delivery_shape``), while
+``out_shape``, compose, temporal and their state stay on the net's grid.  The stage is part of the output conversions, so it lies in the
+whole-pass graph and in every temporal tail graph.  ``source=dict(..., resample='bicubic')`` is its counterpart on the input side for sources
+of 9 to 16 bits per sample: the planes are converted at the source's own size into an fp32 tensor of the lane's and resampled into the net's
+input; it is the only way such a source of another size than the net's is taken, and 8-bit sources are refused with it (``interpolation=``
+serves them).  Without the keys nothing is allocated or launched.
 """
 import ctypes
 
@@ -80,7 +90,8 @@ class FrameStylizer(object):
     KEEP_GRAPH = False     # tests: keep the captured hipGraph_t so that its node types can be inspected
 
     def __init__(self, eng, variables, height, width, upsample_method="resize", batch=1, swap_rb=True, use_graph=True,
-                 bf16=False, jpeg=None, jpeg_threads=4, source=None, yuv_out=None, compose=None, temporal=None, _temporal_slots=None):
+                 bf16=False, jpeg=None, jpeg_threads=4, source=None, yuv_out=None, compose=None, temporal=None, deliver=None,
+                 _temporal_slots=None):
         self.eng = eng
         self.variables = variables
         self.method = upsample_method
@@ -90,9 +101,15 @@ class FrameStylizer(object):
         mem = eng.mem
         Ho, Wo = eng.tnet_out_shape(height, width)
         self.out_shape = (int(batch), Ho, Wo, 3)
+        self.delivery_shape = self.out_shape   # the frames the output conversions write; with deliver=: (batch, height, width, 3) of the delivery
+        self.deliver = None              # with deliver=: dict(height=, width=, filter=)
+        self._deliver_plan = None        # ... the plan from the top-left H x W of the net's Ho x Wo output to the delivery size
+        self._delivered = None           # ... and the delivery tensor every output conversion then reads
+        if deliver is not None:
+            self._deliver_setup(dict(deliver))
         self._in_u8 = mem.upload_u8(np.zeros(self.shape, np.uint8))
         self._in_f32 = mem.empty(self.shape)
-        self._out_u8 = mem.upload_u8(np.zeros(self.out_shape, np.uint8))
+        self._out_u8 = mem.upload_u8(np.zeros(self.delivery_shape, np.uint8))
         self._graph = None
         # A workspace of this stylizer's OWN: with frozen=True the re-laid-out filters of self.variables live inside it and the captured
         # graph no longer rebuilds them -- nobody else may write there (the engine's shared per-shape workspace would be rewritten by any
@@ -121,6 +138,8 @@ class FrameStylizer(object):
         self._src_host = None
         self._src_yuv = None
         self._src_deep = False           # source yuv= with bits above 8: the conversion writes the net's fp32 input itself
+        self._src_rplan = None           # source resample= at another size than the net's: the plan from the source size to the net's
+        self._src_f32 = None             # ... and the deep source converted at its own size
         if source is not None:
             self._source_setup(dict(source))
         self.compose = None              # with compose=: dict(strength_q8=, keep_color=, matrix=, mask=, source_swapped=) as the launch takes them
@@ -136,6 +155,28 @@ class FrameStylizer(object):
         self._tail_graphs = {}           # ... captured tails by the parity written (None: a first frame's)
         if temporal is not None:
             self._temporal_setup(dict(temporal), _temporal_slots)
+
+    DELIVER_KEYS = ("height", "width", "filter")
+
+    def _deliver_setup(self, opt):
+        """The delivery stage's fixed parts: the checked size and filter, the plan and the lane's own delivery tensor."""
+        kw = {k: opt.pop(k) for k in self.DELIVER_KEYS if k in opt}
+        if opt:
+            raise L.FaststyleError("deliver takes %s, got also %r" % (", ".join(self.DELIVER_KEYS), opt))
+        if "height" not in kw or "width" not in kw:
+            raise L.FaststyleError("deliver needs height and width, got %r" % kw)
+        size = []
+        for name in ("height", "width"):
+            v = kw[name]
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise L.FaststyleError("deliver %s must be a whole number of at least 1, got %r" % (name, v))
+            size.append(int(v))
+        filt = kw.get("filter", "bicubic")
+        B, H, W, _ = self.shape
+        self._deliver_plan = self.eng.resample_plan(H, W, size[0], size[1], filt)      # (an unknown filter or a refused plan raises)
+        self.deliver = dict(height=size[0], width=size[1], filter=filt)
+        self.delivery_shape = (B, size[0], size[1], 3)
+        self._delivered = self.eng.mem.empty(self.delivery_shape)
 
     TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr")
 
@@ -204,7 +245,7 @@ class FrameStylizer(object):
 
     def _yuv_out_setup(self, opt):
         """The output side's colour conversion: the descriptor of one output frame and the device buffer of the batch's planes."""
-        B, Ho, Wo, _ = self.out_shape
+        B, Ho, Wo, _ = self.delivery_shape
         self.yuv_out_desc, kw = self._yuv_desc(opt, Wo, Ho, "yuv_out")
         self.yuv_out = kw
         self._out_deep = int(self.yuv_out_desc.reserved[0]) != 0
@@ -221,8 +262,12 @@ class FrameStylizer(object):
             raise L.FaststyleError("source needs height and width, got %r" % opt)
         interpolation, swap, jp = opt.pop("interpolation", None), bool(opt.pop("swap_rb", False)), opt.pop("jpeg", None)
         yuv = opt.pop("yuv", None)
+        has_resample = "resample" in opt
+        resample = opt.pop("resample", None)
         if opt:
-            raise L.FaststyleError("source takes height, width, interpolation, swap_rb, jpeg and yuv, got also %r" % opt)
+            raise L.FaststyleError("source takes height, width, interpolation, swap_rb, jpeg, yuv and resample, got also %r" % opt)
+        if has_resample and resample not in L.FS_RESAMPLE_FILTERS:
+            raise L.FaststyleError("source resample is one of %s, got %r" % (", ".join(sorted(L.FS_RESAMPLE_FILTERS)), resample))
         self.source = dict(height=Hs, width=Ws, interpolation=interpolation, swap_rb=swap, jpeg=None if jp is None else dict(jp))
         self._src_swap = swap
         if yuv is not None:
@@ -230,6 +275,17 @@ class FrameStylizer(object):
                 raise L.FaststyleError("source jpeg= and yuv= are mutually exclusive: the frames of a stylizer have one form")
             self._src_yuv, self.source["yuv"] = self._yuv_desc(yuv, Ws, Hs, "source yuv")
             self._src_deep = int(self._src_yuv.reserved[0]) != 0
+            if has_resample and not self._src_deep:
+                raise L.FaststyleError("source resample= takes sources of 9 to 16 bits per sample only: an 8-bit source is resized by "
+                                       "interpolation= (cv2.resize on the u8 frames)")
+            if self._src_deep and has_resample:
+                self.source["resample"] = resample
+                self.in_shape = (B, int(self._src_yuv.frame_bytes))
+                self._pix_dst = mem.upload_u8(np.zeros(self.in_shape, np.uint8))
+                if (Hs, Ws) != (H, W):                       # converted at its own size, then resampled into the net's fp32 input
+                    self._src_rplan = e.resample_plan(Hs, Ws, H, W, resample)
+                    self._src_f32 = mem.empty((B, Hs, Ws, 3))
+                return
             if self._src_deep and (Hs, Ws) != (H, W):
                 raise L.FaststyleError("a source of %d bits per sample has the net's size %dx%d, got %dx%d: the resize takes 8-bit frames only" %
                                        (self._src_yuv.reserved[0], H, W, Hs, Ws))
@@ -241,6 +297,9 @@ class FrameStylizer(object):
                     raise L.FaststyleError("source %dx%d does not resize to %dx%d but to %dx%d" % ((Hs, Ws, H, W) + self._src_plan.dst_shape))
                 self._src_rgbx = mem.upload_u8(np.zeros((B, Hs, Ws, 4), np.uint8))
             return
+        if has_resample:
+            raise L.FaststyleError("source resample= takes sources of 9 to 16 bits per sample only (yuv= with bits=): 8-bit frames are resized by "
+                                   "interpolation= (cv2.resize on the u8 frames)")
         self.in_shape = (B, Hs, Ws, 3)
         if (Hs, Ws) != (H, W) or swap:
             self._src_plan = e.cvresize_plan(Hs, Ws, W / float(Ws), H / float(Hs), interpolation)
@@ -311,7 +370,7 @@ class FrameStylizer(object):
         if opt or sub not in self.SUBSAMPLING or not 1 <= quality <= 100:
             raise L.FaststyleError("jpeg takes quality (1..100) and subsampling (0, 1, 2), got %r" % dict(opt, quality=quality, subsampling=sub))
         e, mem = self.eng, self.eng.mem
-        B, Ho, Wo, _ = self.out_shape
+        B, Ho, Wo, _ = self.delivery_shape
         rc, info = e.jpeg_encode_plan(Wo, Ho, 3, *self.SUBSAMPLING[sub])
         L.check(e.lib, rc, "fs_jpeg_encode_plan")
         self.jpeg = dict(quality=quality, subsampling=sub)
@@ -335,7 +394,7 @@ class FrameStylizer(object):
 
     def _write_all(self, coef_addr, pool=None):
         """The files of the batch, in order; on ``pool`` (a ThreadPoolExecutor) when there is more than one."""
-        B = self.out_shape[0]
+        B = self.delivery_shape[0]
         if B == 1 or pool is None:
             return [self._write_one(coef_addr, b) for b in range(B)]
         return list(pool.map(lambda b: self._write_one(coef_addr, b), range(B)))
@@ -349,7 +408,10 @@ class FrameStylizer(object):
             else:
                 e.jpeg_reconstruct_many(self._src_coef, self._sitems, self._in_u8, items_dev=(self._sitems_dev, 0))
         elif self._src_yuv is not None:                      # the planes of the frame(s) are in self._pix_dst
-            if self._src_deep:                               # 16-bit samples: straight to the net's fp32 input
+            if self._src_rplan is not None:                  # 16-bit samples of another size: fp32 at the source's size, resampled to the net's
+                e.yuv_deep_to_f32(self._pix_dst, self._src_yuv, self._src_f32, swap_rb=self._src_swap)
+                e.resample_f32(self._src_f32, self._src_rplan, self._in_f32)
+            elif self._src_deep:                             # 16-bit samples: straight to the net's fp32 input
                 e.yuv_deep_to_f32(self._pix_dst, self._src_yuv, self._in_f32, swap_rb=self._src_swap)
             elif self._src_plan is not None:
                 e.yuv_to_rgb_u8(self._pix_dst, self._src_yuv, self._src_rgbx)
@@ -373,8 +435,11 @@ class FrameStylizer(object):
         self._outputs(y)
 
     def _outputs(self, y):
-        """The output conversions of y: the net's output, the composed or the stabilised tensor."""
+        """The output conversions of y: the net's output, the composed or the stabilised tensor; with deliver= of its top-left H x W
+        resampled to the delivery size."""
         e = self.eng
+        if self._deliver_plan is not None:
+            y = e.resample_f32(e.mem.view(y, 0, self.out_shape), self._deliver_plan, self._delivered)
         if self._out_deep:                                   # 16-bit samples: straight from the net's fp32 output
             e.f32_to_yuv_deep(y, self.yuv_out_desc, self._result, swap_rb=self.swap_rb)
             return
@@ -503,6 +568,15 @@ class FrameStylizer(object):
         if self._y is None:
             raise L.FaststyleError("stabilised_output: this stylizer has not run a frame yet")
         return np.array(self.eng.mem.to_numpy(self._stab), dtype=np.float32, copy=True)
+
+    def delivered_output(self):
+        """For tests and inspection: a host float32 copy [B,Hd,Wd,3] of the delivery tensor of the last pass (synchronises); a stylizer built
+        without deliver= has none."""
+        if self._delivered is None:
+            raise L.FaststyleError("delivered_output: this stylizer was built without deliver=")
+        if self._y is None:
+            raise L.FaststyleError("delivered_output: this stylizer has not run a frame yet")
+        return np.array(self.eng.mem.to_numpy(self._delivered), dtype=np.float32, copy=True)
 
     def motion_vectors(self):
         """For tests and inspection: the block vectors (dy, dx) of the last pass, host int8 [ceil(Ho / 16), ceil(Wo / 16), 2] (synchronises)."""

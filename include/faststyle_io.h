@@ -483,6 +483,75 @@ int fs_temporal_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cu
                     int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma,
                     unsigned short* out88, signed char* mv, float* dst);
 
+/* ---- Resampling between fp32 tensors (csrc/fs_resample.hip): the net's (or composed, or stabilised) output at a delivery size, a deep
+ * source's fp32 planes at the net's size; no u8 stage on either path.  The arithmetic below is the contract: it is Pillow's Image.resize on
+ * mode-F images (double coefficients, double accumulation, a float32 result), and tests/test_resample.py restates it in numpy, holds the
+ * restatement to Pillow and the kernel to the restatement, for equality.  A host-only plan, host-only tables, one asynchronous device call.
+ *
+ * Per axis, for the source length n_in, the destination length n_out and a filter f of support s:
+ *   box       s = 0.5   f(x) = 1 for -0.5 < x <= 0.5
+ *   bilinear  s = 1     f(x) = 1 - |x| for |x| < 1
+ *   bicubic   s = 2     a = -0.5; |x| < 1: ((a + 2)|x| - (a + 3)) |x| |x| + 1; |x| < 2: (((|x| - 5)|x| + 8)|x| - 4) a
+ *   lanczos   s = 3     sinc(x) sinc(x / 3) for -3 <= x < 3; sinc(0) = 1, otherwise sin(pi x) / (pi x) with pi x rounded first
+ *   and f = 0 elsewhere.
+ * Tables, all in double, every operation rounded on its own (no fused multiply-add):
+ *   scale = n_in / n_out;  fscale = max(scale, 1);  support = s * fscale;  inv = 1 / fscale;  ksize = 2 * (int)ceil(support) + 1
+ *   for the output index d:  center = (d + 0.5) * scale
+ *     xmin = max(0, (int)(center - support + 0.5));  xmax = min(n_in, (int)(center + support + 0.5));  cnt = xmax - xmin
+ *     w_k = f((k + xmin - center + 0.5) * inv) for k in [0, cnt);  ww = the sum of the w_k in order of k, from 0.0;  w_k = w_k / ww when ww != 0
+ * A pass: out = (float)(sum over k of (double)in[xmin + k] * w_k), the sum from 0.0 in order of k, the product and the sum rounded separately.
+ * The horizontal pass runs first and its result is rounded to float32; the vertical pass runs on those float32 values.  A pass whose axis
+ * does not change length is skipped (not run with unit weights: NaN and infinities pass through it untouched).  Channels are independent.
+ * Nothing is clamped: a bicubic overshoots a 0 | 255 step to about -19 and 274, and the output conversions clamp. */
+
+#define FS_RESAMPLE_BOX 0
+#define FS_RESAMPLE_BILINEAR 1
+#define FS_RESAMPLE_BICUBIC 2
+#define FS_RESAMPLE_LANCZOS 3
+#define FS_RESAMPLE_TILE_W 64         /* destination columns of a workgroup's tile */
+#define FS_RESAMPLE_LDS_ROWS 85       /* most source rows a tile keeps in LDS: 85 rows of 64 pixels of 3 float32 are 65280 bytes */
+
+/* What fs_resample_plan reports.  The tables of the two axes share one buffer of table_bytes bytes, the x axis at x_offset and the y axis at
+ * y_offset (multiples of 16): per output index 8 + 8 ksize bytes, {int32 xmin, int32 cnt} and then ksize doubles, w_k for k < cnt and 0.0 behind
+ * them.  An axis that keeps its length has ksize 0 and no table; with both kept table_bytes is 0 and the call copies.
+ * The kernel's geometry: one 256-thread workgroup per tile of FS_RESAMPLE_TILE_W destination columns by tile_h destination rows of one image;
+ * tile_rows is the largest number of source rows the vertical taps of one tile span (tile_h when the y axis is kept), and tile_h is the largest
+ * of 16, 8, 4, 2, 1 with tile_rows <= FS_RESAMPLE_LDS_ROWS; lds_rows (16, 40 or 85) is the row capacity of the kernel instance launched, the
+ * smallest that holds tile_rows.  No implicit padding: 12 int32, then uint64. */
+typedef struct fs_resample_info {
+    int32_t src_h, src_w;
+    int32_t dst_h, dst_w;
+    int32_t filter;                    /* FS_RESAMPLE_* */
+    int32_t x_ksize, y_ksize;          /* tap capacity per output index: 2 ceil(support) + 1; 0 for an axis that keeps its length */
+    int32_t tile_w, tile_h;
+    int32_t tile_rows, lds_rows;
+    int32_t reserved;
+    uint64_t x_offset, y_offset;
+    uint64_t table_bytes;
+} fs_resample_info;
+
+/* Plans the resampling of src_h x src_w images to dst_h x dst_w.  Host only: no HIP call, no global state, no allocation.  Equal sizes are
+ * taken and give a copy.  Errors: -1 null plan / a side outside [1, 32767]; -2 a filter other than the four above, or a vertical shrink one of
+ * whose output rows takes more than FS_RESAMPLE_LDS_ROWS source rows (cnt > 85 on the y axis).  cnt is at most 2 s scale + 2, so a vertical
+ * shrink by up to 83 (box), 41 (bilinear), 20 (bicubic) and 13 (lanczos) is always taken; the horizontal factor and any enlargement are
+ * free. */
+int fs_resample_plan(int src_h, int src_w, int dst_h, int dst_w, int filter, fs_resample_info* plan);
+
+/* Writes the plan's tables into tables[0, plan->table_bytes), in the arithmetic above.  Host only.  Errors: -1 null argument (tables may be
+ * null when table_bytes is 0) / a plan fs_resample_plan did not fill / cap < table_bytes, -5 tables not 8-byte aligned. */
+int fs_resample_tables(const fs_resample_info* plan, void* tables, size_t cap);
+
+/* Resamples N images of 3-channel fp32.  Image n starts at src + n * src_rows * src_pitch * 3 and its row y at + y * src_pitch * 3, with
+ * src_rows >= src_h and src_pitch >= src_w: the top-left src_h x src_w of larger images is read and the margin never is.  dst is packed
+ * [N, dst_h, dst_w, 3] and must not overlap src.  tables_dev: the device copy of what fs_resample_tables wrote (may be null when table_bytes is
+ * 0).  Asynchronous on the ctx stream, allocates nothing, can be captured into a hipGraph.  The kernel clamps every table entry into the source
+ * itself (xmin into [0, n_in - 1], cnt into [0, min(ksize, n_in - xmin)]) and every LDS row index into its array: a stale or wrong table gives
+ * wrong pixels, nothing else.  A refused call launches nothing.
+ * Errors: -1 null ctx / plan / src / dst, null tables_dev with table_bytes > 0, N outside [1, 65535], src_rows < src_h or src_pitch < src_w or
+ * either above 32767, a plan fs_resample_plan did not fill, dst == src; -5 src or dst not 4-byte aligned, tables_dev not 16-byte aligned. */
+int fs_resample_f32(fs_ctx* ctx, const fs_resample_info* plan, const void* tables_dev, const float* src, int src_rows, int src_pitch, int N,
+                    float* dst);
+
 #ifdef __cplusplus
 }
 #endif

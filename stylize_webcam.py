@@ -22,7 +22,7 @@ frame's planes into pinned memory and writes the result's planes, nothing else. 
 siting and range at the net's output size.  ``--video_in`` without ``--video_out`` writes 000000.png, 000001.png ... (or .jpg) to --output_dir.
 Deep video: ``--video_depth stream`` takes the stream at its own depth (C420p10, C422p10, C444p12 ... up to 16 bits; the default ``8`` refuses
 them) and ``--video_out_depth N`` writes N bits (default: the input's); above 8 bits the planes go straight to and from the net's fp32 tensors,
-without a u8 stage on that side.  ``--frame_size`` does not take a deep input.
+without a u8 stage on that side.  ``--frame_size`` takes a deep input only with ``--frame_filter`` (below).
 
 How much of the style lands: ``--style_strength S`` (0 the source, 1 the net's output) blends every stylized frame back towards its source,
 ``--preserve_color`` keeps the source's colours under the stylized luminance (``--color_matrix`` names the luma weights; the default is
@@ -35,6 +35,13 @@ Less flicker: ``--temporal_strength S`` (0 nothing, 1 all of it) blends every fr
 there (``--temporal_sensitivity K``, 1..256: nothing is blended at a luma difference of 256 / K) -- three more launches per frame, on the
 net's fp32 tensors, behind the stage above (faststyle_amd/stream.py, temporal=).  The luma weights follow --color_matrix / --video_matrix.
 With --frames_dir a change of frame size starts over.  Without the flag nothing changes; ``--temporal_strength 0`` writes the same bytes.
+
+Deliver at any size: ``--output_size W H`` (or ``--output_size source``: the stream's or the first frame's own size) resamples every result
+from the net's size to that size on the device -- Pillow's mode-F arithmetic on the net's fp32 output (or the blended / stabilised tensor),
+``--output_filter`` box, bilinear, bicubic (default) or lanczos, one launch ahead of the output conversions (faststyle_amd/stream.py,
+deliver=) -- so ``--frame_size 1280 720 --output_size source`` runs the net at 720p on a 2160p stream and writes 2160p.  The .png / .jpg
+files, the YUV4MPEG2 header and deep outputs carry that size.  ``--frame_filter F`` lets ``--frame_size`` take a ``--video_depth stream`` input
+of 9 to 16 bits: its fp32 frames are resampled to the net's size the same way (source resample=), with no u8 stage.
 """
 import os
 import sys
@@ -96,6 +103,39 @@ def temporal_options(args, matrix='bt601'):
     return dict(strength=s, sensitivity=sensitivity, radius=radius, matrix=args.color_matrix or matrix, source_bgr=True)
 
 
+def delivery_options(args):
+    """--output_size / --output_filter -> (size, filter) with size (W, H) or 'source', None without --output_size.  The flags are absent from
+    the namespace unless given.  A malformed size, or --output_filter alone, is a SystemExit here, before anything is loaded."""
+    size, filt = getattr(args, 'output_size', None), getattr(args, 'output_filter', None)
+    if size is None:
+        if filt is not None:
+            raise SystemExit('--output_filter needs --output_size')
+        return None
+    if list(size) == ['source']:
+        return 'source', filt or 'bicubic'
+    try:
+        if len(size) != 2:
+            raise ValueError
+        W, H = (int(v) for v in size)
+    except ValueError:
+        raise SystemExit("--output_size takes W H or 'source', got %s" % ' '.join(size))
+    if W < 1 or H < 1:
+        raise SystemExit('--output_size %d %d: both sides must be at least 1' % (W, H))
+    return (W, H), filt or 'bicubic'
+
+
+def deliver_dict(delivery, source_size, net_size):
+    """The deliver= dict of the lanes for delivery_options' answer (source_size, net_size: (W, H)); the resampling plan is checked here, on the
+    host: a size the kernel does not take is a SystemExit."""
+    from faststyle_amd import _lib, engine
+    W, H = source_size if delivery[0] == 'source' else delivery[0]
+    try:
+        engine.ResampleHost().resample_plan(net_size[1], net_size[0], H, W, delivery[1])
+    except _lib.FaststyleError as e:
+        raise SystemExit('--output_size %d %d: %s' % (W, H, e))
+    return dict(height=H, width=W, filter=delivery[1])
+
+
 def check_mask_size(args, compose, W, H):
     """SystemExit unless the mask (if any) has the net's input size W x H."""
     if compose is not None and 'mask' in compose and compose['mask'].shape != (H, W):
@@ -113,12 +153,19 @@ def run_frames_dir(args):
         raise SystemExit('no frames under %s' % args.frames_dir)
     compose = compose_options(args)
     temporal = temporal_options(args)
-    if compose is not None and 'mask' in compose:                # (the first frame's size, before the model is loaded; later sizes: build())
-        size = args.frame_size or args.resolution
-        if size is None:
+    delivery = delivery_options(args)
+    first_size = None
+    if delivery is not None or (compose is not None and 'mask' in compose and (args.frame_size or args.resolution) is None):
+        try:
             with Image.open(os.path.join(args.frames_dir, names[0])) as im:
-                size = im.size
-        check_mask_size(args, compose, *size)
+                first_size = im.size
+        except (IOError, OSError) as e:
+            raise SystemExit('%s: %s' % (os.path.join(args.frames_dir, names[0]), e))
+    if compose is not None and 'mask' in compose:                # (the first frame's size, before the model is loaded; later sizes: build())
+        check_mask_size(args, compose, *(args.frame_size or args.resolution or first_size))
+    if delivery is not None:                                     # ('source': the first frame's own size, for every frame; checked before the model is loaded)
+        delivery = (tuple(first_size) if delivery[0] == 'source' else delivery[0], delivery[1])
+        deliver_dict(delivery, first_size, tuple(args.frame_size or args.resolution or first_size))
     eng, variables = _load(args)
     if not os.path.isdir(args.output_dir):
         os.makedirs(args.output_dir)
@@ -182,6 +229,9 @@ def run_frames_dir(args):
         print('Resolution is: {0} by {1}'.format(W, H))
         check_mask_size(args, compose, W, H)
         more = dict(kw, source=source) if source is not None else kw
+        if delivery is not None:
+            more = dict(more, deliver=deliver_dict(delivery, (Ws, Hs), (W, H)))
+            print('Output size is: {0} by {1}'.format(*delivery[0]))
         if depth > 1:
             return stream.PipelinedStylizer(eng, variables, H, W, depth=depth, upsample_method=args.upsample_method, **more)
         return stream.FrameStylizer(eng, variables, H, W, args.upsample_method, **more)
@@ -225,6 +275,11 @@ def check_video_flags(args):
         raise SystemExit('--video_in and --frames_dir are mutually exclusive: frames come from one place')
     if args.video_in is not None and args.resolution is not None:
         raise SystemExit('--video_in and --resolution are mutually exclusive: --resolution is a PIL resize of image files; use --frame_size W H')
+    if getattr(args, 'frame_filter', None) is not None:
+        if args.video_in is None or args.video_depth != 'stream':
+            raise SystemExit('--frame_filter resamples the fp32 frames of a deep stream: it needs --video_in and --video_depth stream')
+        if args.frame_size is None:
+            raise SystemExit('--frame_filter needs --frame_size W H: it is the filter of that resize')
 
 
 def run_video(args):
@@ -234,6 +289,8 @@ def run_video(args):
     check_video_flags(args)
     compose = compose_options(args, args.video_matrix)
     temporal = temporal_options(args, args.video_matrix)
+    delivery = delivery_options(args)
+    frame_filter = getattr(args, 'frame_filter', None)
     to_stdout = args.video_out == '-'
     log = sys.stderr if to_stdout else sys.stdout
 
@@ -254,7 +311,10 @@ def run_video(args):
         colour_in = dict(colour, bits=fmt.bits) if fmt.bits != 8 else colour       # (an 8-bit stream runs exactly as without --video_depth)
         out_bits = fmt.bits if args.video_out_depth is None else args.video_out_depth
         colour_out = dict(colour, bits=out_bits) if out_bits != 8 else colour
-        if fmt.bits != 8 and args.frame_size is not None:
+        if frame_filter is not None and fmt.bits == 8:
+            raise SystemExit('--video_in %s: --frame_filter takes a stream of 9 to 16 bits per sample, this one has 8: --frame_size resizes it '
+                             'with cv2.resize\'s resampling' % args.video_in)
+        if fmt.bits != 8 and args.frame_size is not None and frame_filter is None:
             raise SystemExit('--video_in %s: --frame_size does not take a stream of %d bits per sample: the resize is 8-bit only' %
                              (args.video_in, fmt.bits))
         try:
@@ -265,12 +325,33 @@ def run_video(args):
             raise SystemExit('--video_in %s: %s' % (args.video_in, e))
         W, H = args.frame_size if args.frame_size is not None else (Ws, Hs)
         check_mask_size(args, compose, W, H)
+        deliver = None
+        if delivery is not None:                                             # (a size the kernel or the output layout does not take: said before the model is loaded)
+            deliver = deliver_dict(delivery, (Ws, Hs), (W, H))
+            try:
+                if args.video_out is not None:
+                    engine.YuvHost().yuv_plan(deliver['width'], deliver['height'], **colour_out)
+                if frame_filter is not None and (W, H) != (Ws, Hs):
+                    engine.ResampleHost().resample_plan(Hs, Ws, H, W, frame_filter)
+            except _lib.FaststyleError as e:
+                raise SystemExit('--output_size %d %d: %s' % (deliver['width'], deliver['height'], e))
+        elif frame_filter is not None and (W, H) != (Ws, Hs):
+            try:
+                engine.ResampleHost().resample_plan(Hs, Ws, H, W, frame_filter)
+            except _lib.FaststyleError as e:
+                raise SystemExit('--frame_size %d %d: %s' % (W, H, e))
         say('Resolution is: {0} by {1}'.format(W, H))
+        if deliver is not None:
+            say('Output size is: {0} by {1}'.format(deliver['width'], deliver['height']))
         say('Loading up model...')
         eng, variables = _load(args)
         # The channel quirk as in run_frames_dir: the net sees B,G,R (source swap_rb, what a cv2 capture delivers) and the output is swapped back --
         # which is the frame of a lane that does not swap, so the lanes of a video or .jpg output are built with swap_rb=False.
         kw = dict(source=dict(height=Hs, width=Ws, swap_rb=True, yuv=colour_in))
+        if frame_filter is not None:                                         # (a deep stream: fp32 at its own size, resampled to the net's)
+            kw['source']['resample'] = frame_filter
+        if deliver is not None:
+            kw.update(deliver=deliver)
         jpg = args.video_out is None and args.output_format == 'jpg'
         if args.video_out is not None:
             kw.update(swap_rb=False, yuv_out=colour_out)
@@ -354,6 +435,7 @@ def run_webcam(args):
     from faststyle_amd import stream
     compose = compose_options(args)
     temporal = temporal_options(args)
+    delivery = delivery_options(args)
     cap = cv2.VideoCapture(0)
     if args.resolution is not None:
         x_length, y_length = args.resolution
@@ -365,12 +447,17 @@ def run_webcam(args):
     print('Loading up model...')
     eng, variables = _load(args)
     more = dict(temporal=temporal) if temporal is not None else {}
+    x_out, y_out = x_new, y_new
+    if delivery is not None:
+        more['deliver'] = deliver_dict(delivery, (x_new, y_new), (x_new, y_new))
+        x_out, y_out = more['deliver']['width'], more['deliver']['height']
+        print('Output size is: {0} by {1}'.format(x_out, y_out))
     if compose is not None:                                  # (compose_options: the lane does not swap, the loop below does)
         st = stream.FrameStylizer(eng, variables, y_new, x_new, args.upsample_method, swap_rb=False, compose=compose, **more)
     else:
         st = stream.FrameStylizer(eng, variables, y_new, x_new, args.upsample_method, **more)
     fourcc = cv2.VideoWriter_fourcc(*'XVID')
-    out = cv2.VideoWriter('output.avi', fourcc, 15.0, (x_new, y_new))
+    out = cv2.VideoWriter('output.avi', fourcc, 15.0, (x_out, y_out))
     print('Begin filtering...')
     while True:
         ret, frame = cap.read()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the TFRecord input pipeline alone (decode threads + GPU resize + HBM shuffle queue) on
-synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode | frames_in | video [out.json [depth]]]
+synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode | frames_in | video [out.json [depth]] | resample [out.json]]
 "frames_in": the frames-dir loop end to end (stylize_webcam.run_frames_dir, two frames in flight, --output_format jpg) at 720p over a directory of
 n JPEG frames: PIL decode against --input_decode native, and from 1080p sources PIL decode + PIL resize (--resolution) against native decode +
 device resize (--frame_size).  Every leg runs on the same device, legs alternate over the repeats, and a leg's rate is taken from the DIFFERENCE
@@ -21,6 +21,10 @@ profiles/video_compose.json with the digest of the kernel sources.
 with --temporal_strength 0.6, plus the device time of one 720p call of fs_temporal_f32 (its three launches back to back, the graph-of-200 scheme:
 with a previous frame at radius 7 and 3, and a first frame); written to profiles/video_temporal.json.  "temporal_kernels" as the third argument runs
 those graphs alone: under a kernel trace that run gives the time of each of the three kernels back to back.
+"resample" (pipe_bench.py 96 4 resample): the fp32 resampler.  The kernel alone (the graph-of-200 scheme, data resident): 720 x 1280 -> 2160 x 3840
+bicubic and lanczos, 2160 x 3840 -> 720 x 1280 bicubic; and the raw-video loop over a 2160p 4:2:0 file with --frame_size 1280 720, without and
+with --output_size source, as two legs that alternate in the one run (rates from the difference between n and n / 4 frames); written to
+profiles/video_resample.json with the digest of the kernel sources.
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -182,6 +186,87 @@ def temporal_kernel_times(W=1280, H=720, launches=200):
     return res
 
 
+def resample_kernel_times(launches=200):
+    """-> dict of device microseconds per call of fs_resample_f32, timed as kernel_times does, with the bytes each call reads and writes."""
+    eng = engine.Engine()
+    mem = eng.mem
+    rng = np.random.default_rng(4)
+    small = mem.from_numpy(rng.uniform(0, 255, (1, 720, 1280, 3)).astype(np.float32))
+    big = mem.from_numpy(rng.uniform(0, 255, (1, 2160, 3840, 3)).astype(np.float32))
+    res = {}
+    for name, src, dst, filt in (("720p_to_2160p_bicubic", small, big, "bicubic"), ("720p_to_2160p_lanczos", small, big, "lanczos"),
+                                 ("2160p_to_720p_bicubic", big, small, "bicubic")):
+        plan = eng.resample_plan(src.shape[1], src.shape[2], dst.shape[1], dst.shape[2], filt)
+        out = mem.empty(tuple(dst.shape))
+        us = kernel_timed(lambda: eng.resample_f32(src, plan, out), launches)
+        nbytes = 4 * (int(np.prod(src.shape)) + int(np.prod(dst.shape)))
+        res[name] = {"us": us, "bytes_read_and_written": nbytes, "GB_per_s": nbytes / us / 1e3, "tile_h": plan.tile_h,
+                     "tile_rows": int(plan.info.tile_rows), "lds_rows": int(plan.info.lds_rows)}
+        print("resample: %8.1f us per call, %6.0f GB/s of source + destination: %s" % (us, nbytes / us / 1e3, name))
+    return res
+
+
+def resample(n, repeats=3, out_json=None):
+    """-> dict: resample_kernel_times and the two video legs; prints them and writes profiles/video_resample.json."""
+    import contextlib
+    import json
+    import shutil
+    from PIL import Image
+    from faststyle_amd import build as fsbuild
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import stylize_webcam
+    n = max(16, n // 4 * 4)
+    w, h = 3840, 2160
+    d = tempfile.mkdtemp()
+    rng = np.random.default_rng(0)
+    base = rng.integers(0, 256, (135, 240, 3), dtype=np.uint8)
+    planes = []
+    for k in range(16):      # 16 distinct natural-ish frames (upsampled noise), reused; PIL's matrix, box-averaged chroma
+        ycc = np.asarray(Image.fromarray(np.roll(base, 5 * k, axis=1)).resize((w, h), Image.BICUBIC).convert("YCbCr"), np.uint16)
+        sub = (ycc[0::2, 0::2, 1:] + ycc[0::2, 1::2, 1:] + ycc[1::2, 0::2, 1:] + ycc[1::2, 1::2, 1:] + 2) >> 2
+        planes.append(b"FRAME\n" + ycc[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 1].astype(np.uint8).tobytes())
+    for count in (n, n // 4):
+        with open(os.path.join(d, "2160p_%d.y4m" % count), "wb") as f:
+            f.write(b"YUV4MPEG2 W%d H%d F30:1 Ip A1:1 C420jpeg XCOLORRANGE=FULL\n" % (w, h))
+            for k in range(count):
+                f.write(planes[k % 16])
+    parser = stylize_webcam.setup_parser()
+    out = os.path.join(d, "out.y4m")
+    legs = [("video_y4m_2160p_net_720p_out_720p", [], 1280 * 720), ("video_y4m_2160p_net_720p_out_2160p_bicubic", ["--output_size", "source"], w * h)]
+
+    def run(count, flags, pixels):
+        args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--video_in", os.path.join(d, "2160p_%d.y4m" % count),
+                                  "--video_out", out, "--frame_size", "1280", "720"] + flags)
+        with contextlib.redirect_stdout(io.StringIO()):
+            t0 = time.time()
+            stylize_webcam.run_video(args)
+            dt = time.time() - t0
+        assert os.path.getsize(out) > count * pixels * 3 // 2
+        os.remove(out)
+        return dt
+
+    run(n // 4, [], 1280 * 720)                                   # warm-up: library load, first kernels
+    times = {name: [] for name, _, _ in legs}
+    for _ in range(repeats):                                      # legs alternate: a drifting clock touches both alike
+        for name, flags, pixels in legs:
+            times[name].append((run(n, flags, pixels), run(n // 4, flags, pixels)))
+            print("resample: %s: %.2f s for %d frames, %.2f s for %d" % ((name,) + (times[name][-1][0], n, times[name][-1][1], n // 4)), flush=True)
+    shutil.rmtree(d)
+    res = {"frames": n, "frames_in_flight": 2, "host_threads": "1 driver", "host_cores": os.cpu_count(), "omp_num_threads": os.environ.get("OMP_NUM_THREADS"),
+           "video": "2160p 4:2:0 YUV4MPEG2 (full range, BT.601) from a file, --frame_size 1280 720, to a file of 8-bit 4:2:0",
+           "method": "rate = (n - n/4) / (t(n) - t(n/4)), median of %d alternating repeats" % repeats, "source_digest": fsbuild.source_digest(), "legs": {}}
+    for name, _, _ in legs:
+        rates = sorted((n - n // 4) / (a - b) for a, b in times[name])
+        res["legs"][name] = {"frames_per_s": rates[len(rates) // 2], "all_repeats": rates, "seconds_n_and_quarter": times[name]}
+        print("resample: %7.0f frames/s %s (repeats: %s)" % (rates[len(rates) // 2], name, ", ".join("%.0f" % r for r in rates)))
+    res["kernel_per_call"] = resample_kernel_times()
+    with open(out_json or os.path.join(root, "profiles", "video_resample.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    return res
+
+
 def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False, temporal=False):
     """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json (video: with the raw-video leg, to
     profiles/video_stream.json; video with a depth: the 8-bit and the deep raw-video legs alone, to profiles/video_deep.json; video with
@@ -329,6 +414,9 @@ def main():
         fifth = sys.argv[5] if len(sys.argv) > 5 and sys.argv[3] == "video" else None
         frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video",
                   depth=int(fifth) if fifth not in (None, "compose", "temporal") else None, compose=fifth == "compose", temporal=fifth == "temporal")
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "resample":
+        resample(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None)
         return
     if len(sys.argv) > 3 and sys.argv[3] == "temporal_kernels":
         temporal_kernel_times()
