@@ -92,6 +92,13 @@ class fs_resample_info(Structure):
                 ("x_offset", c_uint64), ("y_offset", c_uint64), ("table_bytes", c_uint64)]
 
 
+class fs_temporal_pyr_info(Structure):
+    """include/faststyle_io.h: what fs_temporal_pyr_layout reports."""
+    _fields_ = [("levels", ctypes.c_int32), ("reserved", ctypes.c_int32), ("h", ctypes.c_int32 * 3), ("w", ctypes.c_int32 * 3),
+                ("nby", ctypes.c_int32 * 3), ("nbx", ctypes.c_int32 * 3), ("luma_offset", c_uint64 * 3), ("mv_offset", c_uint64 * 3),
+                ("pyr_bytes", c_uint64)]
+
+
 class fs_yuv_desc(Structure):
     """include/faststyle_io.h: one planar YCbCr frame geometry, filled by fs_yuv_plan."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
@@ -212,6 +219,9 @@ PROTOTYPES = {
     "fs_compose_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fs_temporal_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fs_temporal_pyr_layout": (c_int, [c_int, c_int, c_int, POINTER(fs_temporal_pyr_info)]),
+    "fs_temporal_pyr_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fs_resample_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_resample_info)]),
     "fs_resample_tables": (c_int, [POINTER(fs_resample_info), c_void_p, c_size_t]),
     "fs_resample_f32": (c_int, [c_void_p, POINTER(fs_resample_info), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -118,6 +118,9 @@ def stylize_webcam_parser():
                                           "frame, fetched along block motion vectors, where the source matched; 0 nothing, 1 all of it (default: no "
                                           "such stage); with --frames_dir, --video_in and the camera")),
         ('--temporal_radius', dict(default=argparse.SUPPRESS, type=int, metavar='R', help="(addition) search radius of the motion vectors in pixels, 0..7 (default 7)")),
+        ('--temporal_levels', dict(default=argparse.SUPPRESS, type=int, metavar='L',
+                                   help="(addition) search the motion vectors coarse to fine over L halved lumas, 1..3 (default 1): fast motion, "
+                                        "found reliably up to about R 2^(L-1) pixels; needs --temporal_strength")),
         ('--temporal_sensitivity', dict(default=argparse.SUPPRESS, type=int, metavar='K',
                                         help="(addition) how fast a source mismatch turns the blend off, 1..256: none of it is left at a luma "
                                              "difference of 256 / K (default 16)")),

@@ -19,6 +19,7 @@ struct fs_jpeg_item;
 struct fs_jpegenc_item;
 struct fs_cvresize_info;
 struct fs_resample_info;
+struct fs_temporal_pyr_info;
 struct fs_yuv_desc;
 
 namespace fs {
@@ -699,6 +700,11 @@ int compose_f32(const float* src, int H, int W, const float* net, int Ho, int Wo
 int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius, int matrix, int src_bgr,
                  const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma, unsigned short* out88, signed char* mv,
                  float* dst, hipStream_t s);
+// ... with the coarse-to-fine search over `levels` halved lumas: luma, pyramid (levels > 1), one predicted search per level, blend; `lay` is
+// what fs_temporal_pyr_layout fills for (Ho, Wo, levels)
+int temporal_pyr_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
+                     int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
+                     unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, float* dst, hipStream_t s);
 // resampling between fp32 tensors (fs_resample.hip): whether a plan is what fs_resample_plan fills, and the one launch (argument checks are in
 // fs_api.hip)
 bool resample_plan_ok(const ::fs_resample_info& plan);

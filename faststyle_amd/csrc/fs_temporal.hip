@@ -15,6 +15,11 @@
 //   blend  -- elementwise, four pixels of an output row (they lie in one block: one vector per thread).
 // No value read from a tensor reaches an address except through mv, which the search bounds by R and the blend clamps again together with
 // the displaced coordinates.  The arithmetic is integer throughout.
+// fs_temporal_pyr_f32 reaches further with the same pieces: a pyramid kernel halves the luma once or twice (elementwise, one launch), and the
+// search runs per level, coarsest first, on a window displaced by twice the coarser level's vector (temporal_search_pred_kernel: the search
+// above plus that predictor, which is held to its bound before it reaches an address); the blend is the one above with the larger bound.
+#include <cstring>
+
 #include "../../include/faststyle_io.h"
 
 #include "fs_kernels.h"
@@ -211,7 +216,172 @@ __global__ __launch_bounds__(256) void temporal_blend_kernel(const BlendArgs A, 
         }
 }
 
+// ---- the coarse-to-fine search (fs_temporal_pyr_f32): a pyramid of halved lumas and the search above with a displaced window, per level
+struct PyrArgs {
+    int H0, W0, H1, W1;
+    int H2, W2;                             // 0, 0 with two levels
+};
+
+// the byte of level 1 at (y, x) from level 0: the rounded mean of its 2 x 2 bytes, the odd edge clamped
+__device__ __forceinline__ int pyr_level1(const unsigned char* __restrict__ l0, int H0, int W0, int y, int x) {
+    const int ya = 2 * y < H0 - 1 ? 2 * y : H0 - 1, yb = 2 * y + 1 < H0 - 1 ? 2 * y + 1 : H0 - 1;
+    const int xa = 2 * x < W0 - 1 ? 2 * x : W0 - 1, xb = 2 * x + 1 < W0 - 1 ? 2 * x + 1 : W0 - 1;
+    const unsigned char* ra = l0 + (size_t)ya * W0;
+    const unsigned char* rb = l0 + (size_t)yb * W0;
+    return ((int)ra[xa] + (int)ra[xb] + (int)rb[xa] + (int)rb[xb] + 2) >> 2;
+}
+
+// Levels 1 and 2 in one launch: workgroup row blockIdx.x < H1 is row y of level 1, row H1 + y is row y of level 2; thread blockIdx.y * 256 + t
+// writes the four bytes x0 = 4 (...) ... x0 + 3 of that row.  A byte of level 2 comes from its four level-1 bytes recomputed from level 0 with
+// the nested rounding and clamps, so level 2 does not wait for level 1.  Bytes throughout: the buffers are held to no alignment.
+__global__ __launch_bounds__(256) void temporal_pyramid_kernel(const PyrArgs A, const unsigned char* __restrict__ l0, unsigned char* __restrict__ l1,
+                                                               unsigned char* __restrict__ l2) {
+    const int x0 = ((int)blockIdx.y * 256 + (int)threadIdx.x) * 4;
+    int y = (int)blockIdx.x;
+    if (y < A.H1) {                                         // (uniform per workgroup)
+        unsigned char* row = l1 + (size_t)y * A.W1;
+        for (int x = x0; x < x0 + 4 && x < A.W1; ++x) row[x] = (unsigned char)pyr_level1(l0, A.H0, A.W0, y, x);
+        return;
+    }
+    y -= A.H1;                                              // below H2: the grid has H1 + H2 rows
+    const int ya = 2 * y < A.H1 - 1 ? 2 * y : A.H1 - 1, yb = 2 * y + 1 < A.H1 - 1 ? 2 * y + 1 : A.H1 - 1;
+    unsigned char* row = l2 + (size_t)y * A.W2;
+    for (int x = x0; x < x0 + 4 && x < A.W2; ++x) {
+        const int xa = 2 * x < A.W1 - 1 ? 2 * x : A.W1 - 1, xb = 2 * x + 1 < A.W1 - 1 ? 2 * x + 1 : A.W1 - 1;
+        row[x] = (unsigned char)((pyr_level1(l0, A.H0, A.W0, ya, xa) + pyr_level1(l0, A.H0, A.W0, ya, xb) + pyr_level1(l0, A.H0, A.W0, yb, xa) +
+                                  pyr_level1(l0, A.H0, A.W0, yb, xb) + 2) >> 2);
+    }
+}
+
+// temporal_search_kernel on one level (cur8 / prev8 [H, W]) with the window's origin displaced by the block's predictor, twice the vector of
+// block (by >> 1, bx >> 1) of the coarser level (parent [.., pnbx, 2]; nullptr at the coarsest level: (0, 0)), held to `hold` per component
+// before it reaches an address.  The window is (y0 + py - R, x0 + px - R) ..., each byte clamped into the level, so the LDS layout, the
+// candidates' reads and their conflict-freedom are those of temporal_search_kernel; the winner is the predictor plus the refinement.
+__global__ __launch_bounds__(256) void temporal_search_pred_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int H,
+                                                                   int W, int R, const signed char* __restrict__ parent, int pnbx, int hold,
+                                                                   signed char* __restrict__ v) {
+    __shared__ unsigned win[TWROWS * (TPITCH / 4)];
+    __shared__ unsigned blk[TB * (TB / 4)];
+    __shared__ unsigned keys[256];
+    const int t = (int)threadIdx.x;
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    signed char* out = v + ((size_t)by * gridDim.x + bx) * 2;
+    if (prev8 == nullptr) {                                 // (uniform per launch)
+        if (t == 0) { out[0] = 0; out[1] = 0; }
+        return;
+    }
+    int py = 0, px = 0;
+    if (parent != nullptr) {                                // (uniform per launch)
+        const signed char* p = parent + ((size_t)(by >> 1) * pnbx + (bx >> 1)) * 2;
+        py = 2 * (int)p[0]; px = 2 * (int)p[1];
+        py = py < -hold ? -hold : (py > hold ? hold : py);  // (the coarser search wrote them within it; held to it again)
+        px = px < -hold ? -hold : (px > hold ? hold : px);
+    }
+    const int y0 = by * TB, x0 = bx * TB;
+    const int rows = H - y0 < TB ? H - y0 : TB, cols = W - x0 < TB ? W - x0 : TB;            // at least 1 each
+    const int n = 2 * R + 1;
+    if (t < (TB + 2 * R) * (TPITCH / 4)) {                  // window row t / 8, dword t % 8: level rows y0 + py - R ..., columns x0 + px - R ...
+        const int wr = t >> 3, wc = (t & 7) * 4;
+        const unsigned char* prow = prev8 + (size_t)clampi(y0 + py - R + wr, H - 1) * W;
+        unsigned u = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) u |= (unsigned)prow[clampi(x0 + px - R + wc + b, W - 1)] << (8 * b);
+        win[t] = u;
+    }
+    if (t < TB * (TB / 4)) {                                // block row t / 4, dword t % 4
+        const int r = t >> 2, c = (t & 3) * 4;
+        unsigned u = 0;
+        if (r < rows) {
+            const unsigned char* crow = cur8 + (size_t)(y0 + r) * W + x0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (c + b < cols) u |= (unsigned)crow[c + b] << (8 * b);
+        }
+        blk[t] = u;
+    }
+    __syncthreads();
+    unsigned key = 0xFFFFFFFFu;
+    if (t < n * n) {
+        const int ryi = t / n, rxi = t - ryi * n;           // ry + R, rx + R: the window's row and column of the candidate's first pixel
+        const int ry = ryi - R, rx = rxi - R;
+        unsigned m[4];                                      // the bytes of dword k that lie inside the block
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int inside = cols - 4 * k;
+            m[k] = inside >= 4 ? 0xFFFFFFFFu : (inside <= 0 ? 0u : (1u << (8 * inside)) - 1u);
+        }
+        const int sh = (rxi & 3) * 8;
+        const unsigned* wp = win + ryi * (TPITCH / 4) + (rxi >> 2);          // (rxi >> 2) + 4 <= 7: inside the row
+        unsigned sad = 0;
+        for (int r = 0; r < rows; ++r) {
+            const unsigned* w = wp + r * (TPITCH / 4);
+            const unsigned* c = blk + r * 4;
+            unsigned lo = w[0];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned hi = w[k + 1];
+                const unsigned a = (unsigned)((((unsigned long long)hi << 32) | lo) >> sh);
+                sad = sad4(a & m[k], c[k], sad);
+                lo = hi;
+            }
+        }
+        const int mag = (ry < 0 ? -ry : ry) + (rx < 0 ? -rx : rx);
+        const unsigned cost = sad + (unsigned)(((rows * cols) >> 5) * mag);              // below 2^17
+        key = (cost << 12) | ((unsigned)mag << 8) | ((unsigned)(ry + 7) << 4) | (unsigned)(rx + 7);
+    }
+    keys[t] = key;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+            const unsigned a = keys[t], b = keys[t + s];
+            keys[t] = a < b ? a : b;
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const unsigned k = keys[0];
+        out[0] = (signed char)(py + (int)((k >> 4) & 15u) - 7);                          // |.| <= hold + R <= 49
+        out[1] = (signed char)(px + (int)(k & 15u) - 7);
+    }
+}
+
 }  // namespace
+
+// arguments: checked by the caller (fs_api.hip: fs_temporal_pyr_f32), lay: fs_temporal_pyr_layout's for the call's Ho, Wo and levels
+int temporal_pyr_f32(const fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
+                     int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
+                     unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, float* dst, hipStream_t s) {
+    const int L = lay.levels, Ho = lay.h[0], Wo = lay.w[0];
+    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
+    LumaArgs LA;
+    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
+    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
+    const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
+    const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
+    hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, src, luma);
+    if (L > 1) {
+        PyrArgs PA;
+        PA.H0 = Ho; PA.W0 = Wo; PA.H1 = lay.h[1]; PA.W1 = lay.w[1];
+        PA.H2 = L > 2 ? lay.h[2] : 0; PA.W2 = L > 2 ? lay.w[2] : 0;
+        const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);            // (W1 >= W2; at most 2^21 columns: within grid.y)
+        hipLaunchKernelGGL(temporal_pyramid_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks), block, 0, s, PA, (const unsigned char*)luma,
+                           pyr + lay.luma_offset[1], L > 2 ? pyr + lay.luma_offset[2] : nullptr);
+    }
+    for (int l = L - 1; l >= 0; --l) {                      // coarsest first: level l reads the vectors level l + 1 wrote
+        const unsigned char* c = l ? pyr + lay.luma_offset[l] : luma;
+        const unsigned char* p = prev_luma == nullptr ? nullptr : (l ? prev_pyr + lay.luma_offset[l] : prev_luma);
+        const signed char* parent = l == L - 1 ? nullptr : (const signed char*)(pyr + lay.mv_offset[l + 1]);
+        signed char* v = l ? (signed char*)(pyr + lay.mv_offset[l]) : mv;
+        hipLaunchKernelGGL(temporal_search_pred_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l]), block, 0, s, c, p, lay.h[l], lay.w[l], radius,
+                           parent, l == L - 1 ? 0 : lay.nbx[l + 1], 2 * radius * ((1 << (L - 1 - l)) - 1), v);
+    }
+    BlendArgs BA;
+    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = lay.nbx[0];
+    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = radius * ((1 << L) - 1);
+    hipLaunchKernelGGL(temporal_blend_kernel, egrid, block, 0, s, BA, cur, (const unsigned char*)luma, prev_luma, prev_out88, (const signed char*)mv, dst,
+                       out88);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 // arguments: checked by the caller (fs_api.hip: fs_temporal_f32)
 int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius, int matrix, int src_bgr,
@@ -235,3 +405,36 @@ int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int W
 }
 
 }  // namespace fs
+
+extern "C" {
+
+int fs_temporal_pyr_layout(int Ho, int Wo, int levels, fs_temporal_pyr_info* info) {
+    using namespace fs;
+    if (!info) return set_error(-1, "fs_temporal_pyr_layout: null argument");
+    if (Ho < 1 || Wo < 1) return set_error(-1, "fs_temporal_pyr_layout: a %dx%d output has a side below 1", Ho, Wo);
+    if (levels < 1 || levels > FS_TEMPORAL_MAX_LEVELS)
+        return set_error(-2, "fs_temporal_pyr_layout: levels must be in [1, %d], got %d", FS_TEMPORAL_MAX_LEVELS, levels);
+    fs_temporal_pyr_info p;
+    memset(&p, 0, sizeof(p));
+    p.levels = levels;
+    for (int l = 0; l < levels; ++l) {
+        p.h[l] = l ? (p.h[l - 1] + 1) / 2 : Ho;
+        p.w[l] = l ? (p.w[l - 1] + 1) / 2 : Wo;
+        p.nby[l] = (p.h[l] + TB - 1) / TB;
+        p.nbx[l] = (p.w[l] + TB - 1) / TB;
+    }
+    uint64_t at = 0;
+    for (int l = 1; l < levels; ++l) {
+        p.luma_offset[l] = at;
+        at += ((uint64_t)p.h[l] * (uint64_t)p.w[l] + 15) & ~(uint64_t)15;
+    }
+    for (int l = 1; l < levels; ++l) {
+        p.mv_offset[l] = at;
+        at += ((uint64_t)p.nby[l] * (uint64_t)p.nbx[l] * 2 + 15) & ~(uint64_t)15;
+    }
+    p.pyr_bytes = at;
+    *info = p;
+    return 0;
+}
+
+}  // extern "C"

@@ -1016,19 +1016,46 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
         return dst
 
     # ------------------------------------------------------------------ temporal stabilisation (csrc/fs_temporal.hip)
-    def temporal_state(self, Ho, Wo):
+    def temporal_pyr_layout(self, Ho, Wo, levels):
+        """fs_temporal_pyr_layout: the level sizes, block counts and offsets of the extra state buffer of a `levels`-level search (host only)."""
+        info = L.fs_temporal_pyr_info()
+        L.check(self.lib, self.lib.fs_temporal_pyr_layout(int(Ho), int(Wo), int(levels), ctypes.byref(info)), "fs_temporal_pyr_layout")
+        return info
+
+    def temporal_state(self, Ho, Wo, levels=1):
         """One state slot of fs_temporal_f32 for an Ho x Wo output, as device uint8 buffers (the memory backend's): (luma [Ho,Wo], out88
-        [Ho,Wo,3,2] -- little-endian u16 on the 8.8 scale --, mv [nby,nbx,2] -- signed char (dy, dx) per 16 x 16 block)."""
+        [Ho,Wo,3,2] -- little-endian u16 on the 8.8 scale --, mv [nby,nbx,2] -- signed char (dy, dx) per 16 x 16 block).  levels > 1
+        (fs_temporal_pyr_f32) appends pyr [pyr_bytes]: the halved lumas and the coarse vectors, laid out as temporal_pyr_layout says."""
         Ho, Wo = int(Ho), int(Wo)
         up = self.mem.upload_u8
-        return (up(np.zeros((Ho, Wo), np.uint8)), up(np.zeros((Ho, Wo, 3, 2), np.uint8)), up(np.zeros(((Ho + 15) // 16, (Wo + 15) // 16, 2), np.uint8)))
+        slot = (up(np.zeros((Ho, Wo), np.uint8)), up(np.zeros((Ho, Wo, 3, 2), np.uint8)), up(np.zeros(((Ho + 15) // 16, (Wo + 15) // 16, 2), np.uint8)))
+        if levels == 1:
+            return slot
+        return slot + (up(np.zeros((int(self.temporal_pyr_layout(Ho, Wo, levels).pyr_bytes),), np.uint8)),)
 
-    def temporal_f32(self, src, cur, dst, state, prev=None, strength_q8=256, sensitivity=16, radius=7, matrix="bt601", src_bgr=False):
+    def temporal_pyramid(self, state, Ho, Wo, levels):
+        """For tests and debugging: what a slot of a `levels`-level search holds beyond level 0, as host arrays -> (lumas, vectors), the
+        uint8 [H_l,W_l] lumas and the int8 [nby_l,nbx_l,2] vectors of the levels 1 .. levels - 1 (synchronises)."""
+        lay = self.temporal_pyr_layout(Ho, Wo, levels)
+        if levels > 1 and (len(state) != 4 or int(np.prod(state[3].shape)) != lay.pyr_bytes):
+            raise L.FaststyleError("temporal_pyramid: not the slot of a %dx%d output with %d levels (temporal_state)" % (Ho, Wo, levels))
+        raw = np.array(self.mem.to_numpy(state[3]), dtype=np.uint8, copy=True).reshape(-1) if levels > 1 else None
+        lumas, vectors = [], []
+        for l in range(1, levels):
+            h, w, nby, nbx = lay.h[l], lay.w[l], lay.nby[l], lay.nbx[l]
+            lumas.append(raw[lay.luma_offset[l]:lay.luma_offset[l] + h * w].reshape(h, w))
+            vectors.append(raw[lay.mv_offset[l]:lay.mv_offset[l] + nby * nbx * 2].view(np.int8).reshape(nby, nbx, 2))
+        return lumas, vectors
+
+    def temporal_f32(self, src, cur, dst, state, prev=None, strength_q8=256, sensitivity=16, radius=7, matrix="bt601", src_bgr=False, levels=1):
         """fs_temporal_f32: src device float32 [H,W,3] (the net's input), cur and dst device float32 [Ho,Wo,3] (the tensor the output
         conversions would read and the stabilised one; dst may be cur; a leading axis of 1 is taken), state the slot written (temporal_state's
         triple), prev the slot the previous frame wrote (None: no previous frame) -> dst = cur blended towards prev's output along the
-        block vectors found between the two lumas; matrix 'bt601' / 'bt709' or 0 / 1, src_bgr: channel 0 of src is blue."""
+        block vectors found between the two lumas; matrix 'bt601' / 'bt709' or 0 / 1, src_bgr: channel 0 of src is blue.  levels > 1:
+        fs_temporal_pyr_f32, the coarse-to-fine search, on slots of temporal_state(Ho, Wo, levels)."""
         self._sync_stream()
+        if levels != 1:
+            return self._temporal_pyr_f32(src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels)
         ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
         if len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,):
             ss, cs, ds = ss[1:], cs[1:], ds[1:]
@@ -1046,6 +1073,31 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
                                                    int(sensitivity), int(radius), int(matrix), 1 if src_bgr else 0,
                                                    None if prev is None else p8(prev[0]), None if prev is None else p8(prev[1]),
                                                    p8(state[0]), p8(state[1]), p8(state[2]), self.mem.ptr(dst)), "fs_temporal_f32")
+        return dst
+
+    def _temporal_pyr_f32(self, src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels):
+        """temporal_f32 with levels > 1: the same shape checks with the fourth buffer held against the layout, then fs_temporal_pyr_f32."""
+        if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= levels <= 3:
+            raise L.FaststyleError("temporal_f32: levels must be a whole number in [1, 3], got %r" % (levels,))
+        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
+        if len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,):
+            ss, cs, ds = ss[1:], cs[1:], ds[1:]
+        if len(ss) != 3 or len(cs) != 3 or ss[2] != 3 or cs[2] != 3 or ds != cs:
+            raise L.FaststyleError("temporal_f32: source %s / current %s / destination %s do not belong together (one image per call)" %
+                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
+        Ho, Wo = cs[:2]
+        lay = self.temporal_pyr_layout(Ho, Wo, levels)
+        want = ((Ho, Wo), (Ho, Wo, 3, 2), ((Ho + 15) // 16, (Wo + 15) // 16, 2), (int(lay.pyr_bytes),))
+        for name, slot in (("state", state), ("prev", prev)):
+            if slot is not None and (len(slot) != 4 or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
+                raise L.FaststyleError("temporal_f32: %s is not the slot of a %dx%d output with %d levels (temporal_state)" % (name, Ho, Wo, levels))
+        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
+        p8 = self.mem.ptr_u8
+        pl, po, pp = (None, None, None) if prev is None else (p8(prev[0]), p8(prev[1]), p8(prev[3]))
+        L.check(self.lib, self.lib.fs_temporal_pyr_f32(self.ctx, self.mem.ptr(src), ss[0], ss[1], self.mem.ptr(cur), Ho, Wo, int(strength_q8),
+                                                       int(sensitivity), int(radius), int(levels), int(matrix), 1 if src_bgr else 0, pl, po, pp,
+                                                       p8(state[0]), p8(state[1]), p8(state[3]), p8(state[2]), self.mem.ptr(dst)),
+                "fs_temporal_pyr_f32")
         return dst
 
     def synth_uniform(self, out, seed, rank, batch_index):

@@ -53,6 +53,9 @@ state slots (luma, the output on the 8.8 scale, the vectors): frame n reads slot
 pointers and "no previous frame" is a launch argument, so such a lane's pass is captured in pieces: the head (input conversions, forward,
 compose) as before, and the tail (the stage and the output conversions) once per parity and once for a first frame, each when it first
 occurs.  ``reset()`` forgets the previous frame.  Without ``temporal=`` nothing is allocated or launched and the one graph is captured whole.
+``levels`` in [1, 3] (default 1) searches coarse to fine over that many halved lumas (fs_temporal_pyr_f32): vectors up to ``radius`` (2^levels
+- 1) pixels, found reliably up to about ``radius`` 2^(levels - 1); each slot then has a fourth buffer, the halved lumas and the coarse vectors,
+and the tail has one launch more for the pyramid and one search launch per level.  With ``levels=1`` or without the key nothing changes.
 
 Delivery at another size: with ``deliver=dict(height=, width=, filter='bicubic')`` one launch ahead of the output conversions (fs_resample_f32,
 csrc/fs_resample.hip) resamples the top-left H x W of the tensor they would read -- the net's output, the composed or the stabilised tensor --
@@ -178,7 +181,7 @@ class FrameStylizer(object):
         self.delivery_shape = (B, size[0], size[1], 3)
         self._delivered = self.eng.mem.empty(self.delivery_shape)
 
-    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr")
+    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels")
 
     def _temporal_setup(self, opt, slots):
         """The temporal stage's fixed parts: the quantised strength, the checked parameters, the state slots and the stabilised tensor."""
@@ -203,8 +206,11 @@ class FrameStylizer(object):
             raise L.FaststyleError("temporal matrix is 'bt601' or 'bt709', got %r" % (kw["matrix"],))
         self.temporal = dict(strength_q8=int(np.floor(s * 256.0 + 0.5)), sensitivity=int(number("sensitivity", 16, 1, 256, True)),
                              radius=int(number("radius", 7, 0, 7, True)), matrix=matrix, source_bgr=bool(kw.get("source_bgr", self.swap_rb)))
+        levels = int(number("levels", 1, 1, 3, True))
+        if levels > 1:                                       # (a lane of one level keeps the dict, the slots and the launches it always had)
+            self.temporal["levels"] = levels
         Ho, Wo = self.out_shape[1:3]
-        self._tslots = slots if slots is not None else [self.eng.temporal_state(Ho, Wo) for _ in range(2)]
+        self._tslots = slots if slots is not None else [self.eng.temporal_state(Ho, Wo, levels) for _ in range(2)]
         self._stab = self.eng.mem.empty(self.out_shape)
 
     COMPOSE_KEYS = ("strength", "keep_color", "matrix", "mask", "source_swapped")
@@ -455,7 +461,7 @@ class FrameStylizer(object):
         t = self.temporal
         self.eng.temporal_f32(self._in_f32, self._cur, self._stab, self._tslots[n & 1], prev=None if n == 0 else self._tslots[(n - 1) & 1],
                               strength_q8=t["strength_q8"], sensitivity=t["sensitivity"], radius=t["radius"], matrix=t["matrix"],
-                              src_bgr=t["source_bgr"])
+                              src_bgr=t["source_bgr"], levels=t.get("levels", 1))
         self._outputs(self._stab)
 
     def _captured(self, launches):

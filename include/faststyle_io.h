@@ -483,6 +483,57 @@ int fs_temporal_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cu
                     int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma,
                     unsigned short* out88, signed char* mv, float* dst);
 
+/* ---- Coarse-to-fine block search for the temporal stage (csrc/fs_temporal.hip): the search above reaches R <= 7 pixels; this one runs it on
+ * a pyramid of `levels` L in {1, 2, 3} halved lumas, each level's window displaced by twice the vector of the level above.  Luma and blend
+ * are those of fs_temporal_f32; the arithmetic below is the contract (tests/test_temporal_pyr.py restates it), integer throughout.
+ *
+ *   pyramid    level 0 is cur8: H_0 = Ho, W_0 = Wo.  For l >= 1: H_l = ceil(H_{l-1} / 2), W_l = ceil(W_{l-1} / 2) and
+ *                L_l[y][x] = (a + b + c + d + 2) >> 2, a .. d = L_{l-1}[min(2y + i, H_{l-1} - 1)][min(2x + j, W_{l-1} - 1)] for i, j in {0, 1}.
+ *              The levels 1 .. L-1 of the current frame are written into the state (pyr), where the next call reads them as the previous
+ *              frame's (prev_pyr).
+ *   search     from level L-1 down to level 0.  Each level has its own 16 x 16 block grid anchored top-left, nby_l = ceil(H_l / 16), nbx_l =
+ *              ceil(W_l / 16), npix per ragged block as above.  The predictor p = (py, px) of block (by, bx) is (0, 0) at level L-1 and
+ *              2 v_{l+1}[by >> 1][bx >> 1] below it (that parent block always exists).  For every (ry, rx) in [-R, R]^2:
+ *                SAD  = sum over the block's pixels (y, x) of |cur_l[y][x] - prev_l[clampy_l(y + py + ry)][clampx_l(x + px + rx)]|
+ *                cost = SAD + (npix >> 5) (|ry| + |rx|)
+ *                key  = cost << 12 | (|ry| + |rx|) << 8 | (ry + 7) << 4 | (rx + 7)
+ *              and the smallest key wins: v_l[b] = p + (ry, rx).  The penalty and the tie order apply to the refinement, not to the whole
+ *              vector.  mv = v_0, two signed char per block, |component| <= R (2^L - 1) <= 49.  Without a previous frame, or with R = 0,
+ *              every vector of every level is (0, 0).  With L = 1 this is the search of fs_temporal_f32, term for term.
+ *   blend      as above, with the vectors held to R (2^L - 1) instead of R before q is clamped.
+ * Reach: a vector can be as long as R (2^L - 1), but motion is reliably found only where the coarsest level sees it, about R 2^(L-1) pixels:
+ * 14 at L = 2, 28 at L = 3 (at L = 3 a move by (20, -33) is mostly lost, since -33 / 4 lies outside 7).  Not provided: L above 3 (the coarsest
+ * level of a small frame becomes one ragged block), sub-pixel vectors, a second zero-vector predictor per level, smoothing of the vector
+ * field, batches. */
+
+#define FS_TEMPORAL_MAX_LEVELS 3
+
+/* What fs_temporal_pyr_layout reports: the sizes and block counts of the levels 0 .. levels - 1 (zero beyond), and where the parts of the one
+ * extra state buffer `pyr` lie: the luma of level l >= 1 (h[l] w[l] bytes) at luma_offset[l], then the vectors v_l of level l >= 1 (2 nby[l]
+ * nbx[l] signed char) at mv_offset[l], each a multiple of 16; entry 0 of both is 0 and unused (level 0 lives in luma and mv).  pyr_bytes is
+ * the buffer's size, 0 for levels = 1.  No implicit padding: 14 int32, then uint64. */
+typedef struct fs_temporal_pyr_info {
+    int32_t levels, reserved;
+    int32_t h[FS_TEMPORAL_MAX_LEVELS], w[FS_TEMPORAL_MAX_LEVELS];
+    int32_t nby[FS_TEMPORAL_MAX_LEVELS], nbx[FS_TEMPORAL_MAX_LEVELS];
+    uint64_t luma_offset[FS_TEMPORAL_MAX_LEVELS], mv_offset[FS_TEMPORAL_MAX_LEVELS];
+    uint64_t pyr_bytes;
+} fs_temporal_pyr_info;
+
+/* Host only: no HIP call, no global state, no allocation.  Errors: -1 null info, Ho or Wo below 1; -2 levels outside [1, 3]. */
+int fs_temporal_pyr_layout(int Ho, int Wo, int levels, fs_temporal_pyr_info* info);
+
+/* fs_temporal_f32 with the coarse-to-fine search: 2 + levels launches, and one more for the pyramid when levels > 1.  pyr / prev_pyr: the
+ * extra state buffer written / the one the previous call wrote (fs_temporal_pyr_layout; bytes, no alignment asked); both are ignored and may
+ * be null with levels = 1.  A predictor is held to 2 R (2^(L-1-l) - 1) per component before it reaches an address and every window byte is
+ * clamped into its level, so a stale prev_pyr gives wrong vectors and nothing else.  Asynchronous on the ctx stream, allocates nothing, can be
+ * captured into a hipGraph.  A refused call launches nothing.  Errors: those of fs_temporal_f32, and -2 levels outside [1, 3]; with levels >
+ * 1: -1 null pyr, prev_pyr null while prev_luma and prev_out88 are given or the reverse, prev_pyr == pyr. */
+int fs_temporal_pyr_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity,
+                        int radius, int levels, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
+                        const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv,
+                        float* dst);
+
 /* ---- Resampling between fp32 tensors (csrc/fs_resample.hip): the net's (or composed, or stabilised) output at a delivery size, a deep
  * source's fp32 planes at the net's size; no u8 stage on either path.  The arithmetic below is the contract: it is Pillow's Image.resize on
  * mode-F images (double coefficients, double accumulation, a float32 result), and tests/test_resample.py restates it in numpy, holds the

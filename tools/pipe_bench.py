@@ -21,6 +21,10 @@ profiles/video_compose.json with the digest of the kernel sources.
 with --temporal_strength 0.6, plus the device time of one 720p call of fs_temporal_f32 (its three launches back to back, the graph-of-200 scheme:
 with a previous frame at radius 7 and 3, and a first frame); written to profiles/video_temporal.json.  "temporal_kernels" as the third argument runs
 those graphs alone: under a kernel trace that run gives the time of each of the three kernels back to back.
+"video" with "temporal_levels" as the fifth argument (pipe_bench.py 1280 4 video profiles/video_temporal_pyr.json temporal_levels): the two legs are
+--temporal_strength 0.6 alone and with --temporal_levels 3, plus the device time of one 720p call of the stage at one level (fs_temporal_f32), two and
+three levels (fs_temporal_pyr_f32: the pyramid launch and one search launch per level more) on a frame moved by (20, -12), the graph-of-200 scheme;
+written to profiles/video_temporal_pyr.json.  "temporal_pyr_kernels" as the third argument runs those graphs alone.
 "resample" (pipe_bench.py 96 4 resample): the fp32 resampler.  The kernel alone (the graph-of-200 scheme, data resident): 720 x 1280 -> 2160 x 3840
 bicubic and lanczos, 2160 x 3840 -> 720 x 1280 bicubic; and the raw-video loop over a 2160p 4:2:0 file with --frame_size 1280 720, without and
 with --output_size source, as two legs that alternate in the one run (rates from the difference between n and n / 4 frames); written to
@@ -186,6 +190,31 @@ def temporal_kernel_times(W=1280, H=720, launches=200):
     return res
 
 
+def temporal_pyr_kernel_times(W=1280, H=720, launches=200):
+    """-> dict of device microseconds per 720p call of the temporal stage by level count, timed as kernel_times does: a frame moved by (20, -12)
+    against its predecessor at radius 7 -- one level is fs_temporal_f32's three launches, two and three levels are fs_temporal_pyr_f32's 5 and 6
+    -- and the share of interior blocks whose vector is the move."""
+    eng = engine.Engine()
+    mem = eng.mem
+    rng = np.random.default_rng(3)
+    small = rng.uniform(0, 255, (H // 8, W // 8, 3)).astype(np.float32)
+    a = np.ascontiguousarray(np.kron(small, np.ones((8, 8, 1), np.float32)) + rng.uniform(-4, 4, (H, W, 3)).astype(np.float32))
+    src0, src1 = mem.from_numpy(a[None]), mem.from_numpy(np.roll(a, (-20, 12), axis=(0, 1))[None])
+    cur = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    dst = mem.empty((1, H, W, 3))
+    kw = dict(strength_q8=154, sensitivity=16, src_bgr=True, radius=7)
+    res = {}
+    for levels in (1, 2, 3):
+        s0, s1 = eng.temporal_state(H, W, levels), eng.temporal_state(H, W, levels)
+        eng.temporal_f32(src0, cur, dst, s0, levels=levels, **kw)                 # the previous frame's state
+        us = kernel_timed(lambda: eng.temporal_f32(src1, cur, dst, s1, prev=s0, levels=levels, **kw), launches)
+        mv = np.array(mem.to_numpy(s1[2]), dtype=np.uint8, copy=True).view(np.int8)[2:-3, 1:-2]
+        found = float(np.mean((mv[..., 0] == 20) & (mv[..., 1] == -12)))
+        res["temporal_levels_%d" % levels] = {"us": us, "launches": 3 if levels == 1 else 3 + levels, "interior_blocks_at_20_-12": found}
+        print("video: %8.1f us per 720p call, %3.0f %% of the interior blocks at (20, -12): %d level(s)" % (us, 100 * found, levels))
+    return res
+
+
 def resample_kernel_times(launches=200):
     """-> dict of device microseconds per call of fs_resample_f32, timed as kernel_times does, with the bytes each call reads and writes."""
     eng = engine.Engine()
@@ -267,11 +296,11 @@ def resample(n, repeats=3, out_json=None):
     return res
 
 
-def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False, temporal=False):
+def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False, temporal=False, temporal_levels=False):
     """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json (video: with the raw-video leg, to
     profiles/video_stream.json; video with a depth: the 8-bit and the deep raw-video legs alone, to profiles/video_deep.json; video with
     compose / temporal: the 8-bit raw-video leg without and with that stage, to profiles/video_compose.json / video_temporal.json)."""
-    compose_flag, compose = compose, compose or temporal          # (the two stages share the two-leg scheme)
+    compose_flag, compose = compose, compose or temporal or temporal_levels          # (the stages share the two-leg scheme)
     import contextlib
     import json
     import shutil
@@ -334,6 +363,9 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=Fals
         legs = [("video_y4m_720p", "720p", None), ("video_y4m_720p_strength_0.7_preserve_color", "720p", ("--style_strength", "0.7", "--preserve_color"))]
     if temporal:
         legs = [("video_y4m_720p", "720p", None), ("video_y4m_720p_temporal_strength_0.6", "720p", ("--temporal_strength", "0.6"))]
+    if temporal_levels:
+        legs = [("video_y4m_720p_temporal_strength_0.6", "720p", ("--temporal_strength", "0.6")),
+                ("video_y4m_720p_temporal_strength_0.6_levels_3", "720p", ("--temporal_strength", "0.6", "--temporal_levels", "3"))]
     parser = stylize_webcam.setup_parser()
     out = os.path.join(d, "out")
 
@@ -399,7 +431,9 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=Fals
         res["kernel_us_per_720p_launch"] = compose_kernel_times()
     if temporal:
         res["kernel_us_per_720p_call_of_three_launches"] = temporal_kernel_times()
-    dst = out_json or os.path.join(root, "profiles", "video_temporal.json" if temporal else "video_compose.json" if compose else "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
+    if temporal_levels:
+        res["kernel_us_per_720p_call_by_levels"] = temporal_pyr_kernel_times()
+    dst = out_json or os.path.join(root, "profiles", "video_temporal_pyr.json" if temporal_levels else "video_temporal.json" if temporal else "video_compose.json" if compose else "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
     with open(dst, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
@@ -413,7 +447,11 @@ def main():
     if len(sys.argv) > 3 and sys.argv[3] in ("frames_in", "video"):
         fifth = sys.argv[5] if len(sys.argv) > 5 and sys.argv[3] == "video" else None
         frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video",
-                  depth=int(fifth) if fifth not in (None, "compose", "temporal") else None, compose=fifth == "compose", temporal=fifth == "temporal")
+                  depth=int(fifth) if fifth not in (None, "compose", "temporal", "temporal_levels") else None, compose=fifth == "compose",
+                  temporal=fifth == "temporal", temporal_levels=fifth == "temporal_levels")
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "temporal_pyr_kernels":
+        temporal_pyr_kernel_times()
         return
     if len(sys.argv) > 3 and sys.argv[3] == "resample":
         resample(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None)
