@@ -225,6 +225,9 @@ PROTOTYPES = {
     "fs_resample_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_resample_info)]),
     "fs_resample_tables": (c_int, [POINTER(fs_resample_info), c_void_p, c_size_t]),
     "fs_resample_f32": (c_int, [c_void_p, POINTER(fs_resample_info), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fs_guided_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "fs_guided_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                              c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "fs_u8_to_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "fs_f32_to_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
 }

@@ -130,6 +130,15 @@ def stylize_webcam_parser():
                                     "every output conversion; with --frames_dir, --video_in and the camera")),
         ('--output_filter', dict(default=argparse.SUPPRESS, choices=['box', 'bilinear', 'bicubic', 'lanczos'], metavar='F',
                                  help="(addition) filter of --output_size: box, bilinear, bicubic (default) or lanczos")),
+        ('--output_guided', dict(default=argparse.SUPPRESS, action='store_true',
+                                 help="(addition) with --frame_size and an --output_size that is the source's: deliver by edge-aware (guided) "
+                                      "upsampling against the full-size source instead of a resampling filter, so that the source's edges return "
+                                      "at the delivery resolution; with --frames_dir, --video_in and the camera")),
+        ('--guided_radius', dict(default=argparse.SUPPRESS, type=int, metavar='R',
+                                 help="(addition) window radius of --output_guided on the net's grid, 1..8 (default 2)")),
+        ('--guided_smoothness', dict(default=argparse.SUPPRESS, type=int, metavar='E',
+                                     help="(addition) smoothness of --output_guided in 8-bit levels, 1..64 (default 4): larger follows the source's "
+                                          "edges less")),
         ('--frame_filter', dict(default=argparse.SUPPRESS, choices=['box', 'bilinear', 'bicubic', 'lanczos'], metavar='F',
                                 help="(addition) with --video_depth stream, a --video_in of 9 to 16 bits and --frame_size: resample the stream's fp32 "
                                      "frames to W x H with this filter on the device (without it --frame_size refuses such a stream)")),

@@ -305,6 +305,35 @@ int fs_resample_f32(fs_ctx* ctx, const fs_resample_info* plan, const void* table
     const int rc = fs::resample_f32(*plan, static_cast<const unsigned char*>(tables_dev), src, src_rows, src_pitch, N, dst, ctx->stream);
     return rc ? fail(rc, "fs_resample_f32: launch failed (%d)", rc) : 0;
 }
+int fs_guided_workspace(int H, int W, int N, size_t* bytes) {
+    if (!bytes) return fail(-1, "fs_guided_workspace: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_guided_workspace: N must be in [1, 65535], got %d", N);
+    if (H < 1 || W < 1 || H > 32767 || W > 32767) return fail(-1, "fs_guided_workspace: a %dx%d grid (each side in [1, 32767])", H, W);
+    *bytes = 2 * fs::guided_part_bytes(H, W, N);
+    return 0;
+}
+int fs_guided_f32(fs_ctx* ctx, const float* lo_src, int H, int W, const float* lo_out, int Ho, int Wo, const void* hi_src, int hi_kind, int Hd, int Wd,
+                  int N, int radius, int smoothness, int matrix, int lo_bgr, int hi_bgr, void* work, size_t work_bytes, float* dst) {
+    if (!ctx || !lo_src || !lo_out || !hi_src || !work || !dst) return fail(-1, "fs_guided_f32: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_guided_f32: N must be in [1, 65535], got %d", N);
+    if (H < 1 || W < 1 || Ho < H || Ho > H + 3 || Wo < W || Wo > W + 3)
+        return fail(-1, "fs_guided_f32: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", H, W, Ho, Wo);
+    if (Hd > 32767 || Wd > 32767 || Hd < H || Wd < W)
+        return fail(-1, "fs_guided_f32: a %dx%d delivery from a %dx%d grid (at least the grid's size, at most 32767 a side)", Hd, Wd, H, W);
+    if (work_bytes < 2 * fs::guided_part_bytes(H, W, N))
+        return fail(-1, "fs_guided_f32: a workspace of %zu bytes, fs_guided_workspace asks for %zu", work_bytes, 2 * fs::guided_part_bytes(H, W, N));
+    if (dst == lo_out || dst == lo_src || (const void*)dst == hi_src) return fail(-1, "fs_guided_f32: dst must not be lo_src, lo_out or hi_src");
+    if (radius < 1 || radius > 8) return fail(-2, "fs_guided_f32: radius must be in [1, 8], got %d", radius);
+    if (smoothness < 1 || smoothness > 64) return fail(-2, "fs_guided_f32: smoothness must be in [1, 64], got %d", smoothness);
+    if (hi_kind < 0 || hi_kind > 2) return fail(-2, "fs_guided_f32: hi_kind must be 0 (u8 x 3), 1 (u8 x 4) or 2 (fp32 x 3), got %d", hi_kind);
+    if (matrix != 0 && matrix != 1) return fail(-2, "fs_guided_f32: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
+    if ((lo_bgr != 0 && lo_bgr != 1) || (hi_bgr != 0 && hi_bgr != 1)) return fail(-2, "fs_guided_f32: lo_bgr and hi_bgr must be 0 or 1, got %d and %d", lo_bgr, hi_bgr);
+    if ((((uintptr_t)lo_src | (uintptr_t)lo_out | (uintptr_t)dst) & 3) || (hi_kind == 2 && ((uintptr_t)hi_src & 3)))
+        return fail(-5, "fs_guided_f32: lo_src, lo_out, dst and an fp32 hi_src must be 4-byte aligned");
+    if ((uintptr_t)work & 15) return fail(-5, "fs_guided_f32: work must be 16-byte aligned");
+    const int rc = fs::guided_f32(lo_src, H, W, lo_out, Ho, Wo, hi_src, hi_kind, Hd, Wd, N, radius, smoothness, matrix, lo_bgr, hi_bgr, work, dst, ctx->stream);
+    return rc ? fail(rc, "fs_guided_f32: launch failed (%d)", rc) : 0;
+}
 int fs_queue_take(fs_ctx* ctx, float* store, int capacity, size_t row_floats, const int32_t* take_idx, int B, const int32_t* move_src,
                   const int32_t* move_dst, int M, float* batch_out) {
     if (!ctx || !store || !take_idx || !batch_out) return fail(-1, "fs_queue_take: null argument");

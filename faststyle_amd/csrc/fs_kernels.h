@@ -710,6 +710,11 @@ int temporal_pyr_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H,
 bool resample_plan_ok(const ::fs_resample_info& plan);
 int resample_f32(const ::fs_resample_info& plan, const unsigned char* tables, const float* src, int src_rows, int src_pitch, int N, float* dst,
                  hipStream_t s);
+// guided delivery (fs_guided.hip): the bytes of one of the two workspace parts (coef, then mean), and the three launches (argument checks are
+// in fs_api.hip)
+size_t guided_part_bytes(int H, int W, int N);
+int guided_f32(const float* lo_src, int H, int W, const float* lo_out, int Ho, int Wo, const void* hi_src, int hi_kind, int Hd, int Wd, int N, int radius,
+               int smoothness, int matrix, int lo_bgr, int hi_bgr, void* work, float* dst, hipStream_t s);
 int in_bwd(const float* gin, const float* z, const float* mean, const float* rstd, const float* a, const float* b, int mode,
            float* dz, float* dgamma, float* dbeta, float* scratch, int N, int HW, int C, hipStream_t s);
 // ... with the per-sample sums taken from records [N][T][C][2] (rec == nullptr: computed here into `scratch`), reduced in the apply kernel's

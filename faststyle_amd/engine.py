@@ -1015,6 +1015,53 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
                                                    ss[0] if len(ss) == 4 else 1, self.mem.ptr(dst)), "fs_resample_f32")
         return dst
 
+    # ------------------------------------------------------------------ guided delivery (csrc/fs_guided.hip)
+    def guided_workspace_bytes(self, H, W, N=1):
+        """fs_guided_workspace: the bytes of the workspace of guided_f32 for N images on an H x W grid (host only)."""
+        n = ctypes.c_size_t()
+        L.check(self.lib, self.lib.fs_guided_workspace(int(H), int(W), int(N), ctypes.byref(n)), "fs_guided_workspace")
+        return int(n.value)
+
+    def guided_workspace(self, H, W, N=1):
+        """The workspace of guided_f32 as a device uint8 buffer (the memory backend's): coef [N,H,W,6] int32 in its first half, mean
+        [N,H,W,6] int32 in its second (each half N H W 24 bytes rounded up to a multiple of 16; guided_parts reads them)."""
+        return self.mem.upload_u8(np.zeros((self.guided_workspace_bytes(H, W, N),), np.uint8))
+
+    def guided_parts(self, work, H, W, N=1):
+        """For tests and debugging: what guided_f32 left in its workspace, as host arrays -> (coef, mean), int32 [N,H,W,6] (synchronises)."""
+        raw = np.array(self.mem.to_numpy(work), dtype=np.uint8, copy=True).reshape(-1)
+        if raw.size != self.guided_workspace_bytes(H, W, N):
+            raise L.FaststyleError("guided_parts: not the workspace of %d %dx%d images (guided_workspace)" % (N, H, W))
+        n = int(N) * int(H) * int(W) * 24
+        return tuple(raw[o:o + n].view(np.int32).reshape(int(N), int(H), int(W), 6) for o in (0, raw.size // 2))
+
+    def guided_f32(self, lo_src, lo_out, hi_src, dst, work, radius=2, smoothness=4, matrix="bt601", lo_bgr=False, hi_bgr=False):
+        """fs_guided_f32: lo_src device float32 [H,W,3] / [N,H,W,3] (the net's input), lo_out device float32 [Ho,Wo,3] / [N,Ho,Wo,3] (the
+        net's, composed or stabilised output), hi_src the source at the delivery size -- device uint8 [..,Hd,Wd,3] (kind 0), uint8
+        [..,Hd,Wd,4] (kind 1) or float32 [..,Hd,Wd,3] (kind 2) --, dst device float32 [..,Hd,Wd,3], work guided_workspace(H, W, N) -> dst =
+        the guided upsampling of lo_out: per channel a * luma(hi_src) + b with the window-averaged coefficients of the local linear model
+        lo_out ~ a * luma(lo_src) + b, interpolated bilinearly.  matrix 'bt601' / 'bt709' or 0 / 1; lo_bgr / hi_bgr: channel 0 of lo_src /
+        hi_src is blue."""
+        self._sync_stream()
+        ss, os_, hs, ds = (tuple(int(d) for d in t.shape) for t in (lo_src, lo_out, hi_src, dst))
+        is_u8 = str(hi_src.dtype).endswith("uint8")
+        kind = (0 if hs[-1:] == (3,) else 1) if is_u8 else 2
+        if len(ss) not in (3, 4) or len(os_) != len(ss) or len(hs) != len(ss) or len(ds) != len(ss) or ss[-1] != 3 or os_[-1] != 3 or \
+                hs[-1] != (4 if kind == 1 else 3) or (is_u8 and hs[-1] not in (3, 4)) or ds != hs[:-1] + (3,) or \
+                (len(ss) == 4 and not ss[0] == os_[0] == hs[0]) or not (is_u8 or str(hi_src.dtype).endswith("float32")):
+            raise L.FaststyleError("guided_f32: net input %s / output %s / source %s %s / destination %s do not belong together" %
+                                   (ss, os_, hs, hi_src.dtype, ds))
+        N = ss[0] if len(ss) == 4 else 1
+        nbytes = int(np.prod(tuple(int(d) for d in work.shape)))
+        if not str(work.dtype).endswith("uint8"):
+            raise L.FaststyleError("guided_f32: the workspace is a uint8 buffer (guided_workspace), got %s" % (work.dtype,))
+        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
+        hp = self.mem.ptr_u8(hi_src) if is_u8 else self.mem.ptr(hi_src)
+        L.check(self.lib, self.lib.fs_guided_f32(self.ctx, self.mem.ptr(lo_src), ss[-3], ss[-2], self.mem.ptr(lo_out), os_[-3], os_[-2], hp, kind,
+                                                 hs[-3], hs[-2], N, int(radius), int(smoothness), int(matrix), 1 if lo_bgr else 0,
+                                                 1 if hi_bgr else 0, self.mem.ptr_u8(work), nbytes, self.mem.ptr(dst)), "fs_guided_f32")
+        return dst
+
     # ------------------------------------------------------------------ temporal stabilisation (csrc/fs_temporal.hip)
     def temporal_pyr_layout(self, Ho, Wo, levels):
         """fs_temporal_pyr_layout: the level sizes, block counts and offsets of the extra state buffer of a `levels`-level search (host only)."""

@@ -66,6 +66,15 @@ whole-pass graph and in every temporal tail graph.  ``source=dict(..., resample=
 of 9 to 16 bits per sample: the planes are converted at the source's own size into an fp32 tensor of the lane's and resampled into the net's
 input; it is the only way such a source of another size than the net's is taken, and 8-bit sources are refused with it (``interpolation=``
 serves them).  Without the keys nothing is allocated or launched.
+
+Guided delivery: ``deliver=dict(height=, width=, guided=dict(radius=2, smoothness=4, matrix='bt601', source_bgr=<the lane's swap_rb>))`` puts
+fs_guided_f32 (csrc/fs_guided.hip, three launches) where the resampling stands: the fast guided filter fits output ~ a * luma(source) + b per
+channel on the net's grid, smooths a and b over a (2 radius + 1)^2 window, interpolates them to the delivery grid and applies them to the luma
+of the source at its own size, so that the source's edges return at the delivery resolution.  ``smoothness`` in [1, 64] is in 8-bit levels
+(larger: smoother, nearer to a plain bilinear enlargement), ``source_bgr`` says that channel 0 of the net's input is blue.  It needs a
+``source=`` of exactly the delivery's size that is resized to the net's, and reads the buffer the lane holds that source in anyway: the pixel
+frames, the decoded RGBX of JPEG and 8-bit ``yuv=`` sources, or the fp32 planes of a deep source with ``resample=``.  Not together with
+``filter=``.
 """
 import ctypes
 
@@ -108,6 +117,10 @@ class FrameStylizer(object):
         self.deliver = None              # with deliver=: dict(height=, width=, filter=)
         self._deliver_plan = None        # ... the plan from the top-left H x W of the net's Ho x Wo output to the delivery size
         self._delivered = None           # ... and the delivery tensor every output conversion then reads
+        self._guided = None              # with deliver guided=: dict(radius=, smoothness=, matrix=, lo_bgr=) as the launch takes them
+        self._guided_work = None         # ... the workspace of the three launches (Engine.guided_workspace)
+        self._guided_src = None          # ... {jpeg_in: (the device buffer that holds the source at its own size, hi_bgr)}
+        self._hi_jpeg = False            # ... whether the pass under way began with JPEG coefficients
         if deliver is not None:
             self._deliver_setup(dict(deliver))
         self._in_u8 = mem.upload_u8(np.zeros(self.shape, np.uint8))
@@ -145,6 +158,8 @@ class FrameStylizer(object):
         self._src_f32 = None             # ... and the deep source converted at its own size
         if source is not None:
             self._source_setup(dict(source))
+        if self._guided is not None:
+            self._guided_bind()
         self.compose = None              # with compose=: dict(strength_q8=, keep_color=, matrix=, mask=, source_swapped=) as the launch takes them
         self._composed = None            # ... and the composed tensor every output conversion then reads instead of the net's output
         self._mask = None
@@ -160,12 +175,16 @@ class FrameStylizer(object):
             self._temporal_setup(dict(temporal), _temporal_slots)
 
     DELIVER_KEYS = ("height", "width", "filter")
+    GUIDED_KEYS = ("radius", "smoothness", "matrix", "source_bgr")
 
     def _deliver_setup(self, opt):
         """The delivery stage's fixed parts: the checked size and filter, the plan and the lane's own delivery tensor."""
+        guided = opt.pop("guided", None)
         kw = {k: opt.pop(k) for k in self.DELIVER_KEYS if k in opt}
         if opt:
             raise L.FaststyleError("deliver takes %s, got also %r" % (", ".join(self.DELIVER_KEYS), opt))
+        if guided is not None and "filter" in kw:
+            raise L.FaststyleError("deliver guided= takes the place of filter=: the delivery is resampled or guided, got both")
         if "height" not in kw or "width" not in kw:
             raise L.FaststyleError("deliver needs height and width, got %r" % kw)
         size = []
@@ -174,12 +193,68 @@ class FrameStylizer(object):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
                 raise L.FaststyleError("deliver %s must be a whole number of at least 1, got %r" % (name, v))
             size.append(int(v))
-        filt = kw.get("filter", "bicubic")
         B, H, W, _ = self.shape
+        if guided is not None:
+            self._guided_setup(dict(guided), size)
+            return
+        filt = kw.get("filter", "bicubic")
         self._deliver_plan = self.eng.resample_plan(H, W, size[0], size[1], filt)      # (an unknown filter or a refused plan raises)
         self.deliver = dict(height=size[0], width=size[1], filter=filt)
         self.delivery_shape = (B, size[0], size[1], 3)
         self._delivered = self.eng.mem.empty(self.delivery_shape)
+
+    def _guided_setup(self, opt, size):
+        """The guided delivery's checked parameters and the lane's delivery tensor; the source is bound once it is known (_guided_bind)."""
+        kw = {k: opt.pop(k) for k in self.GUIDED_KEYS if k in opt}
+        if opt:
+            raise L.FaststyleError("deliver guided takes %s, got also %r" % (", ".join(self.GUIDED_KEYS), opt))
+
+        def whole(name, default, lo, hi):
+            try:
+                v = float(kw.get(name, default))
+            except (TypeError, ValueError):
+                raise L.FaststyleError("deliver guided %s %r is not a number" % (name, kw[name]))
+            if not lo <= v <= hi or v != int(v):                 # (NaN fails both comparisons)
+                raise L.FaststyleError("deliver guided %s must be a whole number in [%d, %d], got %r" % (name, lo, hi, v))
+            return int(v)
+
+        matrix = {"bt601": 0, "bt709": 1, 0: 0, 1: 1}.get(kw.get("matrix", "bt601"))
+        if matrix is None:
+            raise L.FaststyleError("deliver guided matrix is 'bt601' or 'bt709', got %r" % (kw["matrix"],))
+        B, H, W, _ = self.shape
+        if size[0] < H or size[1] < W or tuple(size) == (H, W) or max(size) > 32767:
+            raise L.FaststyleError("deliver guided= upsamples to the source's size: a delivery of %dx%d from a net of %dx%d (at least the net's "
+                                   "size on both sides, larger on one, at most 32767)" % (size[0], size[1], H, W))
+        self._guided = dict(radius=whole("radius", 2, 1, 8), smoothness=whole("smoothness", 4, 1, 64), matrix=matrix,
+                            lo_bgr=bool(kw.get("source_bgr", self.swap_rb)))
+        self.deliver = dict(height=size[0], width=size[1], guided=dict(self._guided))
+        self.delivery_shape = (B, size[0], size[1], 3)
+        self._delivered = self.eng.mem.empty(self.delivery_shape)
+
+    def _guided_bind(self):
+        """The guide of the guided delivery: the buffer in which the lane already holds the source at its own size, which must be the
+        delivery's.  hi_bgr follows from where R and B are exchanged: in the resize behind that buffer (cvresize_u8(swap_rb=): the buffer has
+        the other order than the net's input) or in the conversion in front of it (yuv_deep_to_f32(swap_rb=): the same order)."""
+        B, H, W, _ = self.shape
+        size = self.delivery_shape[1:3]
+        if self.source is None:
+            raise L.FaststyleError("deliver guided= needs source= at the delivery's size %dx%d, resized to the net's: the full-size source is the guide" % size)
+        if (self.source["height"], self.source["width"]) != size:
+            raise L.FaststyleError("deliver guided= needs a source of the delivery's size %dx%d, got %dx%d" %
+                                   (size + (self.source["height"], self.source["width"])))
+        lo_bgr = self._guided["lo_bgr"]
+        behind = lo_bgr != self._src_swap                        # (the swap happens behind the buffer)
+        if self._src_f32 is not None:
+            self._guided_src = {False: (self._src_f32, lo_bgr)}
+        elif self._src_yuv is not None and not self._src_deep and self._src_rgbx is not None:
+            self._guided_src = {False: (self._src_rgbx, behind)}
+        elif self._src_yuv is None and self._src_plan is not None:
+            self._guided_src = {False: (self._pix_dst, behind)}
+            if self._src_jpeg is not None:
+                self._guided_src[True] = (self._src_rgbx, behind)
+        else:
+            raise L.FaststyleError("deliver guided= needs a source that is resized to the net's size (interpolation=, or resample= for 9 to 16 bits)")
+        self._guided_work = self.eng.guided_workspace(H, W, B)
 
     TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels")
 
@@ -407,6 +482,7 @@ class FrameStylizer(object):
 
     def _device_pass(self, jpeg_in=False):
         e = self.eng
+        self._hi_jpeg = jpeg_in
         if jpeg_in:                                          # the coefficients of the frame(s) are in self._src_coef
             if self._src_plan is not None:
                 e.jpeg_reconstruct_many(self._src_coef, self._sitems, self._src_rgbx, items_dev=(self._sitems_dev, 0))
@@ -446,6 +522,11 @@ class FrameStylizer(object):
         e = self.eng
         if self._deliver_plan is not None:
             y = e.resample_f32(e.mem.view(y, 0, self.out_shape), self._deliver_plan, self._delivered)
+        elif self._guided is not None:                       # the net's grid against the source at its own size, which the lane still holds
+            g = self._guided
+            hi, hi_bgr = self._guided_src[self._hi_jpeg]
+            y = e.guided_f32(self._in_f32, e.mem.view(y, 0, self.out_shape), hi, self._delivered, self._guided_work, radius=g["radius"],
+                             smoothness=g["smoothness"], matrix=g["matrix"], lo_bgr=g["lo_bgr"], hi_bgr=hi_bgr)
         if self._out_deep:                                   # 16-bit samples: straight from the net's fp32 output
             e.f32_to_yuv_deep(y, self.yuv_out_desc, self._result, swap_rb=self.swap_rb)
             return
@@ -494,6 +575,7 @@ class FrameStylizer(object):
         """The device pass of the frame(s) just uploaded: the captured graph's replay, or eager.  With temporal= that pass is the head, and
         the tail follows: eager, or the replay of the graph of its kind (a first frame's, or the parity's), captured when first needed.
         before_tail: called between the two (a PipelinedStylizer's wait for the previous frame's tail on another stream)."""
+        self._hi_jpeg = jpeg_in
         if not self._use_graph:
             self._device_pass(jpeg_in)
         elif jpeg_in:
@@ -511,6 +593,8 @@ class FrameStylizer(object):
             self._tail(n)
         else:
             kind = None if n == 0 else n & 1
+            if self._guided is not None and jpeg_in:             # (a JPEG frame's guide is another buffer than a pixel frame's)
+                kind = (kind, True)
             if kind not in self._tail_graphs:
                 self._tail_graphs[kind] = self._captured(lambda: self._tail(n))
             self._tail_graphs[kind].replay()

@@ -603,6 +603,59 @@ int fs_resample_tables(const fs_resample_info* plan, void* tables, size_t cap);
 int fs_resample_f32(fs_ctx* ctx, const fs_resample_info* plan, const void* tables_dev, const float* src, int src_rows, int src_pitch, int N,
                     float* dst);
 
+/* ---- Guided delivery (csrc/fs_guided.hip): the net's (or composed, or stabilised) output at a larger delivery size with the edges of the
+ * full-size source, by the fast guided filter (He & Sun): a local linear model output ~ a * luma(source) + b per channel on the net's grid,
+ * a and b smoothed there, interpolated to the delivery grid and applied to the luma of the full-size source.  Three launches.  The arithmetic
+ * below is the contract (tests/test_guided.py restates it in numpy and compares for equality); it is integer throughout, on compose's
+ * unsigned 8.8 scale: to88, the luma weight triples, L(X) and the meaning of "bgr" are those of the fs_compose_f32 block above.  Every sum is
+ * an integer sum, so the order of addition is free.
+ *
+ * Inputs per image: lo_src [H, W, 3] fp32, the net's input; lo_out [Ho, Wo, 3] fp32, the net's, composed or stabilised output, H <= Ho <= H + 3
+ * and W <= Wo <= W + 3, of which only the top-left H x W is read; hi_src, the source at the delivery size Hd x Wd (Hd >= H, Wd >= W), of kind
+ * 0: u8, 3 bytes per pixel; 1: u8, 4 bytes per pixel, the fourth ignored; 2: fp32, 3 floats per pixel.  Parameters: the radius r in [1, 8], n =
+ * (2r + 1)^2; the smoothness E in [1, 64], in 8-bit levels; matrix 0 | 1; lo_bgr, hi_bgr 0 | 1: whether channel 0 of lo_src, respectively of
+ * hi_src, is blue.  The channels of lo_out are treated alike, so its order does not matter.
+ *
+ * clampy(v) = min(max(v, 0), H - 1), clampx likewise with W.  The window of pixel (y, x) is {(clampy(y + j), clampx(x + i)) : |i|, |j| <= r},
+ * with multiplicity, so always n terms.
+ *
+ *   coef       on the net's grid.  I = L(to88(lo_src)) under lo_bgr, in [0, 65280]; P_c = to88(lo_out[..c]).  Window sums in int64: S_I, S_II of
+ *              I I, S_c of P_c, S_Ic of I P_c.
+ *                V = n S_II - S_I^2 (never negative);  C_c = n S_Ic - S_I S_c;  D = V + n^2 E^2 65536
+ *                a_c = (C_c 4096) / D;  b_c = (S_c 4096 - a_c S_I) / (256 n)
+ *              both int64 divisions that truncate towards zero, as C++'s do.  |a_c| < 2^18 (|cov| <= sqrt(var_I var_P) and the
+ *              arithmetic-geometric mean) and |b_c| < 2^27 (S_c 4096 / (256 n) <= 2^20, |a_c| S_I / (256 n) < 2^26), stored as int32:
+ *              coef[H][W][6] = a_0 a_1 a_2 b_0 b_1 b_2.  a is Q12; b is 8.8 with four more fraction bits.
+ *   mean       on the net's grid.  abar_c = (sum over the window of a_c) / n, bbar_c likewise, the sums in int64, the division truncating;
+ *              mean[H][W][6] int32.
+ *   apply      at output pixel (Y, X) of the delivery grid.  Vertical axis: ny = (2Y + 1) H - Hd;  y0 = floor(ny / (2 Hd)), which is -1 for the
+ *              first rows of an enlargement;  fy = ((ny - y0 2 Hd) 256) / (2 Hd), in [0, 255]; the rows read are clampy(y0) and clampy(y0 + 1).
+ *              ny, 2 Hd and the remainder times 256 fit int32 for every side up to 32767.  Horizontal axis: the same with X, W, Wd.  Weights
+ *              (256 - fy)(256 - fx), (256 - fy) fx, fy (256 - fx), fy fx, which sum to 65536.  Ahat_c, Bhat_c: the weighted sums of the four
+ *              abar_c, respectively bbar_c, in int64.  G = L(hi88) under hi_bgr, hi88 = to88(v) for kind 2 and v << 8 for the u8 kinds.
+ *                F_c = clamp((Ahat_c G + (Bhat_c << 8) + 2^27) >> 28, 0, 65280), the shift arithmetic; the sum stays below 2^52
+ *                dst = (float)F_c * 2^-8 (exact)
+ * Hence: a constant lo_out of value v gives F = to88(v) everywhere, for every source, radius and smoothness (a = 0 and b = 16 to88(v)
+ * exactly); a flat lo_src gives a = 0, so F is the bilinear interpolation of the window means of P; with Hd = H and Wd = W, fy = fx = 0 and
+ * y0 = Y, so no interpolation takes place; a source that is NaN, below 0 or above 255 behaves as to88 says.  No value read from a tensor
+ * reaches an address.
+ * Not provided: a colour (three-channel) guide, coefficients on a grid coarser than the net's, delivery below the net's size. */
+
+/* The workspace of fs_guided_f32 for N images on an H x W grid: coef [N, H, W, 6] int32 at offset 0, then mean [N, H, W, 6] int32 at offset
+ * *bytes / 2; each part is N H W 24 bytes rounded up to a multiple of 16.  Host only.  Errors: -1 null bytes, N outside [1, 65535], H or W
+ * outside [1, 32767]. */
+int fs_guided_workspace(int H, int W, int N, size_t* bytes);
+
+/* N images: lo_src [N, H, W, 3], lo_out [N, Ho, Wo, 3], hi_src [N, Hd, Wd, 3 | 4] of hi_kind, dst [N, Hd, Wd, 3] fp32; work: work_bytes >=
+ * fs_guided_workspace's, both parts are written (and may be read back: the layout above).  Asynchronous on the ctx stream, allocates nothing,
+ * can be captured into a hipGraph; grid.z (coef, mean) and grid.y (apply) are the image.  A refused call launches nothing.
+ * Errors: -1 null argument, N outside [1, 65535], H or W below 1, Ho outside [H, H + 3] or Wo outside [W, W + 3], Hd or Wd above 32767, Hd < H or
+ * Wd < W, work_bytes short, dst equal to lo_out, lo_src or hi_src; -2 radius outside [1, 8], smoothness outside [1, 64], hi_kind outside [0, 2],
+ * matrix, lo_bgr or hi_bgr other than 0 or 1; -5 lo_src, lo_out, dst or an fp32 hi_src not 4-byte aligned, work not 16-byte aligned (Wd a
+ * multiple of 4 with hi_src and dst 16-byte aligned takes 16-byte accesses, anything else single bytes and floats, with the same values). */
+int fs_guided_f32(fs_ctx* ctx, const float* lo_src, int H, int W, const float* lo_out, int Ho, int Wo, const void* hi_src, int hi_kind, int Hd,
+                  int Wd, int N, int radius, int smoothness, int matrix, int lo_bgr, int hi_bgr, void* work, size_t work_bytes, float* dst);
+
 #ifdef __cplusplus
 }
 #endif

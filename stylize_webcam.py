@@ -44,6 +44,12 @@ from the net's size to that size on the device -- Pillow's mode-F arithmetic on 
 deliver=) -- so ``--frame_size 1280 720 --output_size source`` runs the net at 720p on a 2160p stream and writes 2160p.  The .png / .jpg
 files, the YUV4MPEG2 header and deep outputs carry that size.  ``--frame_filter F`` lets ``--frame_size`` take a ``--video_depth stream`` input
 of 9 to 16 bits: its fp32 frames are resampled to the net's size the same way (source resample=), with no u8 stage.
+
+Edge-aware delivery: ``--output_guided`` (with ``--frame_size W H`` and an ``--output_size`` that is the source's, ``source`` for one) takes
+the place of the resampling filter: a guided filter fits the stylized picture to the source's luma on the net's grid (``--guided_radius R``,
+1..8, default 2: the window; ``--guided_smoothness E``, 1..64 8-bit levels, default 4) and applies the fit to the full-size source, which the
+lane still holds, so that the source's edges return at the delivery resolution -- three launches in the place of one
+(faststyle_amd/stream.py, deliver guided=).  The luma weights follow --color_matrix / --video_matrix.  Without the flag nothing changes.
 """
 import os
 import sys
@@ -133,11 +139,46 @@ def delivery_options(args):
     return (W, H), filt or 'bicubic'
 
 
-def deliver_dict(delivery, source_size, net_size):
+def guided_options(args, matrix='bt601'):
+    """--output_guided / --guided_radius / --guided_smoothness -> the guided= dict of the lanes' deliver= (faststyle_amd/stream.py), None
+    without --output_guided; matrix: what --color_matrix defaults to.  The flags are absent from the namespace unless given.  A value flag
+    without --output_guided, a value outside its range, --output_guided without --output_size or --frame_size or together with
+    --output_filter is a SystemExit here, before anything is loaded.  Every path of this script feeds the net B,G,R: the stage is told so
+    (source_bgr)."""
+    on = getattr(args, 'output_guided', False)
+    for flag in ('guided_radius', 'guided_smoothness'):
+        if hasattr(args, flag) and not on:
+            raise SystemExit('--%s needs --output_guided' % flag)
+    if not on:
+        return None
+    radius, smoothness = getattr(args, 'guided_radius', 2), getattr(args, 'guided_smoothness', 4)
+    if not 1 <= radius <= 8:
+        raise SystemExit('--guided_radius %d is outside [1, 8]' % radius)
+    if not 1 <= smoothness <= 64:
+        raise SystemExit('--guided_smoothness %d is outside [1, 64]' % smoothness)
+    if getattr(args, 'output_size', None) is None:
+        raise SystemExit("--output_guided needs --output_size: the source's own size ('source')")
+    if getattr(args, 'output_filter', None) is not None:
+        raise SystemExit('--output_guided and --output_filter are mutually exclusive: the delivery is guided or resampled')
+    if args.frame_size is None:
+        raise SystemExit("--output_guided needs --frame_size W H: the net runs below the source's size and the full-size source guides the delivery")
+    return dict(radius=radius, smoothness=smoothness, matrix=args.color_matrix or matrix, source_bgr=True)
+
+
+def deliver_dict(delivery, source_size, net_size, guided=None):
     """The deliver= dict of the lanes for delivery_options' answer (source_size, net_size: (W, H)); the resampling plan is checked here, on the
-    host: a size the kernel does not take is a SystemExit."""
+    host: a size the kernel does not take is a SystemExit.  guided: guided_options' answer; the delivery then has the source's size, which
+    is no smaller than the net's and not the net's."""
     from faststyle_amd import _lib, engine
     W, H = source_size if delivery[0] == 'source' else delivery[0]
+    if guided is not None:
+        if (W, H) != tuple(source_size):
+            raise SystemExit("--output_guided: the delivery is %d by %d, the source %d by %d: the full-size source guides the delivery, so "
+                             "--output_size is the source's size ('source')" % ((W, H) + tuple(source_size)))
+        if W < net_size[0] or H < net_size[1] or (W, H) == tuple(net_size) or max(W, H) > 32767:
+            raise SystemExit('--output_guided upsamples: a source of %d by %d with the net at %d by %d (--frame_size no larger than the source '
+                             'on both sides, smaller on one)' % ((W, H) + tuple(net_size)))
+        return dict(height=H, width=W, guided=guided)
     try:
         engine.ResampleHost().resample_plan(net_size[1], net_size[0], H, W, delivery[1])
     except _lib.FaststyleError as e:
@@ -163,6 +204,7 @@ def run_frames_dir(args):
     compose = compose_options(args)
     temporal = temporal_options(args)
     delivery = delivery_options(args)
+    guided = guided_options(args)
     first_size = None
     if delivery is not None or (compose is not None and 'mask' in compose and (args.frame_size or args.resolution) is None):
         try:
@@ -174,7 +216,7 @@ def run_frames_dir(args):
         check_mask_size(args, compose, *(args.frame_size or args.resolution or first_size))
     if delivery is not None:                                     # ('source': the first frame's own size, for every frame; checked before the model is loaded)
         delivery = (tuple(first_size) if delivery[0] == 'source' else delivery[0], delivery[1])
-        deliver_dict(delivery, first_size, tuple(args.frame_size or args.resolution or first_size))
+        deliver_dict(delivery, first_size, tuple(args.frame_size or args.resolution or first_size), guided)
     eng, variables = _load(args)
     if not os.path.isdir(args.output_dir):
         os.makedirs(args.output_dir)
@@ -239,7 +281,7 @@ def run_frames_dir(args):
         check_mask_size(args, compose, W, H)
         more = dict(kw, source=source) if source is not None else kw
         if delivery is not None:
-            more = dict(more, deliver=deliver_dict(delivery, (Ws, Hs), (W, H)))
+            more = dict(more, deliver=deliver_dict(delivery, (Ws, Hs), (W, H), guided))
             print('Output size is: {0} by {1}'.format(*delivery[0]))
         if depth > 1:
             return stream.PipelinedStylizer(eng, variables, H, W, depth=depth, upsample_method=args.upsample_method, **more)
@@ -299,6 +341,7 @@ def run_video(args):
     compose = compose_options(args, args.video_matrix)
     temporal = temporal_options(args, args.video_matrix)
     delivery = delivery_options(args)
+    guided = guided_options(args, args.video_matrix)
     frame_filter = getattr(args, 'frame_filter', None)
     to_stdout = args.video_out == '-'
     log = sys.stderr if to_stdout else sys.stdout
@@ -336,7 +379,7 @@ def run_video(args):
         check_mask_size(args, compose, W, H)
         deliver = None
         if delivery is not None:                                             # (a size the kernel or the output layout does not take: said before the model is loaded)
-            deliver = deliver_dict(delivery, (Ws, Hs), (W, H))
+            deliver = deliver_dict(delivery, (Ws, Hs), (W, H), guided)
             try:
                 if args.video_out is not None:
                     engine.YuvHost().yuv_plan(deliver['width'], deliver['height'], **colour_out)
@@ -445,20 +488,27 @@ def run_webcam(args):
     compose = compose_options(args)
     temporal = temporal_options(args)
     delivery = delivery_options(args)
+    guided = guided_options(args)
     cap = cv2.VideoCapture(0)
     if args.resolution is not None:
         x_length, y_length = args.resolution
         cap.set(cv2.CAP_PROP_FRAME_WIDTH, x_length)      # (the reference passes the raw property ids 3 and 4: stylize_webcam.py:52-53)
         cap.set(cv2.CAP_PROP_FRAME_HEIGHT, y_length)
     x_new, y_new = int(cap.get(cv2.CAP_PROP_FRAME_WIDTH)), int(cap.get(cv2.CAP_PROP_FRAME_HEIGHT))
+    x_cam, y_cam = x_new, y_new
+    if guided is not None:                                   # (the one case in which the camera's frames are resized on the device: to --frame_size)
+        x_new, y_new = args.frame_size
+        deliver_dict(delivery, (x_cam, y_cam), (x_new, y_new), guided)
     print('Resolution is: {0} by {1}'.format(x_new, y_new))
     check_mask_size(args, compose, x_new, y_new)
     print('Loading up model...')
     eng, variables = _load(args)
     more = dict(temporal=temporal) if temporal is not None else {}
+    if guided is not None:
+        more['source'] = dict(height=y_cam, width=x_cam)
     x_out, y_out = x_new, y_new
     if delivery is not None:
-        more['deliver'] = deliver_dict(delivery, (x_new, y_new), (x_new, y_new))
+        more['deliver'] = deliver_dict(delivery, (x_cam, y_cam), (x_new, y_new), guided)
         x_out, y_out = more['deliver']['width'], more['deliver']['height']
         print('Output size is: {0} by {1}'.format(x_out, y_out))
     if compose is not None:                                  # (compose_options: the lane does not swap, the loop below does)

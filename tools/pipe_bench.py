@@ -29,6 +29,10 @@ written to profiles/video_temporal_pyr.json.  "temporal_pyr_kernels" as the thir
 bicubic and lanczos, 2160 x 3840 -> 720 x 1280 bicubic; and the raw-video loop over a 2160p 4:2:0 file with --frame_size 1280 720, without and
 with --output_size source, as two legs that alternate in the one run (rates from the difference between n and n / 4 frames); written to
 profiles/video_resample.json with the digest of the kernel sources.
+"guided" (pipe_bench.py 96 4 guided): guided delivery.  One call of fs_guided_f32 alone (its three launches back to back, the graph-of-200
+scheme, data resident): 720 x 1280 -> 2160 x 3840 at radius 2 for an RGBX and an fp32 source, at radius 8, and the bicubic fs_resample_f32 of
+the same enlargement in the same run; and the 2160p raw-video loop with --frame_size 1280 720 --output_size source, resampled (bicubic) and
+with --output_guided, alternating in the one run; written to profiles/video_guided.json with the digest of the kernel sources.
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -235,8 +239,46 @@ def resample_kernel_times(launches=200):
     return res
 
 
-def resample(n, repeats=3, out_json=None):
-    """-> dict: resample_kernel_times and the two video legs; prints them and writes profiles/video_resample.json."""
+def guided_kernel_times(launches=200):
+    """-> dict of device microseconds per call of fs_guided_f32 (coef, mean and apply back to back), timed as kernel_times does, and of the
+    bicubic fs_resample_f32 of the same enlargement, with the bytes each call reads and writes at least once."""
+    eng = engine.Engine()
+    mem = eng.mem
+    rng = np.random.default_rng(5)
+    H, W, Hd, Wd = 720, 1280, 2160, 3840
+    lo_src = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    lo_out = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    hi = {"rgbx_u8": mem.upload_u8(rng.integers(0, 256, (1, Hd, Wd, 4), dtype=np.uint8)),
+          "fp32": mem.from_numpy(rng.uniform(0, 255, (1, Hd, Wd, 3)).astype(np.float32))}
+    out = mem.empty((1, Hd, Wd, 3))
+    work = eng.guided_workspace(H, W, 1)
+    res = {}
+    for name, kind, radius in (("720p_to_2160p_radius2_rgbx_u8", "rgbx_u8", 2), ("720p_to_2160p_radius2_fp32", "fp32", 2),
+                               ("720p_to_2160p_radius8_rgbx_u8", "rgbx_u8", 8)):
+        us = kernel_timed(lambda: eng.guided_f32(lo_src, lo_out, hi[kind], out, work, radius=radius, smoothness=4), launches)
+        low = 2 * 4 * H * W * 3 + 3 * H * W * 24                 # coef: the two tensors in, coef out; mean: coef in, mean out
+        high = H * W * 24 + Hd * Wd * (4 if kind == "rgbx_u8" else 12) + Hd * Wd * 12      # apply: mean and the source in, the result out
+        res[name] = {"us": us, "bytes_low_resolution_launches": low, "bytes_apply_launch": high, "GB_per_s_of_all": (low + high) / us / 1e3}
+        print("guided: %8.1f us per call (three launches), %6.0f GB/s of everything read and written once: %s" % (us, (low + high) / us / 1e3, name))
+    plan = eng.resample_plan(H, W, Hd, Wd, "bicubic")
+    us = kernel_timed(lambda: eng.resample_f32(lo_out, plan, out), launches)
+    nbytes = 4 * (H * W * 3 + Hd * Wd * 3)
+    res["resample_720p_to_2160p_bicubic"] = {"us": us, "bytes_read_and_written": nbytes, "GB_per_s": nbytes / us / 1e3}
+    print("guided: %8.1f us per call, %6.0f GB/s: fs_resample_f32 bicubic, the same enlargement" % (us, nbytes / us / 1e3))
+    return res
+
+
+def guided(n, repeats=3, out_json=None):
+    """-> dict: guided_kernel_times and the two video legs; prints them and writes profiles/video_guided.json."""
+    w, h = 3840, 2160
+    legs = [("video_y4m_2160p_net_720p_out_2160p_bicubic", ["--output_size", "source"], w * h),
+            ("video_y4m_2160p_net_720p_out_2160p_guided", ["--output_size", "source", "--output_guided"], w * h)]
+    return resample(n, repeats, out_json, legs=legs, kernels=guided_kernel_times, tag="guided", default_json="video_guided.json")
+
+
+def resample(n, repeats=3, out_json=None, legs=None, kernels=None, tag="resample", default_json="video_resample.json"):
+    """-> dict: resample_kernel_times and the two video legs; prints them and writes profiles/video_resample.json (guided(): its own legs and
+    kernel times, to profiles/video_guided.json)."""
     import contextlib
     import json
     import shutil
@@ -262,7 +304,7 @@ def resample(n, repeats=3, out_json=None):
                 f.write(planes[k % 16])
     parser = stylize_webcam.setup_parser()
     out = os.path.join(d, "out.y4m")
-    legs = [("video_y4m_2160p_net_720p_out_720p", [], 1280 * 720), ("video_y4m_2160p_net_720p_out_2160p_bicubic", ["--output_size", "source"], w * h)]
+    legs = legs or [("video_y4m_2160p_net_720p_out_720p", [], 1280 * 720), ("video_y4m_2160p_net_720p_out_2160p_bicubic", ["--output_size", "source"], w * h)]
 
     def run(count, flags, pixels):
         args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--video_in", os.path.join(d, "2160p_%d.y4m" % count),
@@ -280,7 +322,7 @@ def resample(n, repeats=3, out_json=None):
     for _ in range(repeats):                                      # legs alternate: a drifting clock touches both alike
         for name, flags, pixels in legs:
             times[name].append((run(n, flags, pixels), run(n // 4, flags, pixels)))
-            print("resample: %s: %.2f s for %d frames, %.2f s for %d" % ((name,) + (times[name][-1][0], n, times[name][-1][1], n // 4)), flush=True)
+            print("%s: %s: %.2f s for %d frames, %.2f s for %d" % ((tag, name) + (times[name][-1][0], n, times[name][-1][1], n // 4)), flush=True)
     shutil.rmtree(d)
     res = {"frames": n, "frames_in_flight": 2, "host_threads": "1 driver", "host_cores": os.cpu_count(), "omp_num_threads": os.environ.get("OMP_NUM_THREADS"),
            "video": "2160p 4:2:0 YUV4MPEG2 (full range, BT.601) from a file, --frame_size 1280 720, to a file of 8-bit 4:2:0",
@@ -288,9 +330,9 @@ def resample(n, repeats=3, out_json=None):
     for name, _, _ in legs:
         rates = sorted((n - n // 4) / (a - b) for a, b in times[name])
         res["legs"][name] = {"frames_per_s": rates[len(rates) // 2], "all_repeats": rates, "seconds_n_and_quarter": times[name]}
-        print("resample: %7.0f frames/s %s (repeats: %s)" % (rates[len(rates) // 2], name, ", ".join("%.0f" % r for r in rates)))
-    res["kernel_per_call"] = resample_kernel_times()
-    with open(out_json or os.path.join(root, "profiles", "video_resample.json"), "w") as f:
+        print("%s: %7.0f frames/s %s (repeats: %s)" % (tag, rates[len(rates) // 2], name, ", ".join("%.0f" % r for r in rates)))
+    res["kernel_per_call"] = (kernels or resample_kernel_times)()
+    with open(out_json or os.path.join(root, "profiles", default_json), "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     return res
@@ -455,6 +497,12 @@ def main():
         return
     if len(sys.argv) > 3 and sys.argv[3] == "resample":
         resample(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None)
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "guided":
+        guided(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None)
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "guided_kernels":
+        guided_kernel_times()
         return
     if len(sys.argv) > 3 and sys.argv[3] == "temporal_kernels":
         temporal_kernel_times()
