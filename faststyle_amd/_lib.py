@@ -222,6 +222,8 @@ PROTOTYPES = {
     "fs_temporal_pyr_layout": (c_int, [c_int, c_int, c_int, POINTER(fs_temporal_pyr_info)]),
     "fs_temporal_pyr_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fs_temporal_sub_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fs_resample_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_resample_info)]),
     "fs_resample_tables": (c_int, [POINTER(fs_resample_info), c_void_p, c_size_t]),
     "fs_resample_f32": (c_int, [c_void_p, POINTER(fs_resample_info), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -121,6 +121,9 @@ def stylize_webcam_parser():
         ('--temporal_levels', dict(default=argparse.SUPPRESS, type=int, metavar='L',
                                    help="(addition) search the motion vectors coarse to fine over L halved lumas, 1..3 (default 1): fast motion, "
                                         "found reliably up to about R 2^(L-1) pixels; needs --temporal_strength")),
+        ('--temporal_subpel', dict(default=argparse.SUPPRESS, type=int, metavar='S',
+                                   help="(addition) motion vectors in whole (0, the default), half (1) or quarter pixels (2): slow motion keeps "
+                                        "its match, for one more launch and a bilinear fetch; needs --temporal_strength")),
         ('--temporal_sensitivity', dict(default=argparse.SUPPRESS, type=int, metavar='K',
                                         help="(addition) how fast a source mismatch turns the blend off, 1..256: none of it is left at a luma "
                                              "difference of 256 / K (default 16)")),

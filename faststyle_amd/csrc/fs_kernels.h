@@ -705,6 +705,11 @@ int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int W
 int temporal_pyr_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
                      int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
                      unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, float* dst, hipStream_t s);
+// ... with block vectors in half (subpel 1) or quarter pixels (2): the launches above up to the searches, the refinement that writes mvf, and
+// the bilinear blend; subpel 0 is temporal_pyr_f32 and leaves mvf alone
+int temporal_sub_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
+                     int subpel, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
+                     unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf, float* dst, hipStream_t s);
 // resampling between fp32 tensors (fs_resample.hip): whether a plan is what fs_resample_plan fills, and the one launch (argument checks are in
 // fs_api.hip)
 bool resample_plan_ok(const ::fs_resample_info& plan);

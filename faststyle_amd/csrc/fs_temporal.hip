@@ -18,6 +18,7 @@
 // fs_temporal_pyr_f32 reaches further with the same pieces: a pyramid kernel halves the luma once or twice (elementwise, one launch), and the
 // search runs per level, coarsest first, on a window displaced by twice the coarser level's vector (temporal_search_pred_kernel: the search
 // above plus that predictor, which is held to its bound before it reaches an address); the blend is the one above with the larger bound.
+// fs_temporal_sub_f32 adds a fraction per block in quarter pixels and a bilinear fetch (the last part of this file).
 #include <cstring>
 
 #include "../../include/faststyle_io.h"
@@ -401,6 +402,240 @@ int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int W
     BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = radius;
     hipLaunchKernelGGL(temporal_blend_kernel, egrid, block, 0, s, BA, cur, (const unsigned char*)luma, prev_luma, prev_out88, (const signed char*)mv, dst,
                        out88);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// ---- quarter-pixel vectors (fs_temporal_sub_f32): a fraction per block from five SADs around the whole-pixel winner, and a bilinear fetch
+//   subpel -- one workgroup of 256 threads per 16x16 block of level 0.  The previous luma's 18 x 18 window around the block displaced by its
+//             vector (one pixel more on every side, every coordinate clamped) and the block's bytes go to LDS as in the search.  Thread t has
+//             block row (t >> 2) & 15 and dword t & 3 of that row; the wave t >> 6 says which sums it forms: 0 the row above, 1 the row below,
+//             2 the columns left and right, 3 the winner itself.  A thread reads the two window dwords that hold its four bytes, shifts them
+//             into place and adds one packed-byte SAD per sum.  Window pitch 12 dwords: the lanes of a 32-lane half are 8 consecutive rows x
+//             4 dwords at dword address 12 row + k (+ a constant per wave), and 12 row mod 32 over 8 consecutive rows is a permutation of
+//             {0, 4, ..., 28} -- 32 lanes on 32 banks, conflict-free by the rule that ds_read_b32 (and ds_read2_b32) banks are (a / 4) mod 32
+//             per 32-lane half; the block's dwords are at 4 row + k, the lane's own index.  The five sums of 64 partial sums each are reduced
+//             by an LDS tree; thread 0 fits and writes the fraction.
+//   blend  -- temporal_blend_kernel with the previous luma and output fetched bilinearly at quarter-pixel positions: two rows by five columns
+//             per thread, the second row / column only where the fraction along it is not zero.
+namespace {
+
+constexpr int SPITCH = 12;                 // dwords per LDS window row of the refinement: 5 used (18 bytes, the read of dword 4 ends at byte 19)
+constexpr int SWROWS = TB + 2;              // 18
+
+// the contract's fit: m, p the SADs one pixel before / after the winner's s0 along one axis -> the fraction in quarter pixels
+__device__ __forceinline__ int subpel_fit(int s0, int m, int p, int S) {
+    const int E = (m > p ? m : p) - s0;
+    if (E <= 0) return 0;
+    const int num = (m - p) * (1 << S) + E, den = 2 * E;    // |num| < 2^20
+    int g = num / den;
+    if (num < 0 && g * den != num) --g;                     // a true floor
+    const int half = 1 << (S - 1);
+    g = g < -half ? -half : (g > half ? half : g);
+    return g * (1 << (2 - S));
+}
+
+// One workgroup per block (blockIdx.y, blockIdx.x) of level 0.  prev8 == nullptr (no previous frame) or R == 0: every fraction is (0, 0).
+// mv is held to `hold` per component before it reaches an address; nothing else read from a buffer does.
+__global__ __launch_bounds__(256) void temporal_subpel_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int Ho,
+                                                              int Wo, int R, int hold, int S, const signed char* __restrict__ mv,
+                                                              signed char* __restrict__ mvf) {
+    __shared__ unsigned win[SWROWS * SPITCH];
+    __shared__ unsigned blk[TB * (TB / 4)];
+    __shared__ unsigned part[5 * 64];                       // S0, Sym, Syp, Sxm, Sxp: 64 partial sums each
+    const int t = (int)threadIdx.x;
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    const size_t b = (size_t)by * gridDim.x + bx;
+    signed char* out = mvf + b * 2;
+    if (prev8 == nullptr || R == 0) {                       // (uniform per launch)
+        if (t == 0) { out[0] = 0; out[1] = 0; }
+        return;
+    }
+    int dy = (int)mv[b * 2], dx = (int)mv[b * 2 + 1];
+    dy = dy < -hold ? -hold : (dy > hold ? hold : dy);      // (the search wrote them within it; held to it again)
+    dx = dx < -hold ? -hold : (dx > hold ? hold : dx);
+    const int y0 = by * TB, x0 = bx * TB;
+    const int rows = Ho - y0 < TB ? Ho - y0 : TB, cols = Wo - x0 < TB ? Wo - x0 : TB;        // at least 1 each
+    if (t < SWROWS * 5) {                                   // window row t / 5, dword t % 5: frame rows y0 + dy - 1 ..., columns x0 + dx - 1 ...
+        const int wr = t / 5, wd = t - wr * 5;
+        const unsigned char* prow = prev8 + (size_t)clampi(y0 + dy - 1 + wr, Ho - 1) * Wo;
+        unsigned v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v |= (unsigned)prow[clampi(x0 + dx - 1 + wd * 4 + k, Wo - 1)] << (8 * k);
+        win[wr * SPITCH + wd] = v;
+    }
+    if (t < TB * (TB / 4)) {                                // block row t / 4, dword t % 4
+        const int r = t >> 2, c = (t & 3) * 4;
+        unsigned v = 0;
+        if (r < rows) {
+            const unsigned char* crow = cur8 + (size_t)(y0 + r) * Wo + x0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (c + k < cols) v |= (unsigned)crow[c + k] << (8 * k);
+        }
+        blk[t] = v;
+    }
+    __syncthreads();
+    {
+        const int r = (t >> 2) & 15, k = t & 3, which = t >> 6;                 // (which: uniform per wave)
+        const int inside = cols - 4 * k;
+        const unsigned m = r >= rows || inside <= 0 ? 0u : (inside >= 4 ? 0xFFFFFFFFu : (1u << (8 * inside)) - 1u);
+        const unsigned c = blk[r * 4 + k];                  // (zero outside the frame, as the masked window bytes are)
+        const int wr = r + (which == 0 ? 0 : (which == 1 ? 2 : 1));             // the window's row of the block's row r: r + 1 + u
+        const unsigned long long w = ((unsigned long long)win[wr * SPITCH + k + 1] << 32) | win[wr * SPITCH + k];
+        const unsigned mid = sad4((unsigned)(w >> 8) & m, c, 0u);              // the window's column of the block's column x: x + 1 + v
+        const int i = t & 63;
+        if (which == 0) part[64 + i] = mid;
+        else if (which == 1) part[128 + i] = mid;
+        else if (which == 3) part[i] = mid;
+        else {
+            part[192 + i] = sad4((unsigned)w & m, c, 0u);
+            part[256 + i] = sad4((unsigned)(w >> 16) & m, c, 0u);
+        }
+    }
+    __syncthreads();
+    for (int s = 32; s > 0; s >>= 1) {                      // thread t: sum t >> 5 (below 5), entry t & 31
+        if (t < 160 && (t & 31) < s) part[(t >> 5) * 64 + (t & 31)] += part[(t >> 5) * 64 + (t & 31) + s];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const int s0 = (int)part[0];
+        out[0] = (signed char)subpel_fit(s0, (int)part[64], (int)part[128], S);
+        out[1] = (signed char)subpel_fit(s0, (int)part[192], (int)part[256], S);
+    }
+}
+
+// temporal_blend_kernel's threads and arguments, with the block's fraction mvf beside its vector: the previous luma and output are fetched
+// at (4 (y + dy) + fy, 4 (x + dx) + fx) quarter pixels, bilinearly between the two rows and the five columns that the thread's four pixels
+// touch, every one clamped into the frame.  ay and ax are the same for the four pixels (4 x is a multiple of 4).  dst may be cur, as there.
+__global__ __launch_bounds__(256) void temporal_blend_sub_kernel(const BlendArgs A, const float* cur, const unsigned char* __restrict__ cur8,
+                                                                 const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
+                                                                 const signed char* __restrict__ mv, const signed char* __restrict__ mvf, float* dst,
+                                                                 unsigned short* __restrict__ out88) {
+    const int groups = (A.Wo + 3) >> 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)groups * A.Ho) return;
+    const int y = (int)(i / groups), x0 = (int)(i - (long long)y * groups) * 4;
+    const size_t row = (size_t)y * A.Wo;
+    int ay = 0, ax = 0;
+    size_t r0 = 0, r1 = 0;                                  // the two rows' first pixels
+    int col[5] = {0, 0, 0, 0, 0};
+    if (prev8 != nullptr) {                                 // (uniform per launch)
+        const size_t b = ((size_t)(y >> 4) * A.nbx + (x0 >> 4)) * 2;
+        const int dy = (int)mv[b] < -A.R ? -A.R : ((int)mv[b] > A.R ? A.R : (int)mv[b]);     // (written within these bounds; held to them again)
+        const int dx = (int)mv[b + 1] < -A.R ? -A.R : ((int)mv[b + 1] > A.R ? A.R : (int)mv[b + 1]);
+        const int fy = (int)mvf[b] < -2 ? -2 : ((int)mvf[b] > 2 ? 2 : (int)mvf[b]);
+        const int fx = (int)mvf[b + 1] < -2 ? -2 : ((int)mvf[b + 1] > 2 ? 2 : (int)mvf[b + 1]);
+        const int Y4 = 4 * (y + dy) + fy, X4 = 4 * (x0 + dx) + fx;
+        ay = Y4 & 3; ax = X4 & 3;
+        r0 = (size_t)clampi(Y4 >> 2, A.Ho - 1) * A.Wo;
+        r1 = (size_t)clampi((Y4 >> 2) + 1, A.Ho - 1) * A.Wo;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) col[j] = clampi((X4 >> 2) + j, A.Wo - 1);
+    }
+    const int n = A.Wo - x0 < 4 ? A.Wo - x0 : 4;
+    const size_t at0 = (row + x0) * 3;
+    float b[12];                                            // every read of cur before the first write of dst: the two may be one tensor
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int xn = k < n ? k : n - 1;                   // (beyond the row's end: the last pixel again, never stored)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b[3 * k + c] = cur[at0 + 3 * xn + c];
+    }
+    const int wy0 = 4 - ay, wx0 = 4 - ax;
+    int F[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int xn = x0 + (k < n ? k : n - 1);
+        const int B0 = temporal_f88(b[3 * k]), B1 = temporal_f88(b[3 * k + 1]), B2 = temporal_f88(b[3 * k + 2]);
+        F[3 * k] = B0; F[3 * k + 1] = B1; F[3 * k + 2] = B2;
+        if (prev8 != nullptr) {
+            const size_t q00 = r0 + col[k], q01 = r0 + col[k + 1], q10 = r1 + col[k], q11 = r1 + col[k + 1];
+            int pq = (int)prev8[q00];
+            int P0 = prev88[q00 * 3], P1 = prev88[q00 * 3 + 1], P2 = prev88[q00 * 3 + 2];
+            if (ay | ax) {                                  // a weight of zero stands before whatever is not fetched
+                int l01 = 0, l10 = 0, l11 = 0, p01[3] = {0, 0, 0}, p10[3] = {0, 0, 0}, p11[3] = {0, 0, 0};
+                if (ax) {
+                    l01 = prev8[q01];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) p01[c] = prev88[q01 * 3 + c];
+                }
+                if (ay) {
+                    l10 = prev8[q10];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) p10[c] = prev88[q10 * 3 + c];
+                    if (ax) {
+                        l11 = prev8[q11];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) p11[c] = prev88[q11 * 3 + c];
+                    }
+                }
+                pq = (wy0 * (wx0 * pq + ax * l01) + ay * (wx0 * l10 + ax * l11) + 8) >> 4;
+                P0 = (wy0 * (wx0 * P0 + ax * p01[0]) + ay * (wx0 * p10[0] + ax * p11[0]) + 8) >> 4;      // at most 16 x 65280 + 8
+                P1 = (wy0 * (wx0 * P1 + ax * p01[1]) + ay * (wx0 * p10[1] + ax * p11[1]) + 8) >> 4;
+                P2 = (wy0 * (wx0 * P2 + ax * p01[2]) + ay * (wx0 * p10[2] + ax * p11[2]) + 8) >> 4;
+            }
+            const int d = (int)cur8[row + xn] - pq;
+            const int e = d < 0 ? -d : d;
+            const int conf = 256 - e * A.sensitivity;
+            const long long w = (long long)A.strength_q8 * (conf > 0 ? conf : 0);        // 0 ... 65536
+            F[3 * k] = B0 + (int)(((long long)(P0 - B0) * w + 32768) >> 16);
+            F[3 * k + 1] = B1 + (int)(((long long)(P1 - B1) * w + 32768) >> 16);
+            F[3 * k + 2] = B2 + (int)(((long long)(P2 - B2) * w + 32768) >> 16);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < n) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                dst[at0 + 3 * k + c] = (float)F[3 * k + c] * 0.00390625f;
+                out88[at0 + 3 * k + c] = (unsigned short)F[3 * k + c];
+            }
+        }
+}
+
+}  // namespace
+
+// arguments: checked by the caller (fs_api.hip: fs_temporal_sub_f32), lay: fs_temporal_pyr_layout's for the call's Ho, Wo and levels.
+// subpel 0 is temporal_pyr_f32; above it, its launches up to the searches, the refinement, and the bilinear blend in place of the whole-pixel one.
+int temporal_sub_f32(const fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
+                     int subpel, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
+                     unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf, float* dst, hipStream_t s) {
+    if (subpel == 0)
+        return temporal_pyr_f32(lay, src, H, W, cur, strength_q8, sensitivity, radius, matrix, src_bgr, prev_luma, prev_out88, prev_pyr, luma, out88, pyr,
+                                mv, dst, s);
+    const int L = lay.levels, Ho = lay.h[0], Wo = lay.w[0];
+    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
+    LumaArgs LA;
+    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
+    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
+    const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
+    const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
+    hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, src, luma);
+    if (L > 1) {
+        PyrArgs PA;
+        PA.H0 = Ho; PA.W0 = Wo; PA.H1 = lay.h[1]; PA.W1 = lay.w[1];
+        PA.H2 = L > 2 ? lay.h[2] : 0; PA.W2 = L > 2 ? lay.w[2] : 0;
+        const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);
+        hipLaunchKernelGGL(temporal_pyramid_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks), block, 0, s, PA, (const unsigned char*)luma,
+                           pyr + lay.luma_offset[1], L > 2 ? pyr + lay.luma_offset[2] : nullptr);
+    }
+    for (int l = L - 1; l >= 0; --l) {                      // coarsest first, as in temporal_pyr_f32
+        const unsigned char* c = l ? pyr + lay.luma_offset[l] : luma;
+        const unsigned char* p = prev_luma == nullptr ? nullptr : (l ? prev_pyr + lay.luma_offset[l] : prev_luma);
+        const signed char* parent = l == L - 1 ? nullptr : (const signed char*)(pyr + lay.mv_offset[l + 1]);
+        signed char* v = l ? (signed char*)(pyr + lay.mv_offset[l]) : mv;
+        hipLaunchKernelGGL(temporal_search_pred_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l]), block, 0, s, c, p, lay.h[l], lay.w[l], radius,
+                           parent, l == L - 1 ? 0 : lay.nbx[l + 1], 2 * radius * ((1 << (L - 1 - l)) - 1), v);
+    }
+    const int hold = radius * ((1 << L) - 1);
+    hipLaunchKernelGGL(temporal_subpel_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0]), block, 0, s, (const unsigned char*)luma, prev_luma, Ho, Wo,
+                       radius, hold, subpel, (const signed char*)mv, mvf);
+    BlendArgs BA;
+    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = lay.nbx[0];
+    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = hold;
+    hipLaunchKernelGGL(temporal_blend_sub_kernel, egrid, block, 0, s, BA, cur, (const unsigned char*)luma, prev_luma, prev_out88, (const signed char*)mv,
+                       (const signed char*)mvf, dst, out88);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -1069,16 +1069,21 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
         L.check(self.lib, self.lib.fs_temporal_pyr_layout(int(Ho), int(Wo), int(levels), ctypes.byref(info)), "fs_temporal_pyr_layout")
         return info
 
-    def temporal_state(self, Ho, Wo, levels=1):
+    def temporal_state(self, Ho, Wo, levels=1, subpel=0):
         """One state slot of fs_temporal_f32 for an Ho x Wo output, as device uint8 buffers (the memory backend's): (luma [Ho,Wo], out88
         [Ho,Wo,3,2] -- little-endian u16 on the 8.8 scale --, mv [nby,nbx,2] -- signed char (dy, dx) per 16 x 16 block).  levels > 1
-        (fs_temporal_pyr_f32) appends pyr [pyr_bytes]: the halved lumas and the coarse vectors, laid out as temporal_pyr_layout says."""
+        (fs_temporal_pyr_f32) appends pyr [pyr_bytes]: the halved lumas and the coarse vectors, laid out as temporal_pyr_layout says.
+        subpel > 0 (fs_temporal_sub_f32) appends mvf [nby,nbx,2] as the last buffer: signed char (fy, fx) per block, in quarter pixels."""
         Ho, Wo = int(Ho), int(Wo)
         up = self.mem.upload_u8
         slot = (up(np.zeros((Ho, Wo), np.uint8)), up(np.zeros((Ho, Wo, 3, 2), np.uint8)), up(np.zeros(((Ho + 15) // 16, (Wo + 15) // 16, 2), np.uint8)))
-        if levels == 1:
-            return slot
-        return slot + (up(np.zeros((int(self.temporal_pyr_layout(Ho, Wo, levels).pyr_bytes),), np.uint8)),)
+        if subpel != 0:
+            self._temporal_sub_check(levels, subpel)
+        if levels != 1:
+            slot = slot + (up(np.zeros((int(self.temporal_pyr_layout(Ho, Wo, levels).pyr_bytes),), np.uint8)),)
+        if subpel != 0:
+            slot = slot + (up(np.zeros(((Ho + 15) // 16, (Wo + 15) // 16, 2), np.uint8)),)
+        return slot
 
     def temporal_pyramid(self, state, Ho, Wo, levels):
         """For tests and debugging: what a slot of a `levels`-level search holds beyond level 0, as host arrays -> (lumas, vectors), the
@@ -1094,13 +1099,17 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
             vectors.append(raw[lay.mv_offset[l]:lay.mv_offset[l] + nby * nbx * 2].view(np.int8).reshape(nby, nbx, 2))
         return lumas, vectors
 
-    def temporal_f32(self, src, cur, dst, state, prev=None, strength_q8=256, sensitivity=16, radius=7, matrix="bt601", src_bgr=False, levels=1):
+    def temporal_f32(self, src, cur, dst, state, prev=None, strength_q8=256, sensitivity=16, radius=7, matrix="bt601", src_bgr=False, levels=1,
+                     subpel=0):
         """fs_temporal_f32: src device float32 [H,W,3] (the net's input), cur and dst device float32 [Ho,Wo,3] (the tensor the output
         conversions would read and the stabilised one; dst may be cur; a leading axis of 1 is taken), state the slot written (temporal_state's
         triple), prev the slot the previous frame wrote (None: no previous frame) -> dst = cur blended towards prev's output along the
         block vectors found between the two lumas; matrix 'bt601' / 'bt709' or 0 / 1, src_bgr: channel 0 of src is blue.  levels > 1:
-        fs_temporal_pyr_f32, the coarse-to-fine search, on slots of temporal_state(Ho, Wo, levels)."""
+        fs_temporal_pyr_f32, the coarse-to-fine search, on slots of temporal_state(Ho, Wo, levels).  subpel 1 / 2: fs_temporal_sub_f32, vectors
+        in half / quarter pixels and a bilinear fetch, on slots of temporal_state(Ho, Wo, levels, subpel)."""
         self._sync_stream()
+        if subpel != 0:
+            return self._temporal_sub_f32(src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel)
         if levels != 1:
             return self._temporal_pyr_f32(src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels)
         ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
@@ -1145,6 +1154,42 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
                                                        int(sensitivity), int(radius), int(levels), int(matrix), 1 if src_bgr else 0, pl, po, pp,
                                                        p8(state[0]), p8(state[1]), p8(state[3]), p8(state[2]), self.mem.ptr(dst)),
                 "fs_temporal_pyr_f32")
+        return dst
+
+    @staticmethod
+    def _temporal_sub_check(levels, subpel):
+        for name, v, lo, hi in (("levels", levels, 1, 3), ("subpel", subpel, 0, 2)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise L.FaststyleError("temporal_f32: %s must be a whole number in [%d, %d], got %r" % (name, lo, hi, v))
+
+    def _temporal_sub_f32(self, src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel):
+        """temporal_f32 with subpel > 0: the shape checks with the slot held against (levels, subpel) -- the pyramid buffer fourth when levels
+        > 1, mvf last --, then fs_temporal_sub_f32."""
+        self._temporal_sub_check(levels, subpel)
+        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
+        if len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,):
+            ss, cs, ds = ss[1:], cs[1:], ds[1:]
+        if len(ss) != 3 or len(cs) != 3 or ss[2] != 3 or cs[2] != 3 or ds != cs:
+            raise L.FaststyleError("temporal_f32: source %s / current %s / destination %s do not belong together (one image per call)" %
+                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
+        Ho, Wo = cs[:2]
+        blocks = ((Ho + 15) // 16, (Wo + 15) // 16, 2)
+        want = ((Ho, Wo), (Ho, Wo, 3, 2), blocks)
+        if levels > 1:
+            want += ((int(self.temporal_pyr_layout(Ho, Wo, levels).pyr_bytes),),)
+        want += (blocks,)
+        for name, slot in (("state", state), ("prev", prev)):
+            if slot is not None and (len(slot) != len(want) or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
+                raise L.FaststyleError("temporal_f32: %s is not the slot of a %dx%d output with %d levels and subpel %d (temporal_state)" %
+                                       (name, Ho, Wo, levels, subpel))
+        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
+        p8 = self.mem.ptr_u8
+        pyr = (lambda slot: p8(slot[3])) if levels > 1 else (lambda slot: None)
+        pl, po, pp = (None, None, None) if prev is None else (p8(prev[0]), p8(prev[1]), pyr(prev))
+        L.check(self.lib, self.lib.fs_temporal_sub_f32(self.ctx, self.mem.ptr(src), ss[0], ss[1], self.mem.ptr(cur), Ho, Wo, int(strength_q8),
+                                                       int(sensitivity), int(radius), int(levels), int(subpel), int(matrix),
+                                                       1 if src_bgr else 0, pl, po, pp, p8(state[0]), p8(state[1]), pyr(state), p8(state[2]),
+                                                       p8(state[-1]), self.mem.ptr(dst)), "fs_temporal_sub_f32")
         return dst
 
     def synth_uniform(self, out, seed, rank, batch_index):

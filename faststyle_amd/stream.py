@@ -56,6 +56,10 @@ occurs.  ``reset()`` forgets the previous frame.  Without ``temporal=`` nothing 
 ``levels`` in [1, 3] (default 1) searches coarse to fine over that many halved lumas (fs_temporal_pyr_f32): vectors up to ``radius`` (2^levels
 - 1) pixels, found reliably up to about ``radius`` 2^(levels - 1); each slot then has a fourth buffer, the halved lumas and the coarse vectors,
 and the tail has one launch more for the pyramid and one search launch per level.  With ``levels=1`` or without the key nothing changes.
+``subpel`` in [0, 2] (default 0) gives the block vectors in whole, half or quarter pixels (fs_temporal_sub_f32): a fraction per block fitted
+through the winner's SAD and its four neighbours, and a bilinear fetch of the previous luma and output, so that a slow pan keeps its
+confidence; each slot then has a last buffer more, the fractions, and the tail one launch more.  ``motion_vectors_subpel()`` returns 4 mv + mvf.
+With ``subpel=0`` or without the key nothing changes.
 
 Delivery at another size: with ``deliver=dict(height=, width=, filter='bicubic')`` one launch ahead of the output conversions (fs_resample_f32,
 csrc/fs_resample.hip) resamples the top-left H x W of the tensor they would read -- the net's output, the composed or the stabilised tensor --
@@ -256,7 +260,7 @@ class FrameStylizer(object):
             raise L.FaststyleError("deliver guided= needs a source that is resized to the net's size (interpolation=, or resample= for 9 to 16 bits)")
         self._guided_work = self.eng.guided_workspace(H, W, B)
 
-    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels")
+    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels", "subpel")
 
     def _temporal_setup(self, opt, slots):
         """The temporal stage's fixed parts: the quantised strength, the checked parameters, the state slots and the stabilised tensor."""
@@ -284,8 +288,13 @@ class FrameStylizer(object):
         levels = int(number("levels", 1, 1, 3, True))
         if levels > 1:                                       # (a lane of one level keeps the dict, the slots and the launches it always had)
             self.temporal["levels"] = levels
+        subpel = int(number("subpel", 0, 0, 2, True))
+        if subpel > 0:                                       # (likewise: without the key, or with 0, nothing changes)
+            self.temporal["subpel"] = subpel
         Ho, Wo = self.out_shape[1:3]
-        self._tslots = slots if slots is not None else [self.eng.temporal_state(Ho, Wo, levels) for _ in range(2)]
+        if slots is None:
+            slots = [self.eng.temporal_state(Ho, Wo, levels, subpel) if subpel > 0 else self.eng.temporal_state(Ho, Wo, levels) for _ in range(2)]
+        self._tslots = slots
         self._stab = self.eng.mem.empty(self.out_shape)
 
     COMPOSE_KEYS = ("strength", "keep_color", "matrix", "mask", "source_swapped")
@@ -542,7 +551,7 @@ class FrameStylizer(object):
         t = self.temporal
         self.eng.temporal_f32(self._in_f32, self._cur, self._stab, self._tslots[n & 1], prev=None if n == 0 else self._tslots[(n - 1) & 1],
                               strength_q8=t["strength_q8"], sensitivity=t["sensitivity"], radius=t["radius"], matrix=t["matrix"],
-                              src_bgr=t["source_bgr"], levels=t.get("levels", 1))
+                              src_bgr=t["source_bgr"], levels=t.get("levels", 1), **({"subpel": t["subpel"]} if "subpel" in t else {}))
         self._outputs(self._stab)
 
     def _captured(self, launches):
@@ -675,6 +684,15 @@ class FrameStylizer(object):
         if self._tn == 0:
             raise L.FaststyleError("motion_vectors: this stylizer has not run a frame since it was built or reset")
         return np.array(self.eng.mem.to_numpy(self._tslots[(self._tn - 1) & 1][2]), dtype=np.uint8, copy=True).view(np.int8)
+
+    def motion_vectors_subpel(self):
+        """For tests and inspection: the block vectors (dy, dx) of the last pass in quarter pixels, 4 mv + mvf, host int16 [ceil(Ho / 16),
+        ceil(Wo / 16), 2] (synchronises); a stylizer built without temporal subpel= has none."""
+        if self._tslots is None or "subpel" not in self.temporal:
+            raise L.FaststyleError("motion_vectors_subpel: this stylizer was built without temporal subpel=")
+        mv = self.motion_vectors()                               # (refuses a lane that has not run a frame)
+        mvf = np.array(self.eng.mem.to_numpy(self._tslots[(self._tn - 1) & 1][-1]), dtype=np.uint8, copy=True).view(np.int8)
+        return 4 * mv.astype(np.int16) + mvf.astype(np.int16)
 
     def as_planes(self, a):
         """A frame of a deep source given as 16-bit samples -> the bytes the stylizer takes (anything else: as it is)."""

@@ -503,8 +503,8 @@ int fs_temporal_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cu
  *   blend      as above, with the vectors held to R (2^L - 1) instead of R before q is clamped.
  * Reach: a vector can be as long as R (2^L - 1), but motion is reliably found only where the coarsest level sees it, about R 2^(L-1) pixels:
  * 14 at L = 2, 28 at L = 3 (at L = 3 a move by (20, -33) is mostly lost, since -33 / 4 lies outside 7).  Not provided: L above 3 (the coarsest
- * level of a small frame becomes one ragged block), sub-pixel vectors, a second zero-vector predictor per level, smoothing of the vector
- * field, batches. */
+ * level of a small frame becomes one ragged block), a second zero-vector predictor per level, smoothing of the vector field, batches
+ * (sub-pixel vectors, which stood in this list: fs_temporal_sub_f32 below). */
 
 #define FS_TEMPORAL_MAX_LEVELS 3
 
@@ -533,6 +533,49 @@ int fs_temporal_pyr_f32(fs_ctx* ctx, const float* src, int H, int W, const float
                         int radius, int levels, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
                         const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv,
                         float* dst);
+
+/* ---- Quarter-pixel block vectors for the temporal stage (csrc/fs_temporal.hip): `subpel` S in {0, 1, 2} gives vectors in whole, half or
+ * quarter pixels, so that the stage follows a slow pan instead of switching itself off on moving texture.  Luma, pyramid and the `levels`
+ * searches are those of fs_temporal_pyr_f32 and yield mv; the arithmetic below, at level 0 only, is the contract (tests/test_temporal_sub.py
+ * restates it), integer throughout.
+ *
+ *   refinement for block b with (dy, dx) = mv[b]:
+ *                SAD(u, v) = sum over the block's pixels (y, x) of |cur8[y][x] - prev8[clampy(y + u)][clampx(x + v)]| (a ragged block: its
+ *                pixels inside the frame), raw sums without the search's motion penalty.
+ *                S0 = SAD(dy, dx), Sym = SAD(dy - 1, dx), Syp = SAD(dy + 1, dx), Sxm = SAD(dy, dx - 1), Sxp = SAD(dy, dx + 1)
+ *                fit(m, p): E = max(m, p) - S0; 0 if E <= 0; otherwise g = floor((2^S (m - p) + E) / (2 E)) (a true floor, also of a
+ *                negative numerator), held to [-2^(S-1), 2^(S-1)]; the result is g 2^(2-S), in quarter pixels.
+ *                mvf[b] = (fit(Sym, Syp), fit(Sxm, Sxp)), two signed char in [-2, 2]; at S = 1 each is in {-2, 0, 2}.
+ *              It is the equiangular line fit through the winner and its two neighbours per axis.  Without a previous frame, with R = 0 or
+ *              with S = 0 every mvf is (0, 0); with S = 0 mvf is not written and may be null.  mv keeps its meaning: the block's vector in
+ *              quarter pixels is 4 mv + mvf.  A flat block has E = 0 and stays whole.  A neighbour one pixel beyond the search bound is a
+ *              clamped read like any other, and nothing is stored from it.
+ *   blend      pixel p = (y, x) of block b; dy, dx held to R (2^L - 1) and fy, fx to [-2, 2]:
+ *                Y4 = 4 (y + dy) + fy; y0 = Y4 >> 2 (arithmetic); ay = Y4 & 3; r0 = clampy(y0), r1 = clampy(y0 + 1)
+ *                X4 = 4 (x + dx) + fx; x0 = X4 >> 2; ax = X4 & 3; c0 = clampx(x0), c1 = clampx(x0 + 1)
+ *                bil(a, b, c, d) = ((4 - ay) ((4 - ax) a + ax b) + ay ((4 - ax) c + ax d) + 8) >> 4
+ *                pq  = bil(prev8[r0][c0], prev8[r0][c1], prev8[r1][c0], prev8[r1][c1])
+ *                P_c = bil of the four u16 prev88[..][..][c]
+ *              and then as fs_temporal_f32's blend: e = |cur8[p] - pq|, conf, w, F_c = B_c + (((int64)(P_c - B_c) w + 32768) >> 16), dst,
+ *              out88.  bil of values in [0, 65280] lies in [0, 65280]: still no clamp.
+ * Hence: where mvf[b] = (0, 0), bil returns its first argument and the block's pixels are those of fs_temporal_pyr_f32, bit for bit; S = 0
+ * is fs_temporal_pyr_f32 term for term; strength_q8 0, a first frame, or e K >= 256 everywhere still give F = to88(cur); strength_q8 256 on a
+ * still picture still returns the first frame in every block whose fraction is (0, 0).  A still block has S0 = 0 and E = max(m, p), so the
+ * fit leaves it whole exactly while the smaller neighbour sum along each axis stays above (1 - 2^-S) of the larger; an edge that lies on the
+ * block's first or last row or column, or a ragged block of few rows or columns, whose clamped neighbour repeats pixels, can fall below that
+ * and is then fetched a fraction away (a ragged block of one row takes (2, 0) and fetches the same row twice: no change).  Known property:
+ * under steady fractional motion the state is resampled bilinearly on every frame, so at strength 1 and full confidence the stabilised
+ * picture softens over time; below 1 the current frame re-injects its detail.
+ * Not provided: smoothing of the vectors or the confidence, overlapped blocks, a sharper (bicubic) fetch, fractions at coarse levels, batches.
+ *
+ * mvf [nby, nbx, 2] signed char is written for inspection (the next call does not read it).  With S > 0: fs_temporal_pyr_f32's launches, one
+ * more for the refinement, and the bilinear blend in place of the whole-pixel one: 4 launches at L = 1, 6 at L = 2, 7 at L = 3.  mv is held to
+ * R (2^L - 1) and mvf to [-2, 2] before either reaches an address.  Asynchronous on the ctx stream, allocates nothing, can be captured into a
+ * hipGraph.  A refused call launches nothing.  Errors: those of fs_temporal_pyr_f32, -2 subpel outside [0, 2], -1 null mvf with subpel > 0. */
+int fs_temporal_sub_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity,
+                        int radius, int levels, int subpel, int matrix, int src_bgr, const unsigned char* prev_luma,
+                        const unsigned short* prev_out88, const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88,
+                        unsigned char* pyr, signed char* mv, signed char* mvf, float* dst);
 
 /* ---- Resampling between fp32 tensors (csrc/fs_resample.hip): the net's (or composed, or stabilised) output at a delivery size, a deep
  * source's fp32 planes at the net's size; no u8 stage on either path.  The arithmetic below is the contract: it is Pillow's Image.resize on

@@ -37,6 +37,8 @@ net's fp32 tensors, behind the stage above (faststyle_amd/stream.py, temporal=).
 With --frames_dir a change of frame size starts over.  Without the flag nothing changes; ``--temporal_strength 0`` writes the same bytes.
 ``--temporal_levels L`` (1..3, default 1) searches coarse to fine over L halved lumas for fast motion: vectors up to R (2^L - 1) pixels, found
 reliably up to about R 2^(L-1) -- 14 at L = 2, 28 at L = 3 --, for one more launch and one more search launch per level.
+``--temporal_subpel S`` (0..2, default 0) gives the vectors in whole, half or quarter pixels for slow motion -- a pan, a drifting handheld shot,
+a zoom --: a fraction per block and a bilinear fetch of the previous frame, for one more launch; it combines with ``--temporal_levels``.
 
 Deliver at any size: ``--output_size W H`` (or ``--output_size source``: the stream's or the first frame's own size) resamples every result
 from the net's size to that size on the device -- Pillow's mode-F arithmetic on the net's fp32 output (or the blended / stabilised tensor),
@@ -95,17 +97,22 @@ def compose_options(args, matrix='bt601'):
 
 
 def temporal_options(args, matrix='bt601'):
-    """--temporal_strength / --temporal_radius / --temporal_sensitivity / --temporal_levels -> the temporal= dict of the lanes
-    (faststyle_amd/stream.py), None without --temporal_strength; matrix: what --color_matrix defaults to.  A value outside its range, or
-    --temporal_levels without --temporal_strength, is a SystemExit here, before anything is loaded.  Every path of this script feeds the net
-    B,G,R: the stage is told so (source_bgr)."""
-    s = getattr(args, 'temporal_strength', None)                # (the four flags are absent from the namespace unless given)
+    """--temporal_strength / --temporal_radius / --temporal_sensitivity / --temporal_levels / --temporal_subpel -> the temporal= dict of the
+    lanes (faststyle_amd/stream.py), None without --temporal_strength; matrix: what --color_matrix defaults to.  A value outside its range, or
+    --temporal_levels or --temporal_subpel without --temporal_strength, is a SystemExit here, before anything is loaded.  Every path of this
+    script feeds the net B,G,R: the stage is told so (source_bgr)."""
+    s = getattr(args, 'temporal_strength', None)                # (the five flags are absent from the namespace unless given)
     radius, sensitivity = getattr(args, 'temporal_radius', 7), getattr(args, 'temporal_sensitivity', 16)
     levels = getattr(args, 'temporal_levels', None)
     if levels is not None and not 1 <= levels <= 3:
         raise SystemExit('--temporal_levels %d is outside [1, 3]' % levels)
     if levels is not None and s is None:
         raise SystemExit('--temporal_levels needs --temporal_strength')
+    subpel = getattr(args, 'temporal_subpel', None)
+    if subpel is not None and not 0 <= subpel <= 2:
+        raise SystemExit('--temporal_subpel %d is outside [0, 2]' % subpel)
+    if subpel is not None and s is None:
+        raise SystemExit('--temporal_subpel needs --temporal_strength')
     if not 0 <= radius <= 7:
         raise SystemExit('--temporal_radius %d is outside [0, 7]' % radius)
     if not 1 <= sensitivity <= 256:
@@ -115,7 +122,9 @@ def temporal_options(args, matrix='bt601'):
     if not 0.0 <= s <= 1.0:
         raise SystemExit('--temporal_strength %r is outside [0, 1]' % s)
     opt = dict(strength=s, sensitivity=sensitivity, radius=radius, matrix=args.color_matrix or matrix, source_bgr=True)
-    return opt if levels is None else dict(opt, levels=levels)
+    if levels is not None:
+        opt = dict(opt, levels=levels)
+    return opt if subpel is None else dict(opt, subpel=subpel)
 
 
 def delivery_options(args):

@@ -25,6 +25,11 @@ those graphs alone: under a kernel trace that run gives the time of each of the 
 --temporal_strength 0.6 alone and with --temporal_levels 3, plus the device time of one 720p call of the stage at one level (fs_temporal_f32), two and
 three levels (fs_temporal_pyr_f32: the pyramid launch and one search launch per level more) on a frame moved by (20, -12), the graph-of-200 scheme;
 written to profiles/video_temporal_pyr.json.  "temporal_pyr_kernels" as the third argument runs those graphs alone.
+"video" with "temporal_subpel" as the fifth argument (pipe_bench.py 1280 4 video profiles/video_temporal_subpel.json temporal_subpel): the two legs
+are --temporal_strength 0.6 alone and with --temporal_subpel 2, plus the device time of one 720p call of the stage at radius 7 on a frame moved by
+(2, -1) quarter pixels: subpel 0 (fs_temporal_f32, the path without the key), 1 and 2 at one level and subpel 2 at three levels (fs_temporal_sub_f32:
+the refinement launch more, the bilinear blend), the graph-of-200 scheme; written to profiles/video_temporal_subpel.json.
+"temporal_subpel_kernels" as the third argument runs those graphs alone.
 "resample" (pipe_bench.py 96 4 resample): the fp32 resampler.  The kernel alone (the graph-of-200 scheme, data resident): 720 x 1280 -> 2160 x 3840
 bicubic and lanczos, 2160 x 3840 -> 720 x 1280 bicubic; and the raw-video loop over a 2160p 4:2:0 file with --frame_size 1280 720, without and
 with --output_size source, as two legs that alternate in the one run (rates from the difference between n and n / 4 frames); written to
@@ -219,6 +224,42 @@ def temporal_pyr_kernel_times(W=1280, H=720, launches=200):
     return res
 
 
+def temporal_subpel_kernel_times(W=1280, H=720, launches=200):
+    """-> dict of device microseconds per 720p call of the temporal stage by (levels, subpel), timed as kernel_times does: a smooth frame moved
+    by (2, -1) quarter pixels (bilinearly) against its predecessor at radius 7 -- subpel 0 at one level is fs_temporal_f32's three launches,
+    the others are fs_temporal_sub_f32's -- and the share of interior blocks whose vector 4 mv + mvf is within one quarter unit of the move."""
+    eng = engine.Engine()
+    mem = eng.mem
+    rng = np.random.default_rng(3)
+    small = rng.uniform(0, 255, (H // 8, W // 8, 3)).astype(np.float32)
+    a = np.kron(small, np.ones((8, 8, 1), np.float32))
+    for axis in (0, 1):                                           # (smooth: the blocks of 8 x 8 under a box of 9)
+        a = sum(np.roll(a, k, axis=axis) for k in range(-4, 5)) / np.float32(9)
+    half = (a + np.roll(a, -1, axis=0)) * np.float32(0.5)         # moved[y][x] = a[y + 1/2][x - 1/4]
+    moved = half * np.float32(0.75) + np.roll(half, 1, axis=1) * np.float32(0.25)
+    noise = lambda: rng.uniform(-1, 1, (H, W, 3)).astype(np.float32)
+    src0, src1 = mem.from_numpy(np.ascontiguousarray(a + noise())[None]), mem.from_numpy(np.ascontiguousarray(moved + noise())[None])
+    cur = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    dst = mem.empty((1, H, W, 3))
+    kw = dict(strength_q8=154, sensitivity=16, src_bgr=True, radius=7)
+    res = {}
+    for levels, subpel in ((1, 0), (1, 1), (1, 2), (3, 2)):
+        more = dict(levels=levels, subpel=subpel) if subpel else dict(levels=levels)      # (subpel 0: the call of a lane without the key)
+        s0, s1 = (eng.temporal_state(H, W, **more) for _ in range(2))
+        eng.temporal_f32(src0, cur, dst, s0, **more, **kw)                            # the previous frame's state
+        us = kernel_timed(lambda: eng.temporal_f32(src1, cur, dst, s1, prev=s0, **more, **kw), launches)
+        q = 4 * np.array(mem.to_numpy(s1[2]), dtype=np.uint8, copy=True).view(np.int8).astype(np.int16)
+        if subpel:
+            q = q + np.array(mem.to_numpy(s1[-1]), dtype=np.uint8, copy=True).view(np.int8)
+        q = q[1:-1, 1:-1]
+        found = float(np.mean((np.abs(q[..., 0] - 2) <= 1) & (np.abs(q[..., 1] + 1) <= 1)))
+        launches_per_call = (3 if levels == 1 else 3 + levels) + (1 if subpel else 0)
+        res["temporal_levels_%d_subpel_%d" % (levels, subpel)] = {"us": us, "launches": launches_per_call, "interior_blocks_within_a_quarter_of_2_-1": found}
+        print("video: %8.1f us per 720p call, %3.0f %% of the interior blocks within a quarter of (2, -1): %d level(s), subpel %d" %
+              (us, 100 * found, levels, subpel))
+    return res
+
+
 def resample_kernel_times(launches=200):
     """-> dict of device microseconds per call of fs_resample_f32, timed as kernel_times does, with the bytes each call reads and writes."""
     eng = engine.Engine()
@@ -338,11 +379,11 @@ def resample(n, repeats=3, out_json=None, legs=None, kernels=None, tag="resample
     return res
 
 
-def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False, temporal=False, temporal_levels=False):
+def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False, temporal=False, temporal_levels=False, temporal_subpel=False):
     """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json (video: with the raw-video leg, to
     profiles/video_stream.json; video with a depth: the 8-bit and the deep raw-video legs alone, to profiles/video_deep.json; video with
     compose / temporal: the 8-bit raw-video leg without and with that stage, to profiles/video_compose.json / video_temporal.json)."""
-    compose_flag, compose = compose, compose or temporal or temporal_levels          # (the stages share the two-leg scheme)
+    compose_flag, compose = compose, compose or temporal or temporal_levels or temporal_subpel      # (the stages share the two-leg scheme)
     import contextlib
     import json
     import shutil
@@ -408,6 +449,9 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=Fals
     if temporal_levels:
         legs = [("video_y4m_720p_temporal_strength_0.6", "720p", ("--temporal_strength", "0.6")),
                 ("video_y4m_720p_temporal_strength_0.6_levels_3", "720p", ("--temporal_strength", "0.6", "--temporal_levels", "3"))]
+    if temporal_subpel:
+        legs = [("video_y4m_720p_temporal_strength_0.6", "720p", ("--temporal_strength", "0.6")),
+                ("video_y4m_720p_temporal_strength_0.6_subpel_2", "720p", ("--temporal_strength", "0.6", "--temporal_subpel", "2"))]
     parser = stylize_webcam.setup_parser()
     out = os.path.join(d, "out")
 
@@ -475,7 +519,9 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=Fals
         res["kernel_us_per_720p_call_of_three_launches"] = temporal_kernel_times()
     if temporal_levels:
         res["kernel_us_per_720p_call_by_levels"] = temporal_pyr_kernel_times()
-    dst = out_json or os.path.join(root, "profiles", "video_temporal_pyr.json" if temporal_levels else "video_temporal.json" if temporal else "video_compose.json" if compose else "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
+    if temporal_subpel:
+        res["kernel_us_per_720p_call_by_levels_and_subpel"] = temporal_subpel_kernel_times()
+    dst = out_json or os.path.join(root, "profiles", "video_temporal_subpel.json" if temporal_subpel else "video_temporal_pyr.json" if temporal_levels else "video_temporal.json" if temporal else "video_compose.json" if compose else "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
     with open(dst, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
@@ -489,8 +535,12 @@ def main():
     if len(sys.argv) > 3 and sys.argv[3] in ("frames_in", "video"):
         fifth = sys.argv[5] if len(sys.argv) > 5 and sys.argv[3] == "video" else None
         frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video",
-                  depth=int(fifth) if fifth not in (None, "compose", "temporal", "temporal_levels") else None, compose=fifth == "compose",
-                  temporal=fifth == "temporal", temporal_levels=fifth == "temporal_levels")
+                  depth=int(fifth) if fifth not in (None, "compose", "temporal", "temporal_levels", "temporal_subpel") else None,
+                  compose=fifth == "compose", temporal=fifth == "temporal", temporal_levels=fifth == "temporal_levels",
+                  temporal_subpel=fifth == "temporal_subpel")
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "temporal_subpel_kernels":
+        temporal_subpel_kernel_times()
         return
     if len(sys.argv) > 3 and sys.argv[3] == "temporal_pyr_kernels":
         temporal_pyr_kernel_times()
