@@ -224,6 +224,9 @@ PROTOTYPES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fs_temporal_sub_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # fs_temporal_sub_f32's arguments with int overlap after subpel
+    "fs_temporal_obmc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fs_resample_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_resample_info)]),
     "fs_resample_tables": (c_int, [POINTER(fs_resample_info), c_void_p, c_size_t]),
     "fs_resample_f32": (c_int, [c_void_p, POINTER(fs_resample_info), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -124,6 +124,10 @@ def stylize_webcam_parser():
         ('--temporal_subpel', dict(default=argparse.SUPPRESS, type=int, metavar='S',
                                    help="(addition) motion vectors in whole (0, the default), half (1) or quarter pixels (2): slow motion keeps "
                                         "its match, for one more launch and a bilinear fetch; needs --temporal_strength")),
+        ('--temporal_overlap', dict(default=argparse.SUPPRESS, type=int, metavar='O',
+                                    help="(addition) 1: blend every pixel along the vectors of the four blocks around it, weighted by a window and "
+                                         "by how well each matched, so that motion edges inside a block keep their match; 0 (the default): whole "
+                                         "blocks; needs --temporal_strength")),
         ('--temporal_sensitivity', dict(default=argparse.SUPPRESS, type=int, metavar='K',
                                         help="(addition) how fast a source mismatch turns the blend off, 1..256: none of it is left at a luma "
                                              "difference of 256 / K (default 16)")),

@@ -710,6 +710,12 @@ int temporal_pyr_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H,
 int temporal_sub_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
                      int subpel, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
                      unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf, float* dst, hipStream_t s);
+// ... with overlapped block vectors (overlap 1): the same launches with the blend replaced by the one that weighs the vectors of the four
+// blocks around every pixel; overlap 0 is temporal_sub_f32
+int temporal_obmc_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
+                      int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
+                      const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf,
+                      float* dst, hipStream_t s);
 // resampling between fp32 tensors (fs_resample.hip): whether a plan is what fs_resample_plan fills, and the one launch (argument checks are in
 // fs_api.hip)
 bool resample_plan_ok(const ::fs_resample_info& plan);

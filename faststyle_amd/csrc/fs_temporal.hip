@@ -639,6 +639,229 @@ int temporal_sub_f32(const fs_temporal_pyr_info& lay, const float* src, int H, i
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+// ---- overlapped block vectors (fs_temporal_obmc_f32): every pixel weighs the vectors of the four blocks whose centres surround it
+//   blend  -- the blends' threads: four pixels of an output row.  They share their four blocks (the block row changes between rows y = 16 b + 7
+//             and 16 b + 8, the block column between x = 16 b + 7 and 16 b + 8, a multiple of 4), so the four vectors are read once per thread
+//             and only the column window weight differs per pixel.  A thread whose four held quarter-pixel vectors are equal runs the body of
+//             temporal_blend_sub_kernel on that vector: one fetch per pixel, no division (Pbar = P and cbar = conf there).  The others fetch
+//             along the four vectors, sum in 64 bits and divide once per channel.  Waves diverge only along motion edges.
+namespace {
+
+// the rows, columns and weights of temporal_blend_sub_kernel's fetch for a thread's four pixels displaced by (qy, qx) quarter pixels
+struct Tap {
+    size_t r0, r1;
+    int col[5];
+    int ay, ax;
+};
+
+__device__ __forceinline__ Tap make_tap(const BlendArgs& A, int y, int x0, int qy, int qx) {
+    Tap t;
+    const int Y4 = 4 * y + qy, X4 = 4 * x0 + qx;
+    t.ay = Y4 & 3; t.ax = X4 & 3;
+    t.r0 = (size_t)clampi(Y4 >> 2, A.Ho - 1) * A.Wo;
+    t.r1 = (size_t)clampi((Y4 >> 2) + 1, A.Ho - 1) * A.Wo;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) t.col[j] = clampi((X4 >> 2) + j, A.Wo - 1);
+    return t;
+}
+
+// pixel k of the thread: the previous luma and output at the tap, bilinear; a weight of zero stands before whatever is not fetched
+__device__ __forceinline__ void tap_fetch(const Tap& t, int k, const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88, int& pq,
+                                          int P[3]) {
+    const size_t q00 = t.r0 + t.col[k], q01 = t.r0 + t.col[k + 1], q10 = t.r1 + t.col[k], q11 = t.r1 + t.col[k + 1];
+    pq = (int)prev8[q00];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) P[c] = prev88[q00 * 3 + c];
+    if (t.ay | t.ax) {
+        const int wy0 = 4 - t.ay, wx0 = 4 - t.ax;
+        int l01 = 0, l10 = 0, l11 = 0, p01[3] = {0, 0, 0}, p10[3] = {0, 0, 0}, p11[3] = {0, 0, 0};
+        if (t.ax) {
+            l01 = prev8[q01];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) p01[c] = prev88[q01 * 3 + c];
+        }
+        if (t.ay) {
+            l10 = prev8[q10];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) p10[c] = prev88[q10 * 3 + c];
+            if (t.ax) {
+                l11 = prev8[q11];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) p11[c] = prev88[q11 * 3 + c];
+            }
+        }
+        pq = (wy0 * (wx0 * pq + t.ax * l01) + t.ay * (wx0 * l10 + t.ax * l11) + 8) >> 4;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) P[c] = (wy0 * (wx0 * P[c] + t.ax * p01[c]) + t.ay * (wx0 * p10[c] + t.ax * p11[c]) + 8) >> 4;   // at most 16 x 65280 + 8
+    }
+}
+
+// floor(num / den) for num < 2^36 and 0 < den <= 2^19 with a quotient below 2^16: a float estimate (off by less than one) and an exact
+// integer fix-up, which is right whatever the estimate was
+__device__ __forceinline__ int floor_div(unsigned long long num, unsigned den) {
+    long long q = (long long)((float)num / (float)den);
+    long long r = (long long)num - q * (long long)den;
+    while (r < 0) { --q; r += den; }
+    while (r >= (long long)den) { ++q; r -= den; }
+    return (int)q;
+}
+
+// temporal_blend_sub_kernel's threads and arguments (mvf == nullptr: every fraction is zero, the whole-pixel vectors of temporal_blend_kernel),
+// nby beside A.nbx.  dst may be cur, as there.  mv and mvf are held to their bounds and the block indices clamped before any of them reaches
+// an address; nothing else read from a buffer does.
+__global__ __launch_bounds__(256) void temporal_blend_obmc_kernel(const BlendArgs A, int nby, const float* cur, const unsigned char* __restrict__ cur8,
+                                                                  const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
+                                                                  const signed char* __restrict__ mv, const signed char* __restrict__ mvf, float* dst,
+                                                                  unsigned short* __restrict__ out88) {
+    const int groups = (A.Wo + 3) >> 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)groups * A.Ho) return;
+    const int y = (int)(i / groups), x0 = (int)(i - (long long)y * groups) * 4;
+    const size_t row = (size_t)y * A.Wo;
+    int qy[4] = {0, 0, 0, 0}, qx[4] = {0, 0, 0, 0};         // the held vectors in quarter pixels of the candidates (row, column): (0, 0) (0, 1) (1, 0) (1, 1)
+    const int ty = 2 * y - 15, tx = 2 * x0 - 15;            // (tx + 2 k for pixel k: the same tx >> 5 for the four)
+    const int wy1 = ty & 31;                                // the window weight of the second block row; 32 - wy1 of the first
+    bool same = true;
+    if (prev8 != nullptr) {                                 // (uniform per launch)
+        const int j0 = ty >> 5, i0 = tx >> 5;
+        const int bj[2] = {clampi(j0, nby - 1), clampi(j0 + 1, nby - 1)}, bi[2] = {clampi(i0, A.nbx - 1), clampi(i0 + 1, A.nbx - 1)};
+        const signed char* __restrict__ fr = mvf != nullptr ? mvf : mv;                  // (no fractions: bytes that can be read, masked away below)
+        const int fmask = mvf != nullptr ? -1 : 0;          // (uniform per launch)
+        int raw[16];                                        // the sixteen loads ahead of their first use, with no branch between them: one wait
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const size_t b = ((size_t)bj[c >> 1] * A.nbx + bi[c & 1]) * 2;
+            raw[4 * c] = (int)mv[b]; raw[4 * c + 1] = (int)mv[b + 1]; raw[4 * c + 2] = (int)fr[b]; raw[4 * c + 3] = (int)fr[b + 1];
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int dy = raw[4 * c] < -A.R ? -A.R : (raw[4 * c] > A.R ? A.R : raw[4 * c]);        // (written within these bounds; held to them again)
+            const int dx = raw[4 * c + 1] < -A.R ? -A.R : (raw[4 * c + 1] > A.R ? A.R : raw[4 * c + 1]);
+            const int fy = (raw[4 * c + 2] < -2 ? -2 : (raw[4 * c + 2] > 2 ? 2 : raw[4 * c + 2])) & fmask;
+            const int fx = (raw[4 * c + 3] < -2 ? -2 : (raw[4 * c + 3] > 2 ? 2 : raw[4 * c + 3])) & fmask;
+            qy[c] = 4 * dy + fy; qx[c] = 4 * dx + fx;
+            same = same && qy[c] == qy[0] && qx[c] == qx[0];
+        }
+    }
+    const int n = A.Wo - x0 < 4 ? A.Wo - x0 : 4;
+    const size_t at0 = (row + x0) * 3;
+    float b[12];                                            // every read of cur before the first write of dst: the two may be one tensor
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int xn = k < n ? k : n - 1;                   // (beyond the row's end: the last pixel again, never stored)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b[3 * k + c] = cur[at0 + 3 * xn + c];
+    }
+    int F[12], c8[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) F[3 * k + c] = temporal_f88(b[3 * k + c]);
+        c8[k] = prev8 != nullptr ? (int)cur8[row + x0 + (k < n ? k : n - 1)] : 0;
+    }
+    if (prev8 != nullptr && same) {                         // the four vectors agree: the whole-block blend along that vector
+        const Tap t = make_tap(A, y, x0, qy[0], qx[0]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int pq, P[3];
+            tap_fetch(t, k, prev8, prev88, pq, P);          // (beyond the row's end: whatever lies there, clamped; never stored)
+            const int d = c8[k] - pq;
+            const int e = d < 0 ? -d : d;
+            const int conf = 256 - e * A.sensitivity;
+            const long long w = (long long)A.strength_q8 * (conf > 0 ? conf : 0);        // 0 ... 65536
+#pragma unroll
+            for (int c = 0; c < 3; ++c) F[3 * k + c] += (int)(((long long)(P[c] - F[3 * k + c]) * w + 32768) >> 16);
+        }
+    } else if (prev8 != nullptr) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {                       // pixel by pixel: the sums of one pixel are live at a time
+            unsigned D = 0;                                 // at most 2^18
+            unsigned long long N[3] = {0, 0, 0};            // below 2^34
+            int cmax = 0;
+            const int wx1 = (tx + 2 * k) & 31;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const Tap t = make_tap(A, y, x0 + k, qy[c], qx[c]);
+                int pq, P[3];
+                tap_fetch(t, 0, prev8, prev88, pq, P);      // (beyond the row's end: whatever lies there, clamped; never stored)
+                const int d = c8[k] - pq;
+                const int e = d < 0 ? -d : d;
+                int conf = 256 - e * A.sensitivity;
+                conf = conf > 0 ? conf : 0;
+                const unsigned wc = (unsigned)(((c >> 1) ? wy1 : 32 - wy1) * ((c & 1) ? wx1 : 32 - wx1) * conf);
+                D += wc;
+                cmax = conf > cmax ? conf : cmax;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) N[ch] += (unsigned long long)wc * (unsigned)P[ch];
+            }
+            if (D == 0) continue;                           // F = B
+            const int cbar = cmax < (int)(D >> 8) ? cmax : (int)(D >> 8);
+            const long long w = (long long)A.strength_q8 * cbar;                         // 0 ... 65536
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const int Pbar = floor_div(2 * N[ch] + D, 2 * D);                        // the rounded weighted mean, 0 ... 65280
+                F[3 * k + ch] += (int)(((long long)(Pbar - F[3 * k + ch]) * w + 32768) >> 16);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < n) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                dst[at0 + 3 * k + c] = (float)F[3 * k + c] * 0.00390625f;
+                out88[at0 + 3 * k + c] = (unsigned short)F[3 * k + c];
+            }
+        }
+}
+
+}  // namespace
+
+// arguments: checked by the caller (fs_api.hip: fs_temporal_obmc_f32).  overlap 0 is temporal_sub_f32; with 1 its launches with the blend
+// replaced by temporal_blend_obmc_kernel (mvf null with subpel 0: no refinement launch, whole-pixel vectors).
+int temporal_obmc_f32(const fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
+                      int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
+                      const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf,
+                      float* dst, hipStream_t s) {
+    if (overlap == 0)
+        return temporal_sub_f32(lay, src, H, W, cur, strength_q8, sensitivity, radius, subpel, matrix, src_bgr, prev_luma, prev_out88, prev_pyr, luma, out88,
+                                pyr, mv, mvf, dst, s);
+    const int L = lay.levels, Ho = lay.h[0], Wo = lay.w[0];
+    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
+    LumaArgs LA;
+    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
+    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
+    const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
+    const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
+    hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, src, luma);
+    if (L > 1) {
+        PyrArgs PA;
+        PA.H0 = Ho; PA.W0 = Wo; PA.H1 = lay.h[1]; PA.W1 = lay.w[1];
+        PA.H2 = L > 2 ? lay.h[2] : 0; PA.W2 = L > 2 ? lay.w[2] : 0;
+        const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);
+        hipLaunchKernelGGL(temporal_pyramid_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks), block, 0, s, PA, (const unsigned char*)luma,
+                           pyr + lay.luma_offset[1], L > 2 ? pyr + lay.luma_offset[2] : nullptr);
+    }
+    for (int l = L - 1; l >= 0; --l) {                      // coarsest first, as in temporal_pyr_f32
+        const unsigned char* c = l ? pyr + lay.luma_offset[l] : luma;
+        const unsigned char* p = prev_luma == nullptr ? nullptr : (l ? prev_pyr + lay.luma_offset[l] : prev_luma);
+        const signed char* parent = l == L - 1 ? nullptr : (const signed char*)(pyr + lay.mv_offset[l + 1]);
+        signed char* v = l ? (signed char*)(pyr + lay.mv_offset[l]) : mv;
+        hipLaunchKernelGGL(temporal_search_pred_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l]), block, 0, s, c, p, lay.h[l], lay.w[l], radius,
+                           parent, l == L - 1 ? 0 : lay.nbx[l + 1], 2 * radius * ((1 << (L - 1 - l)) - 1), v);
+    }
+    const int hold = radius * ((1 << L) - 1);
+    if (subpel > 0)
+        hipLaunchKernelGGL(temporal_subpel_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0]), block, 0, s, (const unsigned char*)luma, prev_luma, Ho,
+                           Wo, radius, hold, subpel, (const signed char*)mv, mvf);
+    BlendArgs BA;
+    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = lay.nbx[0];
+    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = hold;
+    hipLaunchKernelGGL(temporal_blend_obmc_kernel, egrid, block, 0, s, BA, lay.nby[0], cur, (const unsigned char*)luma, prev_luma, prev_out88,
+                       (const signed char*)mv, subpel > 0 ? (const signed char*)mvf : nullptr, dst, out88);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 }  // namespace fs
 
 extern "C" {

@@ -1100,14 +1100,17 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
         return lumas, vectors
 
     def temporal_f32(self, src, cur, dst, state, prev=None, strength_q8=256, sensitivity=16, radius=7, matrix="bt601", src_bgr=False, levels=1,
-                     subpel=0):
+                     subpel=0, overlap=0):
         """fs_temporal_f32: src device float32 [H,W,3] (the net's input), cur and dst device float32 [Ho,Wo,3] (the tensor the output
         conversions would read and the stabilised one; dst may be cur; a leading axis of 1 is taken), state the slot written (temporal_state's
         triple), prev the slot the previous frame wrote (None: no previous frame) -> dst = cur blended towards prev's output along the
         block vectors found between the two lumas; matrix 'bt601' / 'bt709' or 0 / 1, src_bgr: channel 0 of src is blue.  levels > 1:
         fs_temporal_pyr_f32, the coarse-to-fine search, on slots of temporal_state(Ho, Wo, levels).  subpel 1 / 2: fs_temporal_sub_f32, vectors
-        in half / quarter pixels and a bilinear fetch, on slots of temporal_state(Ho, Wo, levels, subpel)."""
+        in half / quarter pixels and a bilinear fetch, on slots of temporal_state(Ho, Wo, levels, subpel).  overlap 1: fs_temporal_obmc_f32,
+        every pixel blended along the vectors of the four blocks around it, on the slots that (levels, subpel) take without it."""
         self._sync_stream()
+        if overlap != 0:
+            return self._temporal_obmc_f32(src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel, overlap)
         if subpel != 0:
             return self._temporal_sub_f32(src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel)
         if levels != 1:
@@ -1190,6 +1193,39 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
                                                        int(sensitivity), int(radius), int(levels), int(subpel), int(matrix),
                                                        1 if src_bgr else 0, pl, po, pp, p8(state[0]), p8(state[1]), pyr(state), p8(state[2]),
                                                        p8(state[-1]), self.mem.ptr(dst)), "fs_temporal_sub_f32")
+        return dst
+
+    def _temporal_obmc_f32(self, src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel, overlap):
+        """temporal_f32 with overlap > 0: the shape checks with the slot held against (levels, subpel) as without it -- the pyramid buffer
+        fourth when levels > 1, mvf last when subpel > 0 --, then fs_temporal_obmc_f32."""
+        self._temporal_sub_check(levels, subpel)
+        if isinstance(overlap, bool) or not isinstance(overlap, (int, np.integer)) or not 0 <= overlap <= 1:
+            raise L.FaststyleError("temporal_f32: overlap must be a whole number in [0, 1], got %r" % (overlap,))
+        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
+        if len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,):
+            ss, cs, ds = ss[1:], cs[1:], ds[1:]
+        if len(ss) != 3 or len(cs) != 3 or ss[2] != 3 or cs[2] != 3 or ds != cs:
+            raise L.FaststyleError("temporal_f32: source %s / current %s / destination %s do not belong together (one image per call)" %
+                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
+        Ho, Wo = cs[:2]
+        blocks = ((Ho + 15) // 16, (Wo + 15) // 16, 2)
+        want = ((Ho, Wo), (Ho, Wo, 3, 2), blocks)
+        if levels > 1:
+            want += ((int(self.temporal_pyr_layout(Ho, Wo, levels).pyr_bytes),),)
+        if subpel > 0:
+            want += (blocks,)
+        for name, slot in (("state", state), ("prev", prev)):
+            if slot is not None and (len(slot) != len(want) or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
+                raise L.FaststyleError("temporal_f32: %s is not the slot of a %dx%d output with %d levels and subpel %d (temporal_state)" %
+                                       (name, Ho, Wo, levels, subpel))
+        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
+        p8 = self.mem.ptr_u8
+        pyr = (lambda slot: p8(slot[3])) if levels > 1 else (lambda slot: None)
+        pl, po, pp = (None, None, None) if prev is None else (p8(prev[0]), p8(prev[1]), pyr(prev))
+        L.check(self.lib, self.lib.fs_temporal_obmc_f32(self.ctx, self.mem.ptr(src), ss[0], ss[1], self.mem.ptr(cur), Ho, Wo, int(strength_q8),
+                                                        int(sensitivity), int(radius), int(levels), int(subpel), int(overlap), int(matrix),
+                                                        1 if src_bgr else 0, pl, po, pp, p8(state[0]), p8(state[1]), pyr(state), p8(state[2]),
+                                                        p8(state[-1]) if subpel > 0 else None, self.mem.ptr(dst)), "fs_temporal_obmc_f32")
         return dst
 
     def synth_uniform(self, out, seed, rank, batch_index):

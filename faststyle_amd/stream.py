@@ -60,6 +60,10 @@ and the tail has one launch more for the pyramid and one search launch per level
 through the winner's SAD and its four neighbours, and a bilinear fetch of the previous luma and output, so that a slow pan keeps its
 confidence; each slot then has a last buffer more, the fractions, and the tail one launch more.  ``motion_vectors_subpel()`` returns 4 mv + mvf.
 With ``subpel=0`` or without the key nothing changes.
+``overlap`` in [0, 1] (default 0): with 1 every pixel is blended along the vectors of the four blocks whose centres surround it, weighted by
+a bilinear window and by how well the source matched along each (fs_temporal_obmc_f32), so that a block that straddles a motion edge keeps
+its weight on both sides; the slots and the number of launches are those of ``levels`` and ``subpel``.  With ``overlap=0`` or without the key
+nothing changes.
 
 Delivery at another size: with ``deliver=dict(height=, width=, filter='bicubic')`` one launch ahead of the output conversions (fs_resample_f32,
 csrc/fs_resample.hip) resamples the top-left H x W of the tensor they would read -- the net's output, the composed or the stabilised tensor --
@@ -260,7 +264,7 @@ class FrameStylizer(object):
             raise L.FaststyleError("deliver guided= needs a source that is resized to the net's size (interpolation=, or resample= for 9 to 16 bits)")
         self._guided_work = self.eng.guided_workspace(H, W, B)
 
-    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels", "subpel")
+    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels", "subpel", "overlap")
 
     def _temporal_setup(self, opt, slots):
         """The temporal stage's fixed parts: the quantised strength, the checked parameters, the state slots and the stabilised tensor."""
@@ -291,6 +295,9 @@ class FrameStylizer(object):
         subpel = int(number("subpel", 0, 0, 2, True))
         if subpel > 0:                                       # (likewise: without the key, or with 0, nothing changes)
             self.temporal["subpel"] = subpel
+        overlap = int(number("overlap", 0, 0, 1, True))
+        if overlap > 0:                                      # (likewise; the slots are those of (levels, subpel))
+            self.temporal["overlap"] = overlap
         Ho, Wo = self.out_shape[1:3]
         if slots is None:
             slots = [self.eng.temporal_state(Ho, Wo, levels, subpel) if subpel > 0 else self.eng.temporal_state(Ho, Wo, levels) for _ in range(2)]
@@ -551,7 +558,7 @@ class FrameStylizer(object):
         t = self.temporal
         self.eng.temporal_f32(self._in_f32, self._cur, self._stab, self._tslots[n & 1], prev=None if n == 0 else self._tslots[(n - 1) & 1],
                               strength_q8=t["strength_q8"], sensitivity=t["sensitivity"], radius=t["radius"], matrix=t["matrix"],
-                              src_bgr=t["source_bgr"], levels=t.get("levels", 1), **({"subpel": t["subpel"]} if "subpel" in t else {}))
+                              src_bgr=t["source_bgr"], levels=t.get("levels", 1), **{k: t[k] for k in ("subpel", "overlap") if k in t})
         self._outputs(self._stab)
 
     def _captured(self, launches):

@@ -566,7 +566,8 @@ int fs_temporal_pyr_f32(fs_ctx* ctx, const float* src, int H, int W, const float
  * and is then fetched a fraction away (a ragged block of one row takes (2, 0) and fetches the same row twice: no change).  Known property:
  * under steady fractional motion the state is resampled bilinearly on every frame, so at strength 1 and full confidence the stabilised
  * picture softens over time; below 1 the current frame re-injects its detail.
- * Not provided: smoothing of the vectors or the confidence, overlapped blocks, a sharper (bicubic) fetch, fractions at coarse levels, batches.
+ * Not provided: smoothing of the vectors, a sharper (bicubic) fetch, fractions at coarse levels, batches (overlapped blocks and the smoothed
+ * confidence, which stood in this list: fs_temporal_obmc_f32 below).
  *
  * mvf [nby, nbx, 2] signed char is written for inspection (the next call does not read it).  With S > 0: fs_temporal_pyr_f32's launches, one
  * more for the refinement, and the bilinear blend in place of the whole-pixel one: 4 launches at L = 1, 6 at L = 2, 7 at L = 3.  mv is held to
@@ -576,6 +577,51 @@ int fs_temporal_sub_f32(fs_ctx* ctx, const float* src, int H, int W, const float
                         int radius, int levels, int subpel, int matrix, int src_bgr, const unsigned char* prev_luma,
                         const unsigned short* prev_out88, const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88,
                         unsigned char* pyr, signed char* mv, signed char* mvf, float* dst);
+
+/* ---- Overlapped block vectors for the temporal stage (csrc/fs_temporal.hip): with `overlap` 1 every pixel considers the vectors of the four
+ * blocks whose centres surround it, weighs them by a bilinear window and by how well the source matched along each, and blends towards the
+ * confidence-weighted prediction, so that the pixels of a block that straddles a motion edge keep their weight on either side of it.  Luma,
+ * pyramid, the `levels` searches and (with subpel > 0) the refinement are those of fs_temporal_sub_f32 and yield mv and mvf; without subpel
+ * read mvf as 0.  The state gains no buffer.  Only the blend differs; its arithmetic below is the contract (tests/test_temporal_obmc.py
+ * restates it), integer throughout.
+ *
+ *   window     pixel (y, x): ty = 2 y - 15; j0 = ty >> 5 (arithmetic); ay = ty & 31.  The two block rows are clamp(j0, 0, nby - 1) and
+ *              clamp(j0 + 1, 0, nby - 1) with the weights 32 - ay and ay; the columns likewise from tx = 2 x - 15 with ax and nbx.  The four
+ *              candidates k have the window weight w_k = wy wx; the four sum to 1024.  Block centres sit at 16 b + 7.5 and the window is
+ *              symmetric about them.  A clamped index repeats the border block: a frame of one block has four equal candidates.
+ *   candidate  k with block b_k: mv[b_k] held to R (2^L - 1) and mvf[b_k] to [-2, 2]; pq_k and P_k,c are fetched exactly as the blend of
+ *              fs_temporal_sub_f32 fetches them for that vector -- bil of prev8 and prev88 at 4 (p + mv) + mvf quarter pixels, every
+ *              coordinate clamped; with subpel 0 the plain fetch of fs_temporal_f32 at the clamped q.
+ *                e_k = |cur8[p] - pq_k|;  conf_k = max(0, 256 - e_k K)
+ *   blend      D = sum w_k conf_k (at most 2^18);  N_c = sum w_k conf_k P_k,c (below 2^34);  cmax = max conf_k.
+ *              D = 0: F_c = B_c.  Otherwise
+ *                Pbar_c = (2 N_c + D) / (2 D), a floor of non-negative integers: the rounded weighted mean, between the smallest and the
+ *                         largest P_k,c and so in [0, 65280]
+ *                cbar   = min(cmax, D >> 8)
+ *                w      = strength_q8 cbar, in [0, 65536]
+ *                F_c    = B_c + (((int64)(Pbar_c - B_c) w + 32768) >> 16)
+ *              dst and out88 as fs_temporal_f32's; still no clamp.  Without a previous frame F = B.
+ * D >> 8 lets a candidate count four times its window share; a pixel's own block has w_k >= 17 x 17 = 289 > 256, so whenever its own vector
+ * matches the pixel keeps everything the whole-block blend gave it.  Hence:
+ *   1. where the four candidates' held quarter-pixel vectors 4 mv + mvf are equal, the pixel is that of fs_temporal_sub_f32 (of
+ *      fs_temporal_f32 without fractions), bit for bit: Pbar = P and cbar = conf.  Uniform motion, the inside of a moving region and a frame
+ *      of one block are such.
+ *   2. the same holds where every candidate other than the pixel's own block has conf_k = 0.
+ *   3. cbar is never below the conf of the whole-block blend for the same mv and mvf.
+ *   4. strength_q8 0, a first frame, or e_k K >= 256 for every candidate give F = to88(cur), and a conversion behind the stage writes byte
+ *      for byte what it writes without it.
+ *   5. strength_q8 256 on a still picture returns the first frame wherever the four candidates' vectors are (0, 0).
+ * Not provided: a vector median or other smoothing of mv itself, windows wider than the four nearest blocks, overlap at coarse levels or in
+ * the search, a bicubic fetch, batches.
+ *
+ * overlap 0 is fs_temporal_sub_f32 term for term (subpel 0 with a null mvf included).  overlap 1 runs the same launches with the blend
+ * replaced: 3 at L = 1, S = 0; 7 at L = 3, S = 2.  mv, mvf and the block indices are held to their bounds before any reaches an address.
+ * Asynchronous on the ctx stream, allocates nothing, can be captured into a hipGraph.  A refused call launches nothing.  Errors: those of
+ * fs_temporal_sub_f32, and -2 overlap outside [0, 1]. */
+int fs_temporal_obmc_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity,
+                         int radius, int levels, int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma,
+                         const unsigned short* prev_out88, const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88,
+                         unsigned char* pyr, signed char* mv, signed char* mvf, float* dst);
 
 /* ---- Resampling between fp32 tensors (csrc/fs_resample.hip): the net's (or composed, or stabilised) output at a delivery size, a deep
  * source's fp32 planes at the net's size; no u8 stage on either path.  The arithmetic below is the contract: it is Pillow's Image.resize on

@@ -39,6 +39,9 @@ With --frames_dir a change of frame size starts over.  Without the flag nothing 
 reliably up to about R 2^(L-1) -- 14 at L = 2, 28 at L = 3 --, for one more launch and one more search launch per level.
 ``--temporal_subpel S`` (0..2, default 0) gives the vectors in whole, half or quarter pixels for slow motion -- a pan, a drifting handheld shot,
 a zoom --: a fraction per block and a bilinear fetch of the previous frame, for one more launch; it combines with ``--temporal_levels``.
+``--temporal_overlap 1`` (0..1, default 0) blends every pixel along the vectors of the four blocks whose centres surround it, weighted by a
+bilinear window and by how well the source matched along each, so that a block that straddles a motion edge -- the outline of every moving
+subject -- keeps its match on both sides; the same launches with another blend; it combines with ``--temporal_levels`` and ``--temporal_subpel``.
 
 Deliver at any size: ``--output_size W H`` (or ``--output_size source``: the stream's or the first frame's own size) resamples every result
 from the net's size to that size on the device -- Pillow's mode-F arithmetic on the net's fp32 output (or the blended / stabilised tensor),
@@ -97,11 +100,11 @@ def compose_options(args, matrix='bt601'):
 
 
 def temporal_options(args, matrix='bt601'):
-    """--temporal_strength / --temporal_radius / --temporal_sensitivity / --temporal_levels / --temporal_subpel -> the temporal= dict of the
-    lanes (faststyle_amd/stream.py), None without --temporal_strength; matrix: what --color_matrix defaults to.  A value outside its range, or
-    --temporal_levels or --temporal_subpel without --temporal_strength, is a SystemExit here, before anything is loaded.  Every path of this
-    script feeds the net B,G,R: the stage is told so (source_bgr)."""
-    s = getattr(args, 'temporal_strength', None)                # (the five flags are absent from the namespace unless given)
+    """--temporal_strength / --temporal_radius / --temporal_sensitivity / --temporal_levels / --temporal_subpel / --temporal_overlap -> the
+    temporal= dict of the lanes (faststyle_amd/stream.py), None without --temporal_strength; matrix: what --color_matrix defaults to.  A value
+    outside its range, or --temporal_levels, --temporal_subpel or --temporal_overlap without --temporal_strength, is a SystemExit here, before
+    anything is loaded.  Every path of this script feeds the net B,G,R: the stage is told so (source_bgr)."""
+    s = getattr(args, 'temporal_strength', None)                # (the six flags are absent from the namespace unless given)
     radius, sensitivity = getattr(args, 'temporal_radius', 7), getattr(args, 'temporal_sensitivity', 16)
     levels = getattr(args, 'temporal_levels', None)
     if levels is not None and not 1 <= levels <= 3:
@@ -113,6 +116,11 @@ def temporal_options(args, matrix='bt601'):
         raise SystemExit('--temporal_subpel %d is outside [0, 2]' % subpel)
     if subpel is not None and s is None:
         raise SystemExit('--temporal_subpel needs --temporal_strength')
+    overlap = getattr(args, 'temporal_overlap', None)
+    if overlap is not None and not 0 <= overlap <= 1:
+        raise SystemExit('--temporal_overlap %d is outside [0, 1]' % overlap)
+    if overlap is not None and s is None:
+        raise SystemExit('--temporal_overlap needs --temporal_strength')
     if not 0 <= radius <= 7:
         raise SystemExit('--temporal_radius %d is outside [0, 7]' % radius)
     if not 1 <= sensitivity <= 256:
@@ -124,7 +132,9 @@ def temporal_options(args, matrix='bt601'):
     opt = dict(strength=s, sensitivity=sensitivity, radius=radius, matrix=args.color_matrix or matrix, source_bgr=True)
     if levels is not None:
         opt = dict(opt, levels=levels)
-    return opt if subpel is None else dict(opt, subpel=subpel)
+    if subpel is not None:
+        opt = dict(opt, subpel=subpel)
+    return opt if overlap is None else dict(opt, overlap=overlap)
 
 
 def delivery_options(args):

@@ -30,6 +30,12 @@ are --temporal_strength 0.6 alone and with --temporal_subpel 2, plus the device 
 (2, -1) quarter pixels: subpel 0 (fs_temporal_f32, the path without the key), 1 and 2 at one level and subpel 2 at three levels (fs_temporal_sub_f32:
 the refinement launch more, the bilinear blend), the graph-of-200 scheme; written to profiles/video_temporal_subpel.json.
 "temporal_subpel_kernels" as the third argument runs those graphs alone.
+"video" with "temporal_overlap" as the fifth argument (pipe_bench.py 1280 4 video profiles/video_temporal_overlap.json temporal_overlap): the two legs
+are --temporal_strength 0.6 alone and with --temporal_overlap 1, plus the device time of one 720p call of the stage at radius 7 with overlap 0
+(the path without the key) and 1 (fs_temporal_obmc_f32), at subpel 0 and 2, on three frames: one moved as a whole (every thread of the
+overlapped blend takes its one-vector shortcut), one whose neighbouring blocks alternate between two vectors (none does) and one whose two halves
+move apart; three alternating repeats of the graph-of-200 scheme, with the share of threads on the shortcut read back from the vectors; written
+to profiles/video_temporal_overlap.json.  "temporal_overlap_kernels" as the third argument runs those graphs alone.
 "resample" (pipe_bench.py 96 4 resample): the fp32 resampler.  The kernel alone (the graph-of-200 scheme, data resident): 720 x 1280 -> 2160 x 3840
 bicubic and lanczos, 2160 x 3840 -> 720 x 1280 bicubic; and the raw-video loop over a 2160p 4:2:0 file with --frame_size 1280 720, without and
 with --output_size source, as two legs that alternate in the one run (rates from the difference between n and n / 4 frames); written to
@@ -260,6 +266,61 @@ def temporal_subpel_kernel_times(W=1280, H=720, launches=200):
     return res
 
 
+def shortcut_share(mv, mvf, H, W):
+    """The share of the overlapped blend's threads (four pixels of a row) whose four candidate blocks hold one vector 4 mv + mvf"""
+    q = 4 * mv.astype(np.int64) + mvf
+    nby, nbx = q.shape[:2]
+    j0, i0 = (2 * np.arange(H) - 15) >> 5, (2 * np.arange(0, W, 4) - 15) >> 5
+    rows, cols = [np.clip(j0 + k, 0, nby - 1) for k in (0, 1)], [np.clip(i0 + k, 0, nbx - 1) for k in (0, 1)]
+    first = q[rows[0][:, None], cols[0][None, :]]
+    return float(np.mean(np.all([np.all(q[r[:, None], c[None, :]] == first, axis=-1) for r in rows for c in cols], axis=0)))
+
+
+def temporal_overlap_kernel_times(W=1280, H=720, launches=200, repeats=3):
+    """-> dict of device microseconds per 720p call of the temporal stage at radius 7 and one level by (frame, subpel, overlap), timed as
+    kernel_times does, `repeats` times with the twelve alternating: overlap 0 is the call of a lane without the key, the yardstick of the same
+    run.  Frames: 'uniform' moved by (2, -3) as a whole, 'alternating' with the blocks of even and odd row + column moved by (0, 3) and (0, -3),
+    'two_region' with the columns before 648 (mid-block) moved by (0, 3) and the others by (0, -3)."""
+    eng = engine.Engine()
+    mem = eng.mem
+    rng = np.random.default_rng(3)
+    small = rng.uniform(0, 255, (H // 8, W // 8, 3)).astype(np.float32)
+    a = np.ascontiguousarray(np.kron(small, np.ones((8, 8, 1), np.float32)) + rng.uniform(-4, 4, (H, W, 3)).astype(np.float32))
+    y, x = np.indices((H, W))
+    left, right = np.roll(a, -3, axis=1), np.roll(a, 3, axis=1)       # what a shows at (y, x + 3) and at (y, x - 3)
+    moved = {"uniform": np.roll(a, (-2, 3), axis=(0, 1)),
+             "alternating": np.where(((((y >> 4) + (x >> 4)) & 1) == 0)[..., None], left, right),
+             "two_region": np.where((x < 648)[..., None], left, right)}
+    src0 = mem.from_numpy(a[None])
+    cur = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    dst = mem.empty((1, H, W, 3))
+    kw = dict(strength_q8=154, sensitivity=16, src_bgr=True, radius=7)
+    runs = []
+    for frame, pic in moved.items():
+        src1 = mem.from_numpy(np.ascontiguousarray(pic)[None])
+        for subpel in (0, 2):
+            more = dict(subpel=subpel) if subpel else {}                                  # (subpel 0: the call of a lane without the key)
+            s0, s1 = (eng.temporal_state(H, W, **more) for _ in range(2))
+            eng.temporal_f32(src0, cur, dst, s0, **more, **kw)                            # the previous frame's state
+            for overlap in (0, 1):
+                over = dict(more, overlap=1) if overlap else more
+                runs.append(("%s_subpel_%d_overlap_%d" % (frame, subpel, overlap), subpel,
+                             lambda src1=src1, s0=s0, s1=s1, over=over: eng.temporal_f32(src1, cur, dst, s1, prev=s0, **over, **kw), s1))
+    res = {name: {"us_repeats": [], "launches": 4 if subpel else 3} for name, subpel, _, _ in runs}
+    for _ in range(repeats):
+        for name, subpel, fn, s1 in runs:
+            res[name]["us_repeats"].append(kernel_timed(fn, launches))
+            if "shortcut_share" not in res[name]:
+                mv = np.array(mem.to_numpy(s1[2]), dtype=np.uint8, copy=True).view(np.int8)
+                mvf = np.array(mem.to_numpy(s1[-1]), dtype=np.uint8, copy=True).view(np.int8) if subpel else np.zeros_like(mv)
+                res[name]["shortcut_share"] = shortcut_share(mv, mvf, H, W)
+    for name, r in res.items():
+        r["us"] = sorted(r["us_repeats"])[len(r["us_repeats"]) // 2]
+        print("video: %8.1f us per 720p call (repeats: %s), %3.0f %% of the threads see one vector: %s" %
+              (r["us"], ", ".join("%.1f" % u for u in r["us_repeats"]), 100 * r["shortcut_share"], name))
+    return res
+
+
 def resample_kernel_times(launches=200):
     """-> dict of device microseconds per call of fs_resample_f32, timed as kernel_times does, with the bytes each call reads and writes."""
     eng = engine.Engine()
@@ -379,11 +440,12 @@ def resample(n, repeats=3, out_json=None, legs=None, kernels=None, tag="resample
     return res
 
 
-def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False, temporal=False, temporal_levels=False, temporal_subpel=False):
+def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=False, temporal=False, temporal_levels=False, temporal_subpel=False,
+              temporal_overlap=False):
     """-> dict of the legs' rates (frames/s); prints them and writes profiles/frames_in.json (video: with the raw-video leg, to
     profiles/video_stream.json; video with a depth: the 8-bit and the deep raw-video legs alone, to profiles/video_deep.json; video with
     compose / temporal: the 8-bit raw-video leg without and with that stage, to profiles/video_compose.json / video_temporal.json)."""
-    compose_flag, compose = compose, compose or temporal or temporal_levels or temporal_subpel      # (the stages share the two-leg scheme)
+    compose_flag, compose = compose, compose or temporal or temporal_levels or temporal_subpel or temporal_overlap      # (the stages share the two-leg scheme)
     import contextlib
     import json
     import shutil
@@ -452,6 +514,9 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=Fals
     if temporal_subpel:
         legs = [("video_y4m_720p_temporal_strength_0.6", "720p", ("--temporal_strength", "0.6")),
                 ("video_y4m_720p_temporal_strength_0.6_subpel_2", "720p", ("--temporal_strength", "0.6", "--temporal_subpel", "2"))]
+    if temporal_overlap:
+        legs = [("video_y4m_720p_temporal_strength_0.6", "720p", ("--temporal_strength", "0.6")),
+                ("video_y4m_720p_temporal_strength_0.6_overlap_1", "720p", ("--temporal_strength", "0.6", "--temporal_overlap", "1"))]
     parser = stylize_webcam.setup_parser()
     out = os.path.join(d, "out")
 
@@ -521,7 +586,9 @@ def frames_in(n, repeats=3, out_json=None, video=False, depth=None, compose=Fals
         res["kernel_us_per_720p_call_by_levels"] = temporal_pyr_kernel_times()
     if temporal_subpel:
         res["kernel_us_per_720p_call_by_levels_and_subpel"] = temporal_subpel_kernel_times()
-    dst = out_json or os.path.join(root, "profiles", "video_temporal_subpel.json" if temporal_subpel else "video_temporal_pyr.json" if temporal_levels else "video_temporal.json" if temporal else "video_compose.json" if compose else "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
+    if temporal_overlap:
+        res["kernel_us_per_720p_call_by_frame_subpel_and_overlap"] = temporal_overlap_kernel_times()
+    dst = out_json or os.path.join(root, "profiles", "video_temporal_overlap.json" if temporal_overlap else "video_temporal_subpel.json" if temporal_subpel else "video_temporal_pyr.json" if temporal_levels else "video_temporal.json" if temporal else "video_compose.json" if compose else "video_deep.json" if depth else "video_stream.json" if video else "frames_in.json")
     with open(dst, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
@@ -535,9 +602,12 @@ def main():
     if len(sys.argv) > 3 and sys.argv[3] in ("frames_in", "video"):
         fifth = sys.argv[5] if len(sys.argv) > 5 and sys.argv[3] == "video" else None
         frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video",
-                  depth=int(fifth) if fifth not in (None, "compose", "temporal", "temporal_levels", "temporal_subpel") else None,
+                  depth=int(fifth) if fifth not in (None, "compose", "temporal", "temporal_levels", "temporal_subpel", "temporal_overlap") else None,
                   compose=fifth == "compose", temporal=fifth == "temporal", temporal_levels=fifth == "temporal_levels",
-                  temporal_subpel=fifth == "temporal_subpel")
+                  temporal_subpel=fifth == "temporal_subpel", temporal_overlap=fifth == "temporal_overlap")
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "temporal_overlap_kernels":
+        temporal_overlap_kernel_times()
         return
     if len(sys.argv) > 3 and sys.argv[3] == "temporal_subpel_kernels":
         temporal_subpel_kernel_times()
