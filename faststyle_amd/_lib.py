@@ -99,6 +99,12 @@ class fs_temporal_pyr_info(Structure):
                 ("pyr_bytes", c_uint64)]
 
 
+class fs_temporal_batch_info(Structure):
+    """include/faststyle_io.h: what fs_temporal_batch_layout reports."""
+    _fields_ = [("frames", ctypes.c_int32), ("levels", ctypes.c_int32), ("subpel", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("mv_offset", c_uint64), ("mv_stride", c_uint64), ("mvf_offset", c_uint64), ("mvf_stride", c_uint64), ("work_bytes", c_uint64)]
+
+
 class fs_yuv_desc(Structure):
     """include/faststyle_io.h: one planar YCbCr frame geometry, filled by fs_yuv_plan."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
@@ -227,6 +233,11 @@ PROTOTYPES = {
     # fs_temporal_sub_f32's arguments with int overlap after subpel
     "fs_temporal_obmc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fs_temporal_batch_layout": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_temporal_batch_info)]),
+    # fs_temporal_obmc_f32's arguments with int frames after Wo, and void* work, size_t work_bytes before dst
+    "fs_temporal_batch_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "fs_resample_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_resample_info)]),
     "fs_resample_tables": (c_int, [POINTER(fs_resample_info), c_void_p, c_size_t]),
     "fs_resample_f32": (c_int, [c_void_p, POINTER(fs_resample_info), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -146,6 +146,14 @@ def stylize_webcam_parser():
         ('--guided_smoothness', dict(default=argparse.SUPPRESS, type=int, metavar='E',
                                      help="(addition) smoothness of --output_guided in 8-bit levels, 1..64 (default 4): larger follows the source's "
                                           "edges less")),
+        ('--video_batch', dict(default=argparse.SUPPRESS, type=int, metavar='N',
+                               help="(addition) with --video_in: N consecutive frames per pass through the net, 1..64 (default 1); with "
+                                    "--temporal_strength the stage runs over the N frames in order; the results are written in order, a stream's "
+                                    "last frames included; latency grows by N frames, so live pipes keep 1")),
+        ('--precision', dict(default=argparse.SUPPRESS, choices=['fp32', 'bf16'],
+                             help="(addition) arithmetic of the net: fp32 (default) or bf16, the mixed-precision path of resize-conv models "
+                                  "(about twice the frame rate, about 52 dB against fp32; not with --upsample_method deconv); with --frames_dir, "
+                                  "--video_in and the camera")),
         ('--frame_filter', dict(default=argparse.SUPPRESS, choices=['box', 'bilinear', 'bicubic', 'lanczos'], metavar='F',
                                 help="(addition) with --video_depth stream, a --video_in of 9 to 16 bits and --frame_size: resample the stream's fp32 "
                                      "frames to W x H with this filter on the device (without it --frame_size refuses such a stream)")),

@@ -361,6 +361,53 @@ int fs_temporal_obmc_f32(fs_ctx* ctx, const float* src, int H, int W, const floa
                                          prev_pyr, luma, out88, pyr, mv, mvf, dst, ctx->stream);
     return rc ? fail(rc, "fs_temporal_obmc_f32: launch failed (%d)", rc) : 0;
 }
+int fs_temporal_batch_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int frames, int strength_q8, int sensitivity,
+                          int radius, int levels, int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma,
+                          const unsigned short* prev_out88, const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88,
+                          unsigned char* pyr, signed char* mv, signed char* mvf, void* work, size_t work_bytes, float* dst) {
+    if (!ctx || !src || !cur || !luma || !out88 || !mv || !dst) return fail(-1, "fs_temporal_batch_f32: null argument");
+    if ((prev_luma == nullptr) != (prev_out88 == nullptr))
+        return fail(-1, "fs_temporal_batch_f32: prev_luma and prev_out88 are both given or both null (no previous frame)");
+    if (prev_luma == luma || prev_out88 == out88)
+        return fail(-1, "fs_temporal_batch_f32: the previous frame's state is read at displaced positions and cannot be the state written");
+    if (H < 1 || W < 1 || Ho < H || Ho - H > 3 || Wo < W || Wo - W > 3)
+        return fail(-1, "fs_temporal_batch_f32: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", H, W, Ho, Wo);
+    if (strength_q8 < 0 || strength_q8 > 256) return fail(-2, "fs_temporal_batch_f32: strength_q8 must be in [0, 256], got %d", strength_q8);
+    if (sensitivity < 1 || sensitivity > 256) return fail(-2, "fs_temporal_batch_f32: sensitivity must be in [1, 256], got %d", sensitivity);
+    if (radius < 0 || radius > 7) return fail(-2, "fs_temporal_batch_f32: radius must be in [0, 7], got %d", radius);
+    if (levels < 1 || levels > FS_TEMPORAL_MAX_LEVELS)
+        return fail(-2, "fs_temporal_batch_f32: levels must be in [1, %d], got %d", FS_TEMPORAL_MAX_LEVELS, levels);
+    if (subpel < 0 || subpel > 2) return fail(-2, "fs_temporal_batch_f32: subpel must be 0 (whole), 1 (half) or 2 (quarter pixels), got %d", subpel);
+    if (overlap < 0 || overlap > 1) return fail(-2, "fs_temporal_batch_f32: overlap must be 0 (whole blocks) or 1 (the four nearest blocks), got %d", overlap);
+    if (matrix != 0 && matrix != 1) return fail(-2, "fs_temporal_batch_f32: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
+    if (src_bgr != 0 && src_bgr != 1) return fail(-2, "fs_temporal_batch_f32: src_bgr must be 0 or 1, got %d", src_bgr);
+    if (subpel > 0 && !mvf) return fail(-1, "fs_temporal_batch_f32: null mvf with subpel %d", subpel);
+    if (levels > 1) {
+        if (!pyr) return fail(-1, "fs_temporal_batch_f32: null pyr with %d levels", levels);
+        if ((prev_pyr == nullptr) != (prev_luma == nullptr))
+            return fail(-1, "fs_temporal_batch_f32: with %d levels prev_pyr is given exactly when prev_luma and prev_out88 are", levels);
+        if (prev_pyr == pyr) return fail(-1, "fs_temporal_batch_f32: the previous frame's pyramid cannot be the one written");
+    }
+    if (((uintptr_t)src | (uintptr_t)cur | (uintptr_t)dst) & 3) return fail(-5, "fs_temporal_batch_f32: src, cur and dst must be 4-byte aligned");
+    if (((uintptr_t)prev_out88 | (uintptr_t)out88) & 1) return fail(-5, "fs_temporal_batch_f32: prev_out88 and out88 must be 2-byte aligned");
+    if (frames < 1 || frames > 64) return fail(-1, "fs_temporal_batch_f32: frames must be in [1, 64], got %d", frames);
+    fs_temporal_batch_info blay;
+    if (fs_temporal_batch_layout(Ho, Wo, levels, subpel, frames, &blay)) return -1;  // (cannot happen: checked above; the message is its own)
+    if (frames > 1) {
+        if (!work || work_bytes < blay.work_bytes)
+            return fail(-1, "fs_temporal_batch_f32: %d frames need a work buffer of %llu bytes (fs_temporal_batch_layout), got %s of %llu", frames,
+                        (unsigned long long)blay.work_bytes, work ? "one" : "null", (unsigned long long)work_bytes);
+        if ((uintptr_t)work & 15) return fail(-5, "fs_temporal_batch_f32: work must be 16-byte aligned");
+    }
+    fs_temporal_pyr_info lay;
+    if (fs_temporal_pyr_layout(Ho, Wo, levels, &lay)) return -1;                    // (cannot happen: checked above; the message is its own)
+    const int rc = frames == 1
+                       ? fs::temporal_obmc_f32(lay, src, H, W, cur, strength_q8, sensitivity, radius, subpel, overlap, matrix, src_bgr, prev_luma,
+                                               prev_out88, prev_pyr, luma, out88, pyr, mv, mvf, dst, ctx->stream)
+                       : fs::temporal_batch_f32(lay, src, H, W, cur, frames, strength_q8, sensitivity, radius, subpel, overlap, matrix, src_bgr, prev_luma,
+                                                prev_out88, prev_pyr, luma, out88, pyr, mv, mvf, static_cast<unsigned char*>(work), dst, ctx->stream);
+    return rc ? fail(rc, "fs_temporal_batch_f32: launch failed (%d)", rc) : 0;
+}
 int fs_resample_f32(fs_ctx* ctx, const fs_resample_info* plan, const void* tables_dev, const float* src, int src_rows, int src_pitch, int N, float* dst) {
     if (!ctx || !plan || !src || !dst) return fail(-1, "fs_resample_f32: null argument");
     if (N < 1 || N > 65535) return fail(-1, "fs_resample_f32: N must be in [1, 65535], got %d", N);

@@ -716,6 +716,12 @@ int temporal_obmc_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H
                       int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
                       const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf,
                       float* dst, hipStream_t s);
+// ... over `frames` > 1 consecutive frames: luma, pyramid, every search level and the refinement once over all frames, then one blend per
+// frame in order; the frames before the last keep their state in `work` (fs_temporal_batch_layout's work_bytes, 16-byte aligned)
+int temporal_batch_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int frames, int strength_q8, int sensitivity,
+                       int radius, int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
+                       const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf,
+                       unsigned char* work, float* dst, hipStream_t s);
 // resampling between fp32 tensors (fs_resample.hip): whether a plan is what fs_resample_plan fills, and the one launch (argument checks are in
 // fs_api.hip)
 bool resample_plan_ok(const ::fs_resample_info& plan);

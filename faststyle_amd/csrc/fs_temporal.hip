@@ -57,7 +57,7 @@ struct LumaArgs {
 };
 
 // Thread i: row y = i / groups, pixels x0 = 4 * (i % groups) ... x0 + 3 (groups = ceil(Wo / 4)); the source is read at (min(y, H - 1), min(x, W - 1)).
-__global__ __launch_bounds__(256) void temporal_luma_kernel(const LumaArgs A, const float* __restrict__ src, unsigned char* __restrict__ luma) {
+__device__ __forceinline__ void temporal_luma_body(const LumaArgs& A, const float* __restrict__ src, unsigned char* __restrict__ luma) {
     const int groups = (A.Wo + 3) >> 2;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)groups * A.Ho) return;
@@ -74,6 +74,10 @@ __global__ __launch_bounds__(256) void temporal_luma_kernel(const LumaArgs A, co
         const long long Y = ((long long)A.k0 * A0 + (long long)A.k1 * A1 + (long long)A.k2 * A2 + 32768) >> 16;       // 0 ... 65280
         lrow[x] = (unsigned char)(Y >> 8);
     }
+}
+
+__global__ __launch_bounds__(256) void temporal_luma_kernel(const LumaArgs A, const float* __restrict__ src, unsigned char* __restrict__ luma) {
+    temporal_luma_body(A, src, luma);
 }
 
 // One workgroup per block (blockIdx.y, blockIdx.x).  prev == nullptr (no previous frame): every vector is (0, 0).
@@ -235,8 +239,8 @@ __device__ __forceinline__ int pyr_level1(const unsigned char* __restrict__ l0, 
 // Levels 1 and 2 in one launch: workgroup row blockIdx.x < H1 is row y of level 1, row H1 + y is row y of level 2; thread blockIdx.y * 256 + t
 // writes the four bytes x0 = 4 (...) ... x0 + 3 of that row.  A byte of level 2 comes from its four level-1 bytes recomputed from level 0 with
 // the nested rounding and clamps, so level 2 does not wait for level 1.  Bytes throughout: the buffers are held to no alignment.
-__global__ __launch_bounds__(256) void temporal_pyramid_kernel(const PyrArgs A, const unsigned char* __restrict__ l0, unsigned char* __restrict__ l1,
-                                                               unsigned char* __restrict__ l2) {
+__device__ __forceinline__ void temporal_pyramid_body(const PyrArgs& A, const unsigned char* __restrict__ l0, unsigned char* __restrict__ l1,
+                                                      unsigned char* __restrict__ l2) {
     const int x0 = ((int)blockIdx.y * 256 + (int)threadIdx.x) * 4;
     int y = (int)blockIdx.x;
     if (y < A.H1) {                                         // (uniform per workgroup)
@@ -254,13 +258,18 @@ __global__ __launch_bounds__(256) void temporal_pyramid_kernel(const PyrArgs A, 
     }
 }
 
+__global__ __launch_bounds__(256) void temporal_pyramid_kernel(const PyrArgs A, const unsigned char* __restrict__ l0, unsigned char* __restrict__ l1,
+                                                               unsigned char* __restrict__ l2) {
+    temporal_pyramid_body(A, l0, l1, l2);
+}
+
 // temporal_search_kernel on one level (cur8 / prev8 [H, W]) with the window's origin displaced by the block's predictor, twice the vector of
 // block (by >> 1, bx >> 1) of the coarser level (parent [.., pnbx, 2]; nullptr at the coarsest level: (0, 0)), held to `hold` per component
 // before it reaches an address.  The window is (y0 + py - R, x0 + px - R) ..., each byte clamped into the level, so the LDS layout, the
 // candidates' reads and their conflict-freedom are those of temporal_search_kernel; the winner is the predictor plus the refinement.
-__global__ __launch_bounds__(256) void temporal_search_pred_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int H,
-                                                                   int W, int R, const signed char* __restrict__ parent, int pnbx, int hold,
-                                                                   signed char* __restrict__ v) {
+__device__ __forceinline__ void temporal_search_pred_body(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int H, int W,
+                                                          int R, const signed char* __restrict__ parent, int pnbx, int hold,
+                                                          signed char* __restrict__ v) {
     __shared__ unsigned win[TWROWS * (TPITCH / 4)];
     __shared__ unsigned blk[TB * (TB / 4)];
     __shared__ unsigned keys[256];
@@ -344,6 +353,12 @@ __global__ __launch_bounds__(256) void temporal_search_pred_kernel(const unsigne
         out[0] = (signed char)(py + (int)((k >> 4) & 15u) - 7);                          // |.| <= hold + R <= 49
         out[1] = (signed char)(px + (int)(k & 15u) - 7);
     }
+}
+
+__global__ __launch_bounds__(256) void temporal_search_pred_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int H,
+                                                                   int W, int R, const signed char* __restrict__ parent, int pnbx, int hold,
+                                                                   signed char* __restrict__ v) {
+    temporal_search_pred_body(cur8, prev8, H, W, R, parent, pnbx, hold, v);
 }
 
 }  // namespace
@@ -436,9 +451,8 @@ __device__ __forceinline__ int subpel_fit(int s0, int m, int p, int S) {
 
 // One workgroup per block (blockIdx.y, blockIdx.x) of level 0.  prev8 == nullptr (no previous frame) or R == 0: every fraction is (0, 0).
 // mv is held to `hold` per component before it reaches an address; nothing else read from a buffer does.
-__global__ __launch_bounds__(256) void temporal_subpel_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int Ho,
-                                                              int Wo, int R, int hold, int S, const signed char* __restrict__ mv,
-                                                              signed char* __restrict__ mvf) {
+__device__ __forceinline__ void temporal_subpel_body(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int Ho, int Wo,
+                                                     int R, int hold, int S, const signed char* __restrict__ mv, signed char* __restrict__ mvf) {
     __shared__ unsigned win[SWROWS * SPITCH];
     __shared__ unsigned blk[TB * (TB / 4)];
     __shared__ unsigned part[5 * 64];                       // S0, Sym, Syp, Sxm, Sxp: 64 partial sums each
@@ -502,6 +516,12 @@ __global__ __launch_bounds__(256) void temporal_subpel_kernel(const unsigned cha
         out[0] = (signed char)subpel_fit(s0, (int)part[64], (int)part[128], S);
         out[1] = (signed char)subpel_fit(s0, (int)part[192], (int)part[256], S);
     }
+}
+
+__global__ __launch_bounds__(256) void temporal_subpel_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int Ho,
+                                                              int Wo, int R, int hold, int S, const signed char* __restrict__ mv,
+                                                              signed char* __restrict__ mvf) {
+    temporal_subpel_body(cur8, prev8, Ho, Wo, R, hold, S, mv, mvf);
 }
 
 // temporal_blend_kernel's threads and arguments, with the block's fraction mvf beside its vector: the previous luma and output are fetched
@@ -862,9 +882,175 @@ int temporal_obmc_f32(const fs_temporal_pyr_info& lay, const float* src, int H, 
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+// ---- batches of consecutive frames (fs_temporal_batch_f32): only the blend is recursive, so the launches before it run once over all frames
+//   The kernels are the bodies above with the frame index f as one more grid dimension (blockIdx.y of the luma's 1-D grid, blockIdx.z of the
+//   others).  A buffer of frame f lies in the work buffer's slot f, except the last frame's, which is the state's (pointer selection, no copy
+//   launch); frame f's "previous" is slot f - 1, for f = 0 the state the previous call wrote (null: no previous frame).  f is uniform per
+//   workgroup and held below `frames`, so the selection stays in scalar registers; no value read from a tensor takes part in it.
+namespace {
+
+struct FrameSel {
+    unsigned char* work;                    // slot f at work + f * slot, f < frames - 1
+    unsigned long long slot;
+    int frames;
+};
+
+// one buffer of every frame: the last frame's (in the state written), frame 0's predecessor (in the state read, or null), the offset in a slot
+struct FrameBuf {
+    unsigned char* last;
+    const unsigned char* before;
+    unsigned long long off;
+};
+
+__device__ __forceinline__ unsigned char* frame_at(const FrameSel& S, const FrameBuf& B, int f) {
+    return f == S.frames - 1 ? B.last : S.work + (size_t)f * S.slot + B.off;
+}
+
+__device__ __forceinline__ const unsigned char* frame_before(const FrameSel& S, const FrameBuf& B, int f) {
+    return f == 0 ? B.before : S.work + (size_t)(f - 1) * S.slot + B.off;
+}
+
+__global__ __launch_bounds__(256) void temporal_luma_batch_kernel(const LumaArgs A, const FrameSel S, const FrameBuf L, const float* __restrict__ src) {
+    const int f = (int)blockIdx.y;
+    if (f >= S.frames) return;
+    temporal_luma_body(A, src + (size_t)f * A.H * A.W * 3, frame_at(S, L, f));
+}
+
+__global__ __launch_bounds__(256) void temporal_pyramid_batch_kernel(const PyrArgs A, const FrameSel S, const FrameBuf L0, const FrameBuf L1,
+                                                                     const FrameBuf L2) {
+    const int f = (int)blockIdx.z;
+    if (f >= S.frames) return;
+    temporal_pyramid_body(A, frame_at(S, L0, f), frame_at(S, L1, f), A.H2 > 0 ? frame_at(S, L2, f) : nullptr);
+}
+
+// C: the level's luma (its predecessor: the previous luma), P: the coarser level's vectors (has_parent 0: none), V: the vectors written
+__global__ __launch_bounds__(256) void temporal_search_batch_kernel(const FrameSel S, const FrameBuf C, int H, int W, int R, const FrameBuf P, int has_parent,
+                                                                    int pnbx, int hold, const FrameBuf V) {
+    const int f = (int)blockIdx.z;
+    if (f >= S.frames) return;
+    temporal_search_pred_body(frame_at(S, C, f), frame_before(S, C, f), H, W, R, has_parent ? (const signed char*)frame_at(S, P, f) : nullptr, pnbx, hold,
+                              (signed char*)frame_at(S, V, f));
+}
+
+__global__ __launch_bounds__(256) void temporal_subpel_batch_kernel(const FrameSel S, const FrameBuf C, int Ho, int Wo, int R, int hold, int Sp,
+                                                                    const FrameBuf MV, const FrameBuf MVF) {
+    const int f = (int)blockIdx.z;
+    if (f >= S.frames) return;
+    temporal_subpel_body(frame_at(S, C, f), frame_before(S, C, f), Ho, Wo, R, hold, Sp, (const signed char*)frame_at(S, MV, f),
+                         (signed char*)frame_at(S, MVF, f));
+}
+
+inline uint64_t up16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
+
+// the work buffer: frames - 1 slots of [luma | pyr | mv | mvf], then min(frames - 1, 2) out88 frames (a blend reads its predecessor's only)
+struct BatchLay {
+    uint64_t luma_off, pyr_off, mv_off, mvf_off, slot, o88_off, o88_size, bytes;
+};
+
+BatchLay batch_lay(const fs_temporal_pyr_info& lay, int subpel, int frames) {
+    BatchLay b;
+    const uint64_t blocks = up16((uint64_t)lay.nby[0] * (uint64_t)lay.nbx[0] * 2);
+    b.luma_off = 0;
+    b.pyr_off = up16((uint64_t)lay.h[0] * (uint64_t)lay.w[0]);
+    b.mv_off = b.pyr_off + lay.pyr_bytes;   // (a multiple of 16 already)
+    b.mvf_off = b.mv_off + blocks;
+    b.slot = b.mvf_off + (subpel > 0 ? blocks : 0);
+    b.o88_off = b.slot * (uint64_t)(frames - 1);
+    b.o88_size = up16((uint64_t)lay.h[0] * (uint64_t)lay.w[0] * 6);
+    b.bytes = b.o88_off + b.o88_size * (uint64_t)(frames - 1 < 2 ? frames - 1 : 2);
+    return b;
+}
+
+}  // namespace
+
+// arguments: checked by the caller (fs_api.hip: fs_temporal_batch_f32), frames > 1
+int temporal_batch_f32(const fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int frames, int strength_q8, int sensitivity,
+                       int radius, int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
+                       const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf,
+                       unsigned char* work, float* dst, hipStream_t s) {
+    const int L = lay.levels, Ho = lay.h[0], Wo = lay.w[0], N = frames;
+    const BatchLay B = batch_lay(lay, subpel, N);
+    FrameSel S;
+    S.work = work; S.slot = B.slot; S.frames = N;
+    const FrameBuf FL = {luma, prev_luma, B.luma_off};
+    const FrameBuf FMV = {(unsigned char*)mv, nullptr, B.mv_off}, FMVF = {(unsigned char*)mvf, nullptr, B.mvf_off};
+    FrameBuf FPL[FS_TEMPORAL_MAX_LEVELS], FPV[FS_TEMPORAL_MAX_LEVELS];                    // the levels' lumas and vectors; entry 0: level 0's
+    FPL[0] = FL; FPV[0] = FMV;
+    for (int l = 1; l < L; ++l) {
+        FPL[l] = {pyr + lay.luma_offset[l], prev_luma == nullptr ? nullptr : prev_pyr + lay.luma_offset[l], B.pyr_off + lay.luma_offset[l]};
+        FPV[l] = {pyr + lay.mv_offset[l], nullptr, B.pyr_off + lay.mv_offset[l]};
+    }
+    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
+    LumaArgs LA;
+    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
+    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
+    const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
+    const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
+    hipLaunchKernelGGL(temporal_luma_batch_kernel, dim3(egrid.x, (unsigned)N), block, 0, s, LA, S, FL, src);
+    if (L > 1) {
+        PyrArgs PA;
+        PA.H0 = Ho; PA.W0 = Wo; PA.H1 = lay.h[1]; PA.W1 = lay.w[1];
+        PA.H2 = L > 2 ? lay.h[2] : 0; PA.W2 = L > 2 ? lay.w[2] : 0;
+        const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);
+        hipLaunchKernelGGL(temporal_pyramid_batch_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks, (unsigned)N), block, 0, s, PA, S, FL, FPL[1],
+                           L > 2 ? FPL[2] : FPL[1]);
+    }
+    for (int l = L - 1; l >= 0; --l)                        // coarsest first, as in temporal_pyr_f32
+        hipLaunchKernelGGL(temporal_search_batch_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l], (unsigned)N), block, 0, s, S, FPL[l], lay.h[l],
+                           lay.w[l], radius, l == L - 1 ? FPV[l] : FPV[l + 1], l == L - 1 ? 0 : 1, l == L - 1 ? 0 : lay.nbx[l + 1],
+                           2 * radius * ((1 << (L - 1 - l)) - 1), FPV[l]);
+    const int hold = radius * ((1 << L) - 1);
+    if (subpel > 0)
+        hipLaunchKernelGGL(temporal_subpel_batch_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0], (unsigned)N), block, 0, s, S, FL, Ho, Wo, radius,
+                           hold, subpel, FMV, FMVF);
+    BlendArgs BA;
+    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = lay.nbx[0];
+    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = hold;
+    const size_t image = (size_t)Ho * Wo * 3;
+    for (int i = 0; i < N; ++i) {                           // in order: frame i reads the out88 frame i - 1 wrote (the two in `work` alternate)
+        const bool last = i == N - 1;
+        const unsigned char* c8 = last ? luma : work + (size_t)i * B.slot + B.luma_off;
+        const unsigned char* p8 = i == 0 ? prev_luma : work + (size_t)(i - 1) * B.slot + B.luma_off;
+        const unsigned short* p88 = i == 0 ? prev_out88 : (const unsigned short*)(work + B.o88_off + (size_t)((i - 1) & 1) * B.o88_size);
+        unsigned short* o88 = last ? out88 : (unsigned short*)(work + B.o88_off + (size_t)(i & 1) * B.o88_size);
+        const signed char* v = (const signed char*)(last ? (unsigned char*)mv : work + (size_t)i * B.slot + B.mv_off);
+        const signed char* vf = subpel > 0 ? (const signed char*)(last ? (unsigned char*)mvf : work + (size_t)i * B.slot + B.mvf_off) : nullptr;
+        if (overlap)
+            hipLaunchKernelGGL(temporal_blend_obmc_kernel, egrid, block, 0, s, BA, lay.nby[0], cur + i * image, c8, p8, p88, v, vf, dst + i * image, o88);
+        else if (subpel > 0)
+            hipLaunchKernelGGL(temporal_blend_sub_kernel, egrid, block, 0, s, BA, cur + i * image, c8, p8, p88, v, vf, dst + i * image, o88);
+        else
+            hipLaunchKernelGGL(temporal_blend_kernel, egrid, block, 0, s, BA, cur + i * image, c8, p8, p88, v, dst + i * image, o88);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 }  // namespace fs
 
 extern "C" {
+
+int fs_temporal_batch_layout(int Ho, int Wo, int levels, int subpel, int frames, fs_temporal_batch_info* info) {
+    using namespace fs;
+    if (!info) return set_error(-1, "fs_temporal_batch_layout: null argument");
+    if (Ho < 1 || Wo < 1) return set_error(-1, "fs_temporal_batch_layout: a %dx%d output has a side below 1", Ho, Wo);
+    if (frames < 1 || frames > 64) return set_error(-1, "fs_temporal_batch_layout: frames must be in [1, 64], got %d", frames);
+    if (levels < 1 || levels > FS_TEMPORAL_MAX_LEVELS)
+        return set_error(-2, "fs_temporal_batch_layout: levels must be in [1, %d], got %d", FS_TEMPORAL_MAX_LEVELS, levels);
+    if (subpel < 0 || subpel > 2) return set_error(-2, "fs_temporal_batch_layout: subpel must be 0 (whole), 1 (half) or 2 (quarter pixels), got %d", subpel);
+    fs_temporal_pyr_info lay;
+    if (fs_temporal_pyr_layout(Ho, Wo, levels, &lay)) return -1;                    // (cannot happen: checked above)
+    const BatchLay B = batch_lay(lay, subpel, frames);
+    fs_temporal_batch_info b;
+    memset(&b, 0, sizeof(b));
+    b.frames = frames; b.levels = levels; b.subpel = subpel;
+    if (frames > 1) {
+        b.mv_offset = B.mv_off; b.mv_stride = B.slot;
+        if (subpel > 0) { b.mvf_offset = B.mvf_off; b.mvf_stride = B.slot; }
+        b.work_bytes = B.bytes;
+    }
+    *info = b;
+    return 0;
+}
 
 int fs_temporal_pyr_layout(int Ho, int Wo, int levels, fs_temporal_pyr_info* info) {
     using namespace fs;

@@ -1228,6 +1228,77 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
                                                         p8(state[-1]) if subpel > 0 else None, self.mem.ptr(dst)), "fs_temporal_obmc_f32")
         return dst
 
+    def temporal_batch_layout(self, Ho, Wo, frames, levels=1, subpel=0):
+        """fs_temporal_batch_layout: the size of the work buffer of `frames` consecutive frames per call and where the vectors of the frames
+        before the last lie in it (host only)."""
+        info = L.fs_temporal_batch_info()
+        L.check(self.lib, self.lib.fs_temporal_batch_layout(int(Ho), int(Wo), int(levels), int(subpel), int(frames), ctypes.byref(info)),
+                "fs_temporal_batch_layout")
+        return info
+
+    def temporal_batch_work(self, Ho, Wo, frames, levels=1, subpel=0):
+        """The work buffer of temporal_batch_f32 as a device uint8 buffer (the memory backend's) of temporal_batch_layout's work_bytes (at
+        least 16, so that one frame per call has a buffer too)."""
+        return self.mem.upload_u8(np.zeros((max(16, int(self.temporal_batch_layout(Ho, Wo, frames, levels, subpel).work_bytes)),), np.uint8))
+
+    def temporal_batch_f32(self, src, cur, dst, state, work, prev=None, strength_q8=256, sensitivity=16, radius=7, matrix="bt601", src_bgr=False,
+                           levels=1, subpel=0, overlap=0):
+        """fs_temporal_batch_f32: temporal_f32 over N consecutive frames of one stream, oldest first -- src device float32 [N,H,W,3], cur and dst
+        [N,Ho,Wo,3] (dst may be cur), state the slot that receives frame N - 1's state, prev the slot the previous call wrote (None: no previous
+        frame before frame 0), both temporal_state(Ho, Wo, levels, subpel)'s; work temporal_batch_work's for at least N frames.  dst[i] is what
+        the i-th of N chained temporal_f32 calls gives, bit for bit."""
+        self._sync_stream()
+        self._temporal_sub_check(levels, subpel)
+        if isinstance(overlap, bool) or not isinstance(overlap, (int, np.integer)) or not 0 <= overlap <= 1:
+            raise L.FaststyleError("temporal_batch_f32: overlap must be a whole number in [0, 1], got %r" % (overlap,))
+        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
+        if len(ss) != 4 or len(cs) != 4 or ss[3] != 3 or cs[3] != 3 or ds != cs or ss[0] != cs[0]:
+            raise L.FaststyleError("temporal_batch_f32: source %s / current %s / destination %s do not belong together ([N,H,W,3] / [N,Ho,Wo,3] each)" %
+                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
+        N, Ho, Wo = cs[:3]
+        if not 1 <= N <= 64:
+            raise L.FaststyleError("temporal_batch_f32: 1 to 64 frames per call, got %d" % N)
+        blocks = ((Ho + 15) // 16, (Wo + 15) // 16, 2)
+        want = ((Ho, Wo), (Ho, Wo, 3, 2), blocks)
+        if levels > 1:
+            want += ((int(self.temporal_pyr_layout(Ho, Wo, levels).pyr_bytes),),)
+        if subpel > 0:
+            want += (blocks,)
+        for name, slot in (("state", state), ("prev", prev)):
+            if slot is not None and (len(slot) != len(want) or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
+                raise L.FaststyleError("temporal_batch_f32: %s is not the slot of a %dx%d output with %d levels and subpel %d (temporal_state)" %
+                                       (name, Ho, Wo, levels, subpel))
+        need = int(self.temporal_batch_layout(Ho, Wo, N, levels, subpel).work_bytes)
+        nbytes = 0 if work is None else int(np.prod(work.shape))
+        if nbytes < need:
+            raise L.FaststyleError("temporal_batch_f32: %d frames of %dx%d need a work buffer of %d bytes (temporal_batch_work), got %d" %
+                                   (N, Ho, Wo, need, nbytes))
+        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
+        p8 = self.mem.ptr_u8
+        pyr = (lambda slot: p8(slot[3])) if levels > 1 else (lambda slot: None)
+        pl, po, pp = (None, None, None) if prev is None else (p8(prev[0]), p8(prev[1]), pyr(prev))
+        L.check(self.lib, self.lib.fs_temporal_batch_f32(self.ctx, self.mem.ptr(src), ss[1], ss[2], self.mem.ptr(cur), Ho, Wo, N, int(strength_q8),
+                                                         int(sensitivity), int(radius), int(levels), int(subpel), int(overlap), int(matrix),
+                                                         1 if src_bgr else 0, pl, po, pp, p8(state[0]), p8(state[1]), pyr(state), p8(state[2]),
+                                                         p8(state[-1]) if subpel > 0 else None, None if work is None else p8(work), nbytes,
+                                                         self.mem.ptr(dst)), "fs_temporal_batch_f32")
+        return dst
+
+    def temporal_batch_vectors(self, work, state, Ho, Wo, frames, levels=1, subpel=0):
+        """For tests and motion_vectors(): the vectors of every frame of the last temporal_batch_f32 call as host arrays -> (mv int8
+        [frames,nby,nbx,2], mvf likewise or None with subpel 0): the frames before the last from `work`, the last from `state` (synchronises)."""
+        lay = self.temporal_batch_layout(Ho, Wo, frames, levels, subpel)
+        nby, nbx = (int(Ho) + 15) // 16, (int(Wo) + 15) // 16
+        n = nby * nbx * 2
+        raw = np.array(self.mem.to_numpy(work), dtype=np.uint8, copy=True).reshape(-1) if frames > 1 else None
+
+        def gather(offset, stride, last):
+            rows = [raw[offset + i * stride:offset + i * stride + n] for i in range(frames - 1)]
+            rows.append(np.array(self.mem.to_numpy(last), dtype=np.uint8, copy=True).reshape(-1))
+            return np.stack(rows).view(np.int8).reshape(frames, nby, nbx, 2)
+        mv = gather(int(lay.mv_offset), int(lay.mv_stride), state[2])
+        return mv, (gather(int(lay.mvf_offset), int(lay.mvf_stride), state[-1]) if subpel > 0 else None)
+
     def synth_uniform(self, out, seed, rank, batch_index):
         """Uniform [0,255) float32 values into ``out``: Philox4x32-10 keyed by seed, counter (element block, batch_index, rank) (fs_synth_uniform)."""
         self._sync_stream()

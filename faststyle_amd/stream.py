@@ -64,6 +64,12 @@ With ``subpel=0`` or without the key nothing changes.
 a bilinear window and by how well the source matched along each (fs_temporal_obmc_f32), so that a block that straddles a motion edge keeps
 its weight on both sides; the slots and the number of launches are those of ``levels`` and ``subpel``.  With ``overlap=0`` or without the key
 nothing changes.
+``sequence=True`` on a lane with ``batch=N`` says that the batch's images are N consecutive frames of one stream, oldest first
+(fs_temporal_batch_f32): luma, pyramid, searches and refinement run once over the N frames and N blends follow in order, frame i reading
+what frame i - 1 left, frame 0 what the previous pass left.  Slot parity, the three tail graphs, ``reset()`` and the frame counter then go by
+pass; the lane has one work buffer more for the frames inside a pass, ``stabilised_output()`` is [N, Ho, Wo, 3] and ``motion_vectors()`` /
+``motion_vectors_subpel()`` have a leading axis of N.  A pass always takes N frames: the caller pads a stream's end by repeating its last
+frame.  Without the key a batch other than 1 is refused (a batch could as well be N independent streams); with it at batch 1 nothing changes.
 
 Delivery at another size: with ``deliver=dict(height=, width=, filter='bicubic')`` one launch ahead of the output conversions (fs_resample_f32,
 csrc/fs_resample.hip) resamples the top-left H x W of the tensor they would read -- the net's output, the composed or the stabilised tensor --
@@ -177,6 +183,7 @@ class FrameStylizer(object):
         self._stab = None                # ... the stabilised tensor every output conversion then reads
         self._tslots = None              # ... the two state slots (Engine.temporal_state), shared by the lanes of a PipelinedStylizer
         self._tn = 0                     # ... frames since construction or reset(): frame n reads slot (n - 1) & 1 and writes slot n & 1
+        self._twork = None               # ... with sequence=True and a batch: the work buffer of the frames inside a pass (then _tn counts passes)
         self._cur = None                 # ... the head's result: the net's output or the composed tensor
         self._tail_graphs = {}           # ... captured tails by the parity written (None: a first frame's)
         if temporal is not None:
@@ -264,14 +271,17 @@ class FrameStylizer(object):
             raise L.FaststyleError("deliver guided= needs a source that is resized to the net's size (interpolation=, or resample= for 9 to 16 bits)")
         self._guided_work = self.eng.guided_workspace(H, W, B)
 
-    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels", "subpel", "overlap")
+    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels", "subpel", "overlap", "sequence")
 
     def _temporal_setup(self, opt, slots):
         """The temporal stage's fixed parts: the quantised strength, the checked parameters, the state slots and the stabilised tensor."""
         kw = {k: opt.pop(k) for k in self.TEMPORAL_KEYS if k in opt}
         if opt:
             raise L.FaststyleError("temporal takes %s, got also %r" % (", ".join(self.TEMPORAL_KEYS), opt))
-        if self.shape[0] != 1:
+        sequence = kw.get("sequence", False)
+        if not isinstance(sequence, (bool, np.bool_)):
+            raise L.FaststyleError("temporal sequence is True or False, got %r" % (sequence,))
+        if self.shape[0] != 1 and not sequence:
             raise L.FaststyleError("temporal takes one frame per pass, this stylizer has a batch of %d" % self.shape[0])
 
         def number(name, default, lo, hi, whole):
@@ -303,6 +313,9 @@ class FrameStylizer(object):
             slots = [self.eng.temporal_state(Ho, Wo, levels, subpel) if subpel > 0 else self.eng.temporal_state(Ho, Wo, levels) for _ in range(2)]
         self._tslots = slots
         self._stab = self.eng.mem.empty(self.out_shape)
+        if self.shape[0] != 1:                               # (sequence=True at batch 1 is the lane without the key)
+            self.temporal["sequence"] = True
+            self._twork = self.eng.temporal_batch_work(Ho, Wo, self.shape[0], levels, subpel)
 
     COMPOSE_KEYS = ("strength", "keep_color", "matrix", "mask", "source_swapped")
 
@@ -556,9 +569,12 @@ class FrameStylizer(object):
         """The temporal stage of frame n since construction or reset(), and the output conversions of the stabilised tensor.  It writes
         slot n & 1 and reads slot (n - 1) & 1, so running it twice on one frame (the warm-up of a capture, then the replay) changes nothing."""
         t = self.temporal
-        self.eng.temporal_f32(self._in_f32, self._cur, self._stab, self._tslots[n & 1], prev=None if n == 0 else self._tslots[(n - 1) & 1],
-                              strength_q8=t["strength_q8"], sensitivity=t["sensitivity"], radius=t["radius"], matrix=t["matrix"],
-                              src_bgr=t["source_bgr"], levels=t.get("levels", 1), **{k: t[k] for k in ("subpel", "overlap") if k in t})
+        kw = dict(prev=None if n == 0 else self._tslots[(n - 1) & 1], strength_q8=t["strength_q8"], sensitivity=t["sensitivity"], radius=t["radius"],
+                  matrix=t["matrix"], src_bgr=t["source_bgr"], levels=t.get("levels", 1), **{k: t[k] for k in ("subpel", "overlap") if k in t})
+        if self._twork is not None:                          # a pass of consecutive frames: n counts passes
+            self.eng.temporal_batch_f32(self._in_f32, self.eng.mem.view(self._cur, 0, self.out_shape), self._stab, self._tslots[n & 1], self._twork, **kw)
+        else:
+            self.eng.temporal_f32(self._in_f32, self._cur, self._stab, self._tslots[n & 1], **kw)
         self._outputs(self._stab)
 
     def _captured(self, launches):
@@ -667,8 +683,8 @@ class FrameStylizer(object):
         return np.array(self.eng.mem.to_numpy(self._composed), dtype=np.float32, copy=True)
 
     def stabilised_output(self):
-        """For tests and inspection: a host float32 copy [1,Ho,Wo,3] of the stabilised tensor of the last pass (synchronises); a stylizer
-        built without temporal= has none."""
+        """For tests and inspection: a host float32 copy [B,Ho,Wo,3] of the stabilised tensor of the last pass (synchronises; B is 1 but on a
+        sequence lane); a stylizer built without temporal= has none."""
         if self._stab is None:
             raise L.FaststyleError("stabilised_output: this stylizer was built without temporal=")
         if self._y is None:
@@ -685,12 +701,21 @@ class FrameStylizer(object):
         return np.array(self.eng.mem.to_numpy(self._delivered), dtype=np.float32, copy=True)
 
     def motion_vectors(self):
-        """For tests and inspection: the block vectors (dy, dx) of the last pass, host int8 [ceil(Ho / 16), ceil(Wo / 16), 2] (synchronises)."""
+        """For tests and inspection: the block vectors (dy, dx) of the last pass, host int8 [ceil(Ho / 16), ceil(Wo / 16), 2], on a sequence
+        lane of batch N [N, ...] (synchronises)."""
         if self._tslots is None:
             raise L.FaststyleError("motion_vectors: this stylizer was built without temporal=")
         if self._tn == 0:
             raise L.FaststyleError("motion_vectors: this stylizer has not run a frame since it was built or reset")
+        if self._twork is not None:
+            return self._batch_vectors()[0]
         return np.array(self.eng.mem.to_numpy(self._tslots[(self._tn - 1) & 1][2]), dtype=np.uint8, copy=True).view(np.int8)
+
+    def _batch_vectors(self):
+        """(mv, mvf or None) of the N frames of a sequence lane's last pass"""
+        t = self.temporal
+        return self.eng.temporal_batch_vectors(self._twork, self._tslots[(self._tn - 1) & 1], self.out_shape[1], self.out_shape[2], self.shape[0],
+                                               t.get("levels", 1), t.get("subpel", 0))
 
     def motion_vectors_subpel(self):
         """For tests and inspection: the block vectors (dy, dx) of the last pass in quarter pixels, 4 mv + mvf, host int16 [ceil(Ho / 16),
@@ -698,6 +723,8 @@ class FrameStylizer(object):
         if self._tslots is None or "subpel" not in self.temporal:
             raise L.FaststyleError("motion_vectors_subpel: this stylizer was built without temporal subpel=")
         mv = self.motion_vectors()                               # (refuses a lane that has not run a frame)
+        if self._twork is not None:
+            return 4 * mv.astype(np.int16) + self._batch_vectors()[1].astype(np.int16)
         mvf = np.array(self.eng.mem.to_numpy(self._tslots[(self._tn - 1) & 1][-1]), dtype=np.uint8, copy=True).view(np.int8)
         return 4 * mv.astype(np.int16) + mvf.astype(np.int16)
 
@@ -775,7 +802,8 @@ class PipelinedStylizer(object):
     frame parity (with depth 3 a lane meets both), and frame n's tail waits, between its head's and its tail's replay, for an event recorded
     right behind frame n - 1's tail on the other lane's stream; the forward passes of two frames still overlap, and frame n + 1 overwrites
     the slot frame n reads only behind that chain.  Results equal the one-lane results, in order, for any depth.  reset() forgets the
-    previous frame and is allowed with nothing in flight."""
+    previous frame and is allowed with nothing in flight.  With temporal sequence=True and batch=N all of this goes by pass of N frames; every
+    lane has its own work buffer."""
 
     def __init__(self, eng, variables, height, width, depth=2, jpeg_threads=4, **kw):
         if not hasattr(eng.mem, "torch"):

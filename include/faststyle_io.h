@@ -444,7 +444,7 @@ int fs_compose_f32(fs_ctx* ctx, const float* src, int H, int W, const float* net
  * towards the previous frame's stabilised output, three launches behind the forward pass (or fs_compose_f32).  The arithmetic below is the
  * contract (tests/test_temporal.py restates it in numpy and compares for equality); it is integer throughout, on compose's unsigned 8.8 scale.
  *
- * Inputs, one image per call: src [H, W, 3] fp32, the net's input; cur [Ho, Wo, 3] fp32, the net's output or the composed tensor, H <= Ho <=
+ * Inputs, one image per call (N consecutive frames per call: fs_temporal_batch_f32 below): src [H, W, 3] fp32, the net's input; cur [Ho, Wo, 3] fp32, the net's output or the composed tensor, H <= Ho <=
  * H + 3 and W <= Wo <= W + 3, aligned top-left.  to88 is compose's.  clampy(v) = min(max(v, 0), Ho - 1), clampx likewise with Wo.
  *
  *   luma       cur8 [Ho, Wo] u8: A_c = to88(src[min(y, H - 1)][min(x, W - 1)][c]); Y = (k0 A_0 + k1 A_1 + k2 A_2 + 32768) >> 16 in int64 with
@@ -503,8 +503,8 @@ int fs_temporal_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cu
  *   blend      as above, with the vectors held to R (2^L - 1) instead of R before q is clamped.
  * Reach: a vector can be as long as R (2^L - 1), but motion is reliably found only where the coarsest level sees it, about R 2^(L-1) pixels:
  * 14 at L = 2, 28 at L = 3 (at L = 3 a move by (20, -33) is mostly lost, since -33 / 4 lies outside 7).  Not provided: L above 3 (the coarsest
- * level of a small frame becomes one ragged block), a second zero-vector predictor per level, smoothing of the vector field, batches
- * (sub-pixel vectors, which stood in this list: fs_temporal_sub_f32 below). */
+ * level of a small frame becomes one ragged block), a second zero-vector predictor per level, smoothing of the vector field
+ * (sub-pixel vectors and batches, which stood in this list: fs_temporal_sub_f32 and fs_temporal_batch_f32 below). */
 
 #define FS_TEMPORAL_MAX_LEVELS 3
 
@@ -566,8 +566,8 @@ int fs_temporal_pyr_f32(fs_ctx* ctx, const float* src, int H, int W, const float
  * and is then fetched a fraction away (a ragged block of one row takes (2, 0) and fetches the same row twice: no change).  Known property:
  * under steady fractional motion the state is resampled bilinearly on every frame, so at strength 1 and full confidence the stabilised
  * picture softens over time; below 1 the current frame re-injects its detail.
- * Not provided: smoothing of the vectors, a sharper (bicubic) fetch, fractions at coarse levels, batches (overlapped blocks and the smoothed
- * confidence, which stood in this list: fs_temporal_obmc_f32 below).
+ * Not provided: smoothing of the vectors, a sharper (bicubic) fetch, fractions at coarse levels (overlapped blocks, the smoothed confidence
+ * and batches, which stood in this list: fs_temporal_obmc_f32 and fs_temporal_batch_f32 below).
  *
  * mvf [nby, nbx, 2] signed char is written for inspection (the next call does not read it).  With S > 0: fs_temporal_pyr_f32's launches, one
  * more for the refinement, and the bilinear blend in place of the whole-pixel one: 4 launches at L = 1, 6 at L = 2, 7 at L = 3.  mv is held to
@@ -612,7 +612,7 @@ int fs_temporal_sub_f32(fs_ctx* ctx, const float* src, int H, int W, const float
  *      for byte what it writes without it.
  *   5. strength_q8 256 on a still picture returns the first frame wherever the four candidates' vectors are (0, 0).
  * Not provided: a vector median or other smoothing of mv itself, windows wider than the four nearest blocks, overlap at coarse levels or in
- * the search, a bicubic fetch, batches.
+ * the search, a bicubic fetch (batches, which stood in this list: fs_temporal_batch_f32 below).
  *
  * overlap 0 is fs_temporal_sub_f32 term for term (subpel 0 with a null mvf included).  overlap 1 runs the same launches with the blend
  * replaced: 3 at L = 1, S = 0; 7 at L = 3, S = 2.  mv, mvf and the block indices are held to their bounds before any reaches an address.
@@ -622,6 +622,38 @@ int fs_temporal_obmc_f32(fs_ctx* ctx, const float* src, int H, int W, const floa
                          int radius, int levels, int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma,
                          const unsigned short* prev_out88, const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88,
                          unsigned char* pyr, signed char* mv, signed char* mvf, float* dst);
+
+/* ---- Batches of consecutive frames for the temporal stage (csrc/fs_temporal.hip): `frames` N in [1, 64] successive frames of one stream in
+ * one call, oldest first.  The arithmetic is that of the four blocks above and is not restated: the call writes bit for bit what N successive
+ * calls of fs_temporal_obmc_f32 with the same parameters write, frame 0 reading the prev_* state (all null: no previous frame -- zero vectors
+ * and F = B for frame 0 only), frame i > 0 the state frame i - 1 wrote.  luma / out88 / pyr / mv / mvf receive frame N - 1's state, which the
+ * next call reads as its prev_*; dst[i] is frame i's stabilised tensor; dst may be cur.  Only the blend is recursive, so luma, pyramid, every
+ * search level and the refinement run once over all frames (the frame is one more grid dimension) and the N blends follow in order: 2 + N
+ * launches at L = 1, S = 0; 6 + N at L = 3, S = 2.
+ *
+ * The state of the frames 0 .. N - 2 lives in `work` (device memory, 16-byte aligned, fs_temporal_batch_layout's work_bytes; nothing is kept
+ * in it between calls).  Its layout is private but for the vectors: frame i < N - 1 has mv [nby, nbx, 2] signed char at work + mv_offset +
+ * i mv_stride and, with subpel > 0, mvf at work + mvf_offset + i mvf_stride (frame N - 1's are in mv / mvf).  It holds two out88 frames
+ * whatever N is: a blend reads its predecessor's only.  With frames = 1 the call is fs_temporal_obmc_f32 term for term, work_bytes is 0 and
+ * work may be null.  No implicit padding: 4 int32, then uint64. */
+typedef struct fs_temporal_batch_info {
+    int32_t frames, levels, subpel, reserved;
+    uint64_t mv_offset, mv_stride, mvf_offset, mvf_stride, work_bytes;
+} fs_temporal_batch_info;
+
+/* Host only: no HIP call, no global state, no allocation.  Errors: -1 null info, Ho or Wo below 1, frames outside [1, 64]; -2 levels outside
+ * [1, 3], subpel outside [0, 2]. */
+int fs_temporal_batch_layout(int Ho, int Wo, int levels, int subpel, int frames, fs_temporal_batch_info* info);
+
+/* src [frames, H, W, 3], cur and dst [frames, Ho, Wo, 3] fp32.  The frame index comes from the grid and is bounded by `frames`; no value
+ * read from a tensor reaches an address except through the held vectors, as in the single-frame calls.  Asynchronous on the ctx stream,
+ * allocates nothing, can be captured into a hipGraph.  A refused call launches nothing.  Errors: those of fs_temporal_obmc_f32; -1 frames
+ * outside [1, 64]; with frames > 1: -1 null work or work_bytes below the layout's, -5 work not 16-byte aligned. */
+int fs_temporal_batch_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int frames, int strength_q8,
+                          int sensitivity, int radius, int levels, int subpel, int overlap, int matrix, int src_bgr,
+                          const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr, unsigned char* luma,
+                          unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf, void* work, size_t work_bytes,
+                          float* dst);
 
 /* ---- Resampling between fp32 tensors (csrc/fs_resample.hip): the net's (or composed, or stabilised) output at a delivery size, a deep
  * source's fp32 planes at the net's size; no u8 stage on either path.  The arithmetic below is the contract: it is Pillow's Image.resize on

@@ -55,6 +55,13 @@ the place of the resampling filter: a guided filter fits the stylized picture to
 1..8, default 2: the window; ``--guided_smoothness E``, 1..64 8-bit levels, default 4) and applies the fit to the full-size source, which the
 lane still holds, so that the source's edges return at the delivery resolution -- three launches in the place of one
 (faststyle_amd/stream.py, deliver guided=).  The luma weights follow --color_matrix / --video_matrix.  Without the flag nothing changes.
+
+Throughput: ``--video_batch N`` (1..64, with --video_in) sends N consecutive frames through the net per pass; with ``--temporal_strength`` the
+stage runs over the N frames in order (faststyle_amd/stream.py, temporal sequence=), so the results are those of the same lanes fed one
+frame at a time up to the net's own batch numerics.  A stream's last pass is padded by repeating its last frame and only the frames read
+are written.  Latency grows by N frames, so live pipes keep 1.  ``--precision bf16`` runs the net's mixed-precision path (resize-conv models
+only: not with --upsample_method deconv) with --frames_dir, --video_in and the camera.  Without the flags, or with ``--video_batch 1`` /
+``--precision fp32``, nothing changes.
 """
 import os
 import sys
@@ -135,6 +142,20 @@ def temporal_options(args, matrix='bt601'):
     if subpel is not None:
         opt = dict(opt, subpel=subpel)
     return opt if overlap is None else dict(opt, overlap=overlap)
+
+
+def batch_options(args):
+    """--video_batch / --precision -> (frames per pass, the lanes' bf16=).  The flags are absent from the namespace unless given.  A batch
+    outside [1, 64] or without --video_in, or bf16 for a deconv model, is a SystemExit here, before anything is loaded."""
+    batch = getattr(args, 'video_batch', None)
+    if batch is not None and not 1 <= batch <= 64:
+        raise SystemExit('--video_batch %d is outside [1, 64]' % batch)
+    if batch is not None and args.video_in is None:
+        raise SystemExit('--video_batch needs --video_in: it batches the consecutive frames of that stream')
+    bf16 = getattr(args, 'precision', 'fp32') == 'bf16'
+    if bf16 and args.upsample_method == 'deconv':
+        raise SystemExit('--precision bf16 does not take --upsample_method deconv: the mixed-precision path is for resize-conv models')
+    return batch or 1, bf16
 
 
 def delivery_options(args):
@@ -224,6 +245,7 @@ def run_frames_dir(args):
     temporal = temporal_options(args)
     delivery = delivery_options(args)
     guided = guided_options(args)
+    bf16 = batch_options(args)[1]
     first_size = None
     if delivery is not None or (compose is not None and 'mask' in compose and (args.frame_size or args.resolution) is None):
         try:
@@ -253,6 +275,8 @@ def run_frames_dir(args):
         kw = dict(kw, swap_rb=False, compose=compose)
     if temporal is not None:                                     # (a run of frames of another size builds a new stylizer: it starts over)
         kw = dict(kw, temporal=temporal)
+    if bf16:
+        kw = dict(kw, bf16=True)
 
     def save(n, img_out):
         if jpg:
@@ -355,12 +379,14 @@ def check_video_flags(args):
 def run_video(args):
     """--video_in [--video_out]: a YUV4MPEG2 stream through the pipelined lanes.  The driver reads frame i + 1 into the next lane's pinned buffer
     while frame i is on the device."""
+    import collections
     from faststyle_amd import _lib, engine, stream, y4m
     check_video_flags(args)
     compose = compose_options(args, args.video_matrix)
     temporal = temporal_options(args, args.video_matrix)
     delivery = delivery_options(args)
     guided = guided_options(args, args.video_matrix)
+    batch, bf16 = batch_options(args)
     frame_filter = getattr(args, 'frame_filter', None)
     to_stdout = args.video_out == '-'
     log = sys.stderr if to_stdout else sys.stdout
@@ -432,6 +458,12 @@ def run_video(args):
             kw.update(swap_rb=False, compose=compose)
         if temporal is not None:
             kw.update(temporal=temporal)
+        if bf16:
+            kw.update(bf16=True)
+        if batch > 1:                                                        # (the batch's images are consecutive frames: the stage is told so)
+            kw.update(batch=batch)
+            if temporal is not None:
+                kw.update(temporal=dict(temporal, sequence=True))
         depth = int(os.environ.get('FS_FRAMES_IN_FLIGHT', '2')) if hasattr(eng.mem, 'torch') else 1
         if depth > 1:
             st = stream.PipelinedStylizer(eng, variables, H, W, depth=depth, upsample_method=args.upsample_method, **kw)
@@ -459,7 +491,40 @@ def run_video(args):
 
         failed = None                                                        # a stream that breaks off: what was read is still written
         try:
-            if depth > 1:
+            if batch > 1:
+                # N frames per pass: the reader fills the [N, frame_bytes] buffer row by row; a last pass is padded with the last frame read
+                # and only its real frames are written
+                real = collections.deque()
+
+                def emit_pass(outs):
+                    for i in range(real.popleft()):
+                        emit(outs[i])
+
+                buf = None if depth > 1 else np.zeros((batch, fmt.frame_bytes), np.uint8)
+                more = True
+                while more:
+                    if depth > 1:
+                        if st.in_flight >= depth:
+                            emit_pass(st.fetch())
+                        buf = st.next_input()                                # [N, frame_bytes], pinned
+                    got = 0
+                    try:
+                        while got < batch and reader.read_frame_into(buf[got]):
+                            got += 1
+                    except y4m.Y4MError as e:
+                        failed = e
+                    more = got == batch
+                    if got == 0:
+                        break
+                    buf[got:] = buf[got - 1]
+                    real.append(got)
+                    if depth > 1:
+                        st.submit(buf)
+                    else:
+                        emit_pass(st(buf))
+                while depth > 1 and st.in_flight:
+                    emit_pass(st.fetch())
+            elif depth > 1:
                 while failed is None:
                     if st.in_flight >= depth:
                         emit(st.fetch())
@@ -508,6 +573,7 @@ def run_webcam(args):
     temporal = temporal_options(args)
     delivery = delivery_options(args)
     guided = guided_options(args)
+    bf16 = batch_options(args)[1]
     cap = cv2.VideoCapture(0)
     if args.resolution is not None:
         x_length, y_length = args.resolution
@@ -523,6 +589,8 @@ def run_webcam(args):
     print('Loading up model...')
     eng, variables = _load(args)
     more = dict(temporal=temporal) if temporal is not None else {}
+    if bf16:
+        more['bf16'] = True
     if guided is not None:
         more['source'] = dict(height=y_cam, width=x_cam)
     x_out, y_out = x_new, y_new
@@ -554,6 +622,7 @@ def run_webcam(args):
 def main(argv=None):
     args = setup_parser().parse_args(argv)
     check_video_flags(args)
+    batch_options(args)
     if args.video_in is not None:
         run_video(args)
     elif args.frames_dir is not None:

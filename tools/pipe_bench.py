@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the TFRecord input pipeline alone (decode threads + GPU resize + HBM shuffle queue) on
-synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode | frames_in | video [out.json [depth]] | resample [out.json]]
+synthetic COCO-like shards (640x480 JPEG quality 90).  usage: pipe_bench.py [n_images] [threads] [host | host_native | host_encode | frames_in | video [out.json [depth | batch]] | resample [out.json]]
 "frames_in": the frames-dir loop end to end (stylize_webcam.run_frames_dir, two frames in flight, --output_format jpg) at 720p over a directory of
 n JPEG frames: PIL decode against --input_decode native, and from 1080p sources PIL decode + PIL resize (--resolution) against native decode +
 device resize (--frame_size).  Every leg runs on the same device, legs alternate over the repeats, and a leg's rate is taken from the DIFFERENCE
@@ -44,6 +44,13 @@ profiles/video_resample.json with the digest of the kernel sources.
 scheme, data resident): 720 x 1280 -> 2160 x 3840 at radius 2 for an RGBX and an fp32 source, at radius 8, and the bicubic fs_resample_f32 of
 the same enlargement in the same run; and the 2160p raw-video loop with --frame_size 1280 720 --output_size source, resampled (bicubic) and
 with --output_guided, alternating in the one run; written to profiles/video_guided.json with the digest of the kernel sources.
+"video" with "batch" as the fifth argument (pipe_bench.py 1280 4 video profiles/video_batch.json batch): consecutive frames per pass.  (a) the
+device time per frame of one fs_temporal_batch_f32 call over 8 frames against 8 chained single-frame calls (Engine.temporal_f32, the path of a
+lane without sequence=), at 720p and 1080p for (levels, subpel, overlap) = (1, 0, 0) and (3, 2, 1): the graph-of-200 scheme with the data
+resident, the two alternating over three repeats.  (b) the raw-video loop over a 1080p 4:2:0 file at --video_batch 1 and 8, --precision fp32
+and bf16, without and with --temporal_strength 0.6: eight legs that alternate in the one run, rates from the difference between n and n / 4
+frames; written to profiles/video_batch.json with the digest of the kernel sources.  "video_batch_kernels" as the third argument runs the
+720p (3, 2, 1) graphs of (a) alone: under a kernel trace that run gives the kernels' shares.
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -318,6 +325,129 @@ def temporal_overlap_kernel_times(W=1280, H=720, launches=200, repeats=3):
         r["us"] = sorted(r["us_repeats"])[len(r["us_repeats"]) // 2]
         print("video: %8.1f us per 720p call (repeats: %s), %3.0f %% of the threads see one vector: %s" %
               (r["us"], ", ".join("%.1f" % u for u in r["us_repeats"]), 100 * r["shortcut_share"], name))
+    return res
+
+
+def temporal_batch_kernel_times(sizes=((720, 1280), (1080, 1920)), modes=((1, 0, 0), (3, 2, 1)), N=8, launches=200, repeats=3):
+    """-> dict of device microseconds per frame of the temporal stage over N consecutive frames at radius 7 by (size, levels, subpel, overlap):
+    'chained' N single-frame calls on two alternating slots (what a lane without sequence= runs), 'batched' one fs_temporal_batch_f32 call,
+    both reading the state a previous frame left; timed as kernel_times does (a graph of `launches` repetitions of the N frames), `repeats`
+    times with the two alternating.  The frames are one picture drifting by (1, -2) pixels per frame."""
+    eng = engine.Engine()
+    mem = eng.mem
+    res = {}
+    for H, W in sizes:
+        rng = np.random.default_rng(3)
+        small = rng.uniform(0, 255, (H // 8, W // 8, 3)).astype(np.float32)
+        a = np.ascontiguousarray(np.kron(small, np.ones((8, 8, 1), np.float32)) + rng.uniform(-4, 4, (H, W, 3)).astype(np.float32))
+        src = mem.from_numpy(np.stack([np.roll(a, (k, -2 * k), axis=(0, 1)) for k in range(1, N + 1)]))
+        first = mem.from_numpy(a[None])
+        cur = mem.from_numpy(rng.uniform(0, 255, (N, H, W, 3)).astype(np.float32))
+        dst = mem.empty((N, H, W, 3))
+        one = lambda t, i: mem.view(t, i * H * W * 3, (1, H, W, 3))
+        for levels, subpel, overlap in modes:
+            more = dict(dict(levels=levels), **dict(dict(subpel=subpel) if subpel else {}, **(dict(overlap=overlap) if overlap else {})))
+            kw = dict(more, strength_q8=154, sensitivity=16, src_bgr=True, radius=7)
+            slots = [eng.temporal_state(H, W, levels, subpel) for _ in range(2)]
+            work = eng.temporal_batch_work(H, W, N, levels, subpel)
+            eng.temporal_f32(first, one(cur, 0), one(dst, 0), slots[1], **kw)             # the state in front of frame 0 (N is even: slot 1 again)
+
+            def chained():
+                for i in range(N):
+                    eng.temporal_f32(one(src, i), one(cur, i), one(dst, i), slots[i & 1], prev=slots[(i - 1) & 1], **kw)
+
+            def batched():
+                eng.temporal_batch_f32(src, cur, dst, slots[0], work, prev=slots[1], **kw)
+
+            name = "%dp_levels_%d_subpel_%d_overlap_%d" % (H, levels, subpel, overlap)
+            per_call = (2 + levels + (levels > 1) + (subpel > 0))
+            r = res[name] = {"frames": N, "launches": {"chained": N * per_call, "batched": per_call - 1 + N},
+                             "chained_us_per_frame_repeats": [], "batched_us_per_frame_repeats": []}
+            for _ in range(repeats):
+                r["chained_us_per_frame_repeats"].append(kernel_timed(chained, launches) / N)
+                r["batched_us_per_frame_repeats"].append(kernel_timed(batched, launches) / N)
+            for k in ("chained", "batched"):
+                r[k + "_us_per_frame"] = sorted(r[k + "_us_per_frame_repeats"])[repeats // 2]
+            print("video_batch: %7.1f us per frame chained (%s), %7.1f batched (%s): %s" %
+                  (r["chained_us_per_frame"], ", ".join("%.1f" % u for u in r["chained_us_per_frame_repeats"]), r["batched_us_per_frame"],
+                   ", ".join("%.1f" % u for u in r["batched_us_per_frame_repeats"]), name), flush=True)
+    return res
+
+
+def video_batch(n, repeats=3, out_json=None):
+    """-> dict: temporal_batch_kernel_times and the eight legs of the 1080p raw-video loop; prints them and writes profiles/video_batch.json
+    (after the kernel times and after every repeat, so that a run that is cut short leaves what it measured)."""
+    import contextlib
+    import json
+    import shutil
+    from PIL import Image
+    from faststyle_amd import build as fsbuild
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import stylize_webcam
+    n = max(32, n // 32 * 32)
+    w, h = 1920, 1080
+    dst = out_json or os.path.join(root, "profiles", "video_batch.json")
+    res = {"frames": n, "frames_in_flight": 2, "host_threads": "1 driver", "host_cores": os.cpu_count(), "omp_num_threads": os.environ.get("OMP_NUM_THREADS"),
+           "video": "1080p 4:2:0 YUV4MPEG2 (full range, BT.601), file to file of 8-bit 4:2:0",
+           "method": "rate = (n - n/4) / (t(n) - t(n/4)), median of %d alternating repeats" % repeats, "source_digest": fsbuild.source_digest(),
+           "launch_count_estimate": {"N": 8, "levels": 3, "subpel": 2, "chained": 56, "batched": 14,
+                                     "note": "arithmetic of the launch counts, not a measurement: see stage_us_per_frame for the measurement"}}
+
+    def save():
+        with open(dst, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+    res["stage_us_per_frame"] = temporal_batch_kernel_times()
+    save()
+    d = tempfile.mkdtemp()
+    rng = np.random.default_rng(0)
+    base = rng.integers(0, 256, (135, 240, 3), dtype=np.uint8)
+    planes = []
+    for k in range(16):      # 16 distinct natural-ish frames (upsampled noise), reused; PIL's matrix, box-averaged chroma
+        ycc = np.asarray(Image.fromarray(np.roll(base, 5 * k, axis=1)).resize((w, h), Image.BICUBIC).convert("YCbCr"), np.uint16)
+        sub = (ycc[0::2, 0::2, 1:] + ycc[0::2, 1::2, 1:] + ycc[1::2, 0::2, 1:] + ycc[1::2, 1::2, 1:] + 2) >> 2
+        planes.append(b"FRAME\n" + ycc[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 1].astype(np.uint8).tobytes())
+    for count in (n, n // 4):
+        with open(os.path.join(d, "1080p_%d.y4m" % count), "wb") as f:
+            f.write(b"YUV4MPEG2 W%d H%d F30:1 Ip A1:1 C420jpeg XCOLORRANGE=FULL\n" % (w, h))
+            for k in range(count):
+                f.write(planes[k % 16])
+    parser = stylize_webcam.setup_parser()
+    out = os.path.join(d, "out.y4m")
+    legs = [("video_y4m_1080p_batch_%d_%s%s" % (b, p, "_temporal_strength_0.6" if t else ""),
+             ["--video_batch", str(b), "--precision", p] + (["--temporal_strength", "0.6"] if t else []))
+            for t in (False, True) for p in ("fp32", "bf16") for b in (1, 8)]
+
+    def run(count, flags):
+        args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--video_in", os.path.join(d, "1080p_%d.y4m" % count),
+                                  "--video_out", out] + flags)
+        with contextlib.redirect_stdout(io.StringIO()):
+            t0 = time.time()
+            stylize_webcam.run_video(args)
+            dt = time.time() - t0
+        assert os.path.getsize(out) > count * w * h * 3 // 2
+        os.remove(out)
+        return dt
+
+    run(n // 4, [])                                               # warm-up: library load, first kernels
+    times = {name: [] for name, _ in legs}
+    res["legs"] = {}
+    try:
+        for _ in range(repeats):                                  # legs alternate: a drifting clock touches all of them alike
+            for name, flags in legs:
+                times[name].append((run(n, flags), run(n // 4, flags)))
+                print("video_batch: %s: %.2f s for %d frames, %.2f s for %d" % ((name,) + (times[name][-1][0], n, times[name][-1][1], n // 4)), flush=True)
+            for name, _ in legs:
+                rates = sorted((n - n // 4) / (a - b) for a, b in times[name])
+                res["legs"][name] = {"frames_per_s": rates[len(rates) // 2], "all_repeats": rates, "seconds_n_and_quarter": times[name]}
+            save()
+    finally:
+        shutil.rmtree(d)
+    for name, _ in legs:
+        r = res["legs"][name]
+        print("video_batch: %7.0f frames/s %s (repeats: %s)" % (r["frames_per_s"], name, ", ".join("%.0f" % v for v in r["all_repeats"])))
     return res
 
 
@@ -599,6 +729,12 @@ def main():
     from PIL import Image
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     threads = int(sys.argv[2]) if len(sys.argv) > 2 else None
+    if len(sys.argv) > 5 and sys.argv[3] == "video" and sys.argv[5] == "batch":
+        video_batch(n, out_json=sys.argv[4])
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "video_batch_kernels":
+        temporal_batch_kernel_times(sizes=((720, 1280),), modes=((3, 2, 1),), repeats=1)
+        return
     if len(sys.argv) > 3 and sys.argv[3] in ("frames_in", "video"):
         fifth = sys.argv[5] if len(sys.argv) > 5 and sys.argv[3] == "video" else None
         frames_in(n, out_json=sys.argv[4] if len(sys.argv) > 4 else None, video=sys.argv[3] == "video",
