@@ -240,173 +240,84 @@ int fs_compose_f32(fs_ctx* ctx, const float* src, int H, int W, const float* net
     const int rc = fs::compose_f32(src, H, W, net, Ho, Wo, N, strength_q8, keep_color ? 1 : 0, matrix, bgr & 1, bgr >> 1, mask, dst, ctx->stream);
     return rc ? fail(rc, "fs_compose_f32: launch failed (%d)", rc) : 0;
 }
+// The checks of every fs_temporal_*_f32 entry point, once: fn is the called function's name, c its arguments with the options its signature
+// lacks at their defaults (levels 1, subpel 0, overlap 0, frames 1, null buffers), which pass their checks -- so a narrower function checks
+// what it always did, in the same order.
+static int temporal_check(const char* fn, const fs_ctx* ctx, const fs::TemporalCall& c) {
+    if (!ctx || !c.src || !c.cur || !c.luma || !c.out88 || !c.mv || !c.dst) return fail(-1, "%s: null argument", fn);
+    if ((c.prev_luma == nullptr) != (c.prev_out88 == nullptr))
+        return fail(-1, "%s: prev_luma and prev_out88 are both given or both null (no previous frame)", fn);
+    if (c.prev_luma == c.luma || c.prev_out88 == c.out88)
+        return fail(-1, "%s: the previous frame's state is read at displaced positions and cannot be the state written", fn);
+    if (c.H < 1 || c.W < 1 || c.Ho < c.H || c.Ho - c.H > 3 || c.Wo < c.W || c.Wo - c.W > 3)
+        return fail(-1, "%s: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", fn, c.H, c.W, c.Ho, c.Wo);
+    if (c.strength_q8 < 0 || c.strength_q8 > 256) return fail(-2, "%s: strength_q8 must be in [0, 256], got %d", fn, c.strength_q8);
+    if (c.sensitivity < 1 || c.sensitivity > 256) return fail(-2, "%s: sensitivity must be in [1, 256], got %d", fn, c.sensitivity);
+    if (c.radius < 0 || c.radius > 7) return fail(-2, "%s: radius must be in [0, 7], got %d", fn, c.radius);
+    if (c.levels < 1 || c.levels > FS_TEMPORAL_MAX_LEVELS) return fail(-2, "%s: levels must be in [1, %d], got %d", fn, FS_TEMPORAL_MAX_LEVELS, c.levels);
+    if (c.subpel < 0 || c.subpel > 2) return fail(-2, "%s: subpel must be 0 (whole), 1 (half) or 2 (quarter pixels), got %d", fn, c.subpel);
+    if (c.overlap < 0 || c.overlap > 1) return fail(-2, "%s: overlap must be 0 (whole blocks) or 1 (the four nearest blocks), got %d", fn, c.overlap);
+    if (c.matrix != 0 && c.matrix != 1) return fail(-2, "%s: matrix must be 0 (BT.601) or 1 (BT.709), got %d", fn, c.matrix);
+    if (c.src_bgr != 0 && c.src_bgr != 1) return fail(-2, "%s: src_bgr must be 0 or 1, got %d", fn, c.src_bgr);
+    if (c.subpel > 0 && !c.mvf) return fail(-1, "%s: null mvf with subpel %d", fn, c.subpel);
+    if (c.levels > 1) {
+        if (!c.pyr) return fail(-1, "%s: null pyr with %d levels", fn, c.levels);
+        if ((c.prev_pyr == nullptr) != (c.prev_luma == nullptr))
+            return fail(-1, "%s: with %d levels prev_pyr is given exactly when prev_luma and prev_out88 are", fn, c.levels);
+        if (c.prev_pyr == c.pyr) return fail(-1, "%s: the previous frame's pyramid cannot be the one written", fn);
+    }
+    if (((uintptr_t)c.src | (uintptr_t)c.cur | (uintptr_t)c.dst) & 3) return fail(-5, "%s: src, cur and dst must be 4-byte aligned", fn);
+    if (((uintptr_t)c.prev_out88 | (uintptr_t)c.out88) & 1) return fail(-5, "%s: prev_out88 and out88 must be 2-byte aligned", fn);
+    if (c.frames < 1 || c.frames > 64) return fail(-1, "%s: frames must be in [1, 64], got %d", fn, c.frames);
+    if (c.frames > 1) {
+        fs_temporal_batch_info blay;
+        if (fs_temporal_batch_layout(c.Ho, c.Wo, c.levels, c.subpel, c.frames, &blay)) return -1;   // (cannot happen: checked above; the message is its own)
+        if (!c.work || c.work_bytes < blay.work_bytes)
+            return fail(-1, "%s: %d frames need a work buffer of %llu bytes (fs_temporal_batch_layout), got %s of %llu", fn, c.frames,
+                        (unsigned long long)blay.work_bytes, c.work ? "one" : "null", (unsigned long long)c.work_bytes);
+        if ((uintptr_t)c.work & 15) return fail(-5, "%s: work must be 16-byte aligned", fn);
+    }
+    return 0;
+}
+static int temporal_call(const char* fn, fs_ctx* ctx, const fs::TemporalCall& c) {
+    if (const int refused = temporal_check(fn, ctx, c)) return refused;
+    const int rc = fs::temporal_run(c, ctx->stream);
+    return rc ? fail(rc, "%s: launch failed (%d)", fn, rc) : 0;
+}
+// (the initialisers below are in TemporalCall's order, which is fs_temporal_batch_f32's argument order)
 int fs_temporal_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius,
                     int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma,
                     unsigned short* out88, signed char* mv, float* dst) {
-    if (!ctx || !src || !cur || !luma || !out88 || !mv || !dst) return fail(-1, "fs_temporal_f32: null argument");
-    if ((prev_luma == nullptr) != (prev_out88 == nullptr))
-        return fail(-1, "fs_temporal_f32: prev_luma and prev_out88 are both given or both null (no previous frame)");
-    if (prev_luma == luma || prev_out88 == out88)
-        return fail(-1, "fs_temporal_f32: the previous frame's state is read at displaced positions and cannot be the state written");
-    if (H < 1 || W < 1 || Ho < H || Ho - H > 3 || Wo < W || Wo - W > 3)
-        return fail(-1, "fs_temporal_f32: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", H, W, Ho, Wo);
-    if (strength_q8 < 0 || strength_q8 > 256) return fail(-2, "fs_temporal_f32: strength_q8 must be in [0, 256], got %d", strength_q8);
-    if (sensitivity < 1 || sensitivity > 256) return fail(-2, "fs_temporal_f32: sensitivity must be in [1, 256], got %d", sensitivity);
-    if (radius < 0 || radius > 7) return fail(-2, "fs_temporal_f32: radius must be in [0, 7], got %d", radius);
-    if (matrix != 0 && matrix != 1) return fail(-2, "fs_temporal_f32: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
-    if (src_bgr != 0 && src_bgr != 1) return fail(-2, "fs_temporal_f32: src_bgr must be 0 or 1, got %d", src_bgr);
-    if (((uintptr_t)src | (uintptr_t)cur | (uintptr_t)dst) & 3) return fail(-5, "fs_temporal_f32: src, cur and dst must be 4-byte aligned");
-    if (((uintptr_t)prev_out88 | (uintptr_t)out88) & 1) return fail(-5, "fs_temporal_f32: prev_out88 and out88 must be 2-byte aligned");
-    const int rc = fs::temporal_f32(src, H, W, cur, Ho, Wo, strength_q8, sensitivity, radius, matrix, src_bgr, prev_luma, prev_out88, luma, out88, mv,
-                                    dst, ctx->stream);
-    return rc ? fail(rc, "fs_temporal_f32: launch failed (%d)", rc) : 0;
+    return temporal_call("fs_temporal_f32", ctx, {src, H, W, cur, Ho, Wo, 1, strength_q8, sensitivity, radius, 1, 0, 0, matrix, src_bgr, prev_luma,
+                                                  prev_out88, nullptr, luma, out88, nullptr, mv, nullptr, nullptr, 0, dst});
 }
 int fs_temporal_pyr_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius,
                         int levels, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
                         const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, float* dst) {
-    if (!ctx || !src || !cur || !luma || !out88 || !mv || !dst) return fail(-1, "fs_temporal_pyr_f32: null argument");
-    if ((prev_luma == nullptr) != (prev_out88 == nullptr))
-        return fail(-1, "fs_temporal_pyr_f32: prev_luma and prev_out88 are both given or both null (no previous frame)");
-    if (prev_luma == luma || prev_out88 == out88)
-        return fail(-1, "fs_temporal_pyr_f32: the previous frame's state is read at displaced positions and cannot be the state written");
-    if (H < 1 || W < 1 || Ho < H || Ho - H > 3 || Wo < W || Wo - W > 3)
-        return fail(-1, "fs_temporal_pyr_f32: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", H, W, Ho, Wo);
-    if (strength_q8 < 0 || strength_q8 > 256) return fail(-2, "fs_temporal_pyr_f32: strength_q8 must be in [0, 256], got %d", strength_q8);
-    if (sensitivity < 1 || sensitivity > 256) return fail(-2, "fs_temporal_pyr_f32: sensitivity must be in [1, 256], got %d", sensitivity);
-    if (radius < 0 || radius > 7) return fail(-2, "fs_temporal_pyr_f32: radius must be in [0, 7], got %d", radius);
-    if (levels < 1 || levels > FS_TEMPORAL_MAX_LEVELS)
-        return fail(-2, "fs_temporal_pyr_f32: levels must be in [1, %d], got %d", FS_TEMPORAL_MAX_LEVELS, levels);
-    if (matrix != 0 && matrix != 1) return fail(-2, "fs_temporal_pyr_f32: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
-    if (src_bgr != 0 && src_bgr != 1) return fail(-2, "fs_temporal_pyr_f32: src_bgr must be 0 or 1, got %d", src_bgr);
-    if (levels > 1) {
-        if (!pyr) return fail(-1, "fs_temporal_pyr_f32: null pyr with %d levels", levels);
-        if ((prev_pyr == nullptr) != (prev_luma == nullptr))
-            return fail(-1, "fs_temporal_pyr_f32: with %d levels prev_pyr is given exactly when prev_luma and prev_out88 are", levels);
-        if (prev_pyr == pyr) return fail(-1, "fs_temporal_pyr_f32: the previous frame's pyramid cannot be the one written");
-    }
-    if (((uintptr_t)src | (uintptr_t)cur | (uintptr_t)dst) & 3) return fail(-5, "fs_temporal_pyr_f32: src, cur and dst must be 4-byte aligned");
-    if (((uintptr_t)prev_out88 | (uintptr_t)out88) & 1) return fail(-5, "fs_temporal_pyr_f32: prev_out88 and out88 must be 2-byte aligned");
-    fs_temporal_pyr_info lay;
-    if (fs_temporal_pyr_layout(Ho, Wo, levels, &lay)) return -1;                    // (cannot happen: checked above; the message is its own)
-    const int rc = fs::temporal_pyr_f32(lay, src, H, W, cur, strength_q8, sensitivity, radius, matrix, src_bgr, prev_luma, prev_out88, prev_pyr, luma,
-                                        out88, pyr, mv, dst, ctx->stream);
-    return rc ? fail(rc, "fs_temporal_pyr_f32: launch failed (%d)", rc) : 0;
+    return temporal_call("fs_temporal_pyr_f32", ctx, {src, H, W, cur, Ho, Wo, 1, strength_q8, sensitivity, radius, levels, 0, 0, matrix, src_bgr,
+                                                      prev_luma, prev_out88, prev_pyr, luma, out88, pyr, mv, nullptr, nullptr, 0, dst});
 }
 int fs_temporal_sub_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius,
                         int levels, int subpel, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
                         const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv,
                         signed char* mvf, float* dst) {
-    if (!ctx || !src || !cur || !luma || !out88 || !mv || !dst) return fail(-1, "fs_temporal_sub_f32: null argument");
-    if ((prev_luma == nullptr) != (prev_out88 == nullptr))
-        return fail(-1, "fs_temporal_sub_f32: prev_luma and prev_out88 are both given or both null (no previous frame)");
-    if (prev_luma == luma || prev_out88 == out88)
-        return fail(-1, "fs_temporal_sub_f32: the previous frame's state is read at displaced positions and cannot be the state written");
-    if (H < 1 || W < 1 || Ho < H || Ho - H > 3 || Wo < W || Wo - W > 3)
-        return fail(-1, "fs_temporal_sub_f32: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", H, W, Ho, Wo);
-    if (strength_q8 < 0 || strength_q8 > 256) return fail(-2, "fs_temporal_sub_f32: strength_q8 must be in [0, 256], got %d", strength_q8);
-    if (sensitivity < 1 || sensitivity > 256) return fail(-2, "fs_temporal_sub_f32: sensitivity must be in [1, 256], got %d", sensitivity);
-    if (radius < 0 || radius > 7) return fail(-2, "fs_temporal_sub_f32: radius must be in [0, 7], got %d", radius);
-    if (levels < 1 || levels > FS_TEMPORAL_MAX_LEVELS)
-        return fail(-2, "fs_temporal_sub_f32: levels must be in [1, %d], got %d", FS_TEMPORAL_MAX_LEVELS, levels);
-    if (subpel < 0 || subpel > 2) return fail(-2, "fs_temporal_sub_f32: subpel must be 0 (whole), 1 (half) or 2 (quarter pixels), got %d", subpel);
-    if (matrix != 0 && matrix != 1) return fail(-2, "fs_temporal_sub_f32: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
-    if (src_bgr != 0 && src_bgr != 1) return fail(-2, "fs_temporal_sub_f32: src_bgr must be 0 or 1, got %d", src_bgr);
-    if (subpel > 0 && !mvf) return fail(-1, "fs_temporal_sub_f32: null mvf with subpel %d", subpel);
-    if (levels > 1) {
-        if (!pyr) return fail(-1, "fs_temporal_sub_f32: null pyr with %d levels", levels);
-        if ((prev_pyr == nullptr) != (prev_luma == nullptr))
-            return fail(-1, "fs_temporal_sub_f32: with %d levels prev_pyr is given exactly when prev_luma and prev_out88 are", levels);
-        if (prev_pyr == pyr) return fail(-1, "fs_temporal_sub_f32: the previous frame's pyramid cannot be the one written");
-    }
-    if (((uintptr_t)src | (uintptr_t)cur | (uintptr_t)dst) & 3) return fail(-5, "fs_temporal_sub_f32: src, cur and dst must be 4-byte aligned");
-    if (((uintptr_t)prev_out88 | (uintptr_t)out88) & 1) return fail(-5, "fs_temporal_sub_f32: prev_out88 and out88 must be 2-byte aligned");
-    fs_temporal_pyr_info lay;
-    if (fs_temporal_pyr_layout(Ho, Wo, levels, &lay)) return -1;                    // (cannot happen: checked above; the message is its own)
-    const int rc = fs::temporal_sub_f32(lay, src, H, W, cur, strength_q8, sensitivity, radius, subpel, matrix, src_bgr, prev_luma, prev_out88, prev_pyr,
-                                        luma, out88, pyr, mv, mvf, dst, ctx->stream);
-    return rc ? fail(rc, "fs_temporal_sub_f32: launch failed (%d)", rc) : 0;
+    return temporal_call("fs_temporal_sub_f32", ctx, {src, H, W, cur, Ho, Wo, 1, strength_q8, sensitivity, radius, levels, subpel, 0, matrix, src_bgr,
+                                                      prev_luma, prev_out88, prev_pyr, luma, out88, pyr, mv, mvf, nullptr, 0, dst});
 }
 int fs_temporal_obmc_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius,
                          int levels, int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
                          const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv,
                          signed char* mvf, float* dst) {
-    if (!ctx || !src || !cur || !luma || !out88 || !mv || !dst) return fail(-1, "fs_temporal_obmc_f32: null argument");
-    if ((prev_luma == nullptr) != (prev_out88 == nullptr))
-        return fail(-1, "fs_temporal_obmc_f32: prev_luma and prev_out88 are both given or both null (no previous frame)");
-    if (prev_luma == luma || prev_out88 == out88)
-        return fail(-1, "fs_temporal_obmc_f32: the previous frame's state is read at displaced positions and cannot be the state written");
-    if (H < 1 || W < 1 || Ho < H || Ho - H > 3 || Wo < W || Wo - W > 3)
-        return fail(-1, "fs_temporal_obmc_f32: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", H, W, Ho, Wo);
-    if (strength_q8 < 0 || strength_q8 > 256) return fail(-2, "fs_temporal_obmc_f32: strength_q8 must be in [0, 256], got %d", strength_q8);
-    if (sensitivity < 1 || sensitivity > 256) return fail(-2, "fs_temporal_obmc_f32: sensitivity must be in [1, 256], got %d", sensitivity);
-    if (radius < 0 || radius > 7) return fail(-2, "fs_temporal_obmc_f32: radius must be in [0, 7], got %d", radius);
-    if (levels < 1 || levels > FS_TEMPORAL_MAX_LEVELS)
-        return fail(-2, "fs_temporal_obmc_f32: levels must be in [1, %d], got %d", FS_TEMPORAL_MAX_LEVELS, levels);
-    if (subpel < 0 || subpel > 2) return fail(-2, "fs_temporal_obmc_f32: subpel must be 0 (whole), 1 (half) or 2 (quarter pixels), got %d", subpel);
-    if (overlap < 0 || overlap > 1) return fail(-2, "fs_temporal_obmc_f32: overlap must be 0 (whole blocks) or 1 (the four nearest blocks), got %d", overlap);
-    if (matrix != 0 && matrix != 1) return fail(-2, "fs_temporal_obmc_f32: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
-    if (src_bgr != 0 && src_bgr != 1) return fail(-2, "fs_temporal_obmc_f32: src_bgr must be 0 or 1, got %d", src_bgr);
-    if (subpel > 0 && !mvf) return fail(-1, "fs_temporal_obmc_f32: null mvf with subpel %d", subpel);
-    if (levels > 1) {
-        if (!pyr) return fail(-1, "fs_temporal_obmc_f32: null pyr with %d levels", levels);
-        if ((prev_pyr == nullptr) != (prev_luma == nullptr))
-            return fail(-1, "fs_temporal_obmc_f32: with %d levels prev_pyr is given exactly when prev_luma and prev_out88 are", levels);
-        if (prev_pyr == pyr) return fail(-1, "fs_temporal_obmc_f32: the previous frame's pyramid cannot be the one written");
-    }
-    if (((uintptr_t)src | (uintptr_t)cur | (uintptr_t)dst) & 3) return fail(-5, "fs_temporal_obmc_f32: src, cur and dst must be 4-byte aligned");
-    if (((uintptr_t)prev_out88 | (uintptr_t)out88) & 1) return fail(-5, "fs_temporal_obmc_f32: prev_out88 and out88 must be 2-byte aligned");
-    fs_temporal_pyr_info lay;
-    if (fs_temporal_pyr_layout(Ho, Wo, levels, &lay)) return -1;                    // (cannot happen: checked above; the message is its own)
-    const int rc = fs::temporal_obmc_f32(lay, src, H, W, cur, strength_q8, sensitivity, radius, subpel, overlap, matrix, src_bgr, prev_luma, prev_out88,
-                                         prev_pyr, luma, out88, pyr, mv, mvf, dst, ctx->stream);
-    return rc ? fail(rc, "fs_temporal_obmc_f32: launch failed (%d)", rc) : 0;
+    return temporal_call("fs_temporal_obmc_f32", ctx, {src, H, W, cur, Ho, Wo, 1, strength_q8, sensitivity, radius, levels, subpel, overlap, matrix,
+                                                       src_bgr, prev_luma, prev_out88, prev_pyr, luma, out88, pyr, mv, mvf, nullptr, 0, dst});
 }
 int fs_temporal_batch_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int frames, int strength_q8, int sensitivity,
                           int radius, int levels, int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma,
                           const unsigned short* prev_out88, const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88,
                           unsigned char* pyr, signed char* mv, signed char* mvf, void* work, size_t work_bytes, float* dst) {
-    if (!ctx || !src || !cur || !luma || !out88 || !mv || !dst) return fail(-1, "fs_temporal_batch_f32: null argument");
-    if ((prev_luma == nullptr) != (prev_out88 == nullptr))
-        return fail(-1, "fs_temporal_batch_f32: prev_luma and prev_out88 are both given or both null (no previous frame)");
-    if (prev_luma == luma || prev_out88 == out88)
-        return fail(-1, "fs_temporal_batch_f32: the previous frame's state is read at displaced positions and cannot be the state written");
-    if (H < 1 || W < 1 || Ho < H || Ho - H > 3 || Wo < W || Wo - W > 3)
-        return fail(-1, "fs_temporal_batch_f32: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", H, W, Ho, Wo);
-    if (strength_q8 < 0 || strength_q8 > 256) return fail(-2, "fs_temporal_batch_f32: strength_q8 must be in [0, 256], got %d", strength_q8);
-    if (sensitivity < 1 || sensitivity > 256) return fail(-2, "fs_temporal_batch_f32: sensitivity must be in [1, 256], got %d", sensitivity);
-    if (radius < 0 || radius > 7) return fail(-2, "fs_temporal_batch_f32: radius must be in [0, 7], got %d", radius);
-    if (levels < 1 || levels > FS_TEMPORAL_MAX_LEVELS)
-        return fail(-2, "fs_temporal_batch_f32: levels must be in [1, %d], got %d", FS_TEMPORAL_MAX_LEVELS, levels);
-    if (subpel < 0 || subpel > 2) return fail(-2, "fs_temporal_batch_f32: subpel must be 0 (whole), 1 (half) or 2 (quarter pixels), got %d", subpel);
-    if (overlap < 0 || overlap > 1) return fail(-2, "fs_temporal_batch_f32: overlap must be 0 (whole blocks) or 1 (the four nearest blocks), got %d", overlap);
-    if (matrix != 0 && matrix != 1) return fail(-2, "fs_temporal_batch_f32: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
-    if (src_bgr != 0 && src_bgr != 1) return fail(-2, "fs_temporal_batch_f32: src_bgr must be 0 or 1, got %d", src_bgr);
-    if (subpel > 0 && !mvf) return fail(-1, "fs_temporal_batch_f32: null mvf with subpel %d", subpel);
-    if (levels > 1) {
-        if (!pyr) return fail(-1, "fs_temporal_batch_f32: null pyr with %d levels", levels);
-        if ((prev_pyr == nullptr) != (prev_luma == nullptr))
-            return fail(-1, "fs_temporal_batch_f32: with %d levels prev_pyr is given exactly when prev_luma and prev_out88 are", levels);
-        if (prev_pyr == pyr) return fail(-1, "fs_temporal_batch_f32: the previous frame's pyramid cannot be the one written");
-    }
-    if (((uintptr_t)src | (uintptr_t)cur | (uintptr_t)dst) & 3) return fail(-5, "fs_temporal_batch_f32: src, cur and dst must be 4-byte aligned");
-    if (((uintptr_t)prev_out88 | (uintptr_t)out88) & 1) return fail(-5, "fs_temporal_batch_f32: prev_out88 and out88 must be 2-byte aligned");
-    if (frames < 1 || frames > 64) return fail(-1, "fs_temporal_batch_f32: frames must be in [1, 64], got %d", frames);
-    fs_temporal_batch_info blay;
-    if (fs_temporal_batch_layout(Ho, Wo, levels, subpel, frames, &blay)) return -1;  // (cannot happen: checked above; the message is its own)
-    if (frames > 1) {
-        if (!work || work_bytes < blay.work_bytes)
-            return fail(-1, "fs_temporal_batch_f32: %d frames need a work buffer of %llu bytes (fs_temporal_batch_layout), got %s of %llu", frames,
-                        (unsigned long long)blay.work_bytes, work ? "one" : "null", (unsigned long long)work_bytes);
-        if ((uintptr_t)work & 15) return fail(-5, "fs_temporal_batch_f32: work must be 16-byte aligned");
-    }
-    fs_temporal_pyr_info lay;
-    if (fs_temporal_pyr_layout(Ho, Wo, levels, &lay)) return -1;                    // (cannot happen: checked above; the message is its own)
-    const int rc = frames == 1
-                       ? fs::temporal_obmc_f32(lay, src, H, W, cur, strength_q8, sensitivity, radius, subpel, overlap, matrix, src_bgr, prev_luma,
-                                               prev_out88, prev_pyr, luma, out88, pyr, mv, mvf, dst, ctx->stream)
-                       : fs::temporal_batch_f32(lay, src, H, W, cur, frames, strength_q8, sensitivity, radius, subpel, overlap, matrix, src_bgr, prev_luma,
-                                                prev_out88, prev_pyr, luma, out88, pyr, mv, mvf, static_cast<unsigned char*>(work), dst, ctx->stream);
-    return rc ? fail(rc, "fs_temporal_batch_f32: launch failed (%d)", rc) : 0;
+    return temporal_call("fs_temporal_batch_f32", ctx, {src, H, W, cur, Ho, Wo, frames, strength_q8, sensitivity, radius, levels, subpel, overlap,
+                                                        matrix, src_bgr, prev_luma, prev_out88, prev_pyr, luma, out88, pyr, mv, mvf,
+                                                        static_cast<unsigned char*>(work), work_bytes, dst});
 }
 int fs_resample_f32(fs_ctx* ctx, const fs_resample_info* plan, const void* tables_dev, const float* src, int src_rows, int src_pitch, int N, float* dst) {
     if (!ctx || !plan || !src || !dst) return fail(-1, "fs_resample_f32: null argument");

@@ -19,7 +19,6 @@ struct fs_jpeg_item;
 struct fs_jpegenc_item;
 struct fs_cvresize_info;
 struct fs_resample_info;
-struct fs_temporal_pyr_info;
 struct fs_yuv_desc;
 
 namespace fs {
@@ -695,33 +694,30 @@ int f32_to_yuv_deep(const ::fs_yuv_desc& desc, const float* src, int swap_rb, in
 // the net's output blended towards its input on the 8.8 scale (fs_compose.hip): the launch (argument checks are in fs_api.hip)
 int compose_f32(const float* src, int H, int W, const float* net, int Ho, int Wo, int N, int strength_q8, int keep_color, int matrix, int bgr,
                 int src_swap, const unsigned char* mask, float* dst, hipStream_t s);
-// temporal stabilisation (fs_temporal.hip): luma of the source, block-matching search against the previous luma, blend towards the previous
-// stabilised output along the vectors -- three launches (argument checks are in fs_api.hip)
-int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius, int matrix, int src_bgr,
-                 const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma, unsigned short* out88, signed char* mv,
-                 float* dst, hipStream_t s);
-// ... with the coarse-to-fine search over `levels` halved lumas: luma, pyramid (levels > 1), one predicted search per level, blend; `lay` is
-// what fs_temporal_pyr_layout fills for (Ho, Wo, levels)
-int temporal_pyr_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
-                     int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
-                     unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, float* dst, hipStream_t s);
-// ... with block vectors in half (subpel 1) or quarter pixels (2): the launches above up to the searches, the refinement that writes mvf, and
-// the bilinear blend; subpel 0 is temporal_pyr_f32 and leaves mvf alone
-int temporal_sub_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
-                     int subpel, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
-                     unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf, float* dst, hipStream_t s);
-// ... with overlapped block vectors (overlap 1): the same launches with the blend replaced by the one that weighs the vectors of the four
-// blocks around every pixel; overlap 0 is temporal_sub_f32
-int temporal_obmc_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
-                      int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
-                      const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf,
-                      float* dst, hipStream_t s);
-// ... over `frames` > 1 consecutive frames: luma, pyramid, every search level and the refinement once over all frames, then one blend per
-// frame in order; the frames before the last keep their state in `work` (fs_temporal_batch_layout's work_bytes, 16-byte aligned)
-int temporal_batch_f32(const ::fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int frames, int strength_q8, int sensitivity,
-                       int radius, int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
-                       const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf,
-                       unsigned char* work, float* dst, hipStream_t s);
+// temporal stabilisation (fs_temporal.hip): one call of any of the fs_temporal_*_f32 entry points, in the argument order of
+// fs_temporal_batch_f32.  An entry point without an option leaves it at levels 1, subpel 0, overlap 0, frames 1 and its buffer null (pyr and
+// prev_pyr, mvf, work).  fs_api.hip checks a call; temporal_run launches a checked one: luma, pyramid (levels > 1), one search per level,
+// the refinement that writes mvf (subpel > 0; mvf is not touched without it) -- each once over all frames --, then one blend per frame in
+// order.  The frames before the last keep their state in `work` (fs_temporal_batch_layout's work_bytes, 16-byte aligned; unused with one frame).
+struct TemporalCall {
+    const float* src;
+    int H, W;
+    const float* cur;
+    int Ho, Wo, frames;
+    int strength_q8, sensitivity, radius, levels, subpel, overlap, matrix, src_bgr;
+    const unsigned char* prev_luma;
+    const unsigned short* prev_out88;
+    const unsigned char* prev_pyr;
+    unsigned char* luma;
+    unsigned short* out88;
+    unsigned char* pyr;
+    signed char* mv;
+    signed char* mvf;
+    unsigned char* work;
+    size_t work_bytes;
+    float* dst;
+};
+int temporal_run(const TemporalCall& c, hipStream_t s);
 // resampling between fp32 tensors (fs_resample.hip): whether a plan is what fs_resample_plan fills, and the one launch (argument checks are in
 // fs_api.hip)
 bool resample_plan_ok(const ::fs_resample_info& plan);

@@ -1,24 +1,32 @@
-// Temporal stabilisation between the forward pass (or compose) and the output conversions (include/faststyle_io.h, whose comment is the
+// Temporal stabilisation between the forward pass (or compose) and the output conversions (include/faststyle_io.h, whose comments are the
 // arithmetic contract): a byte luma of the net's input on the output grid, a block-matching motion search between this luma and the previous
-// frame's, and a per-pixel blend of the new output towards the previous stabilised output fetched along the block's vector, weighted by how
-// well the source matched there.  faststyle_amd/stream.py (temporal=) keeps the two state slots and runs the three launches behind compose.
-//   luma   -- elementwise, the thread layout of compose_kernel: four pixels of an output row.
-//   search -- one workgroup of 256 threads per 16x16 block, one thread per candidate (dy, dx) in [-R, R]^2 (225 at R = 7).  The block's luma
-//             (16 rows of 16 bytes, zero outside the frame) and the previous luma's (16 + 2R)^2 window go to LDS with the clamped coordinates
-//             applied, so the inner loop has no bounds logic; a ragged block runs `rows` rows (uniform) and masks the window's dwords beyond
-//             `cols` (uniform), where the block's own bytes are zero already.  A candidate reads, per row, the five aligned dwords that hold
-//             its sixteen bytes, shifts them into place and adds four packed-byte SADs against the block's dwords (the same address in every
-//             lane: a broadcast).  Window pitch 32 bytes = 8 banks: the lanes of a 32-lane group are candidates of at most 4 consecutive dy
-//             (15 apart is one row down) and of dword columns 0 ... 3 + k, so they touch 4 rows x 8 banks, each bank once per distinct
-//             address -- conflict-free by the rule that ds_read_b32 banks are (a / 4) mod 32 per 32-lane half.  The 256 keys are reduced by an
-//             LDS min tree.
-//   blend  -- elementwise, four pixels of an output row (they lie in one block: one vector per thread).
-// No value read from a tensor reaches an address except through mv, which the search bounds by R and the blend clamps again together with
-// the displaced coordinates.  The arithmetic is integer throughout.
-// fs_temporal_pyr_f32 reaches further with the same pieces: a pyramid kernel halves the luma once or twice (elementwise, one launch), and the
-// search runs per level, coarsest first, on a window displaced by twice the coarser level's vector (temporal_search_pred_kernel: the search
-// above plus that predictor, which is held to its bound before it reaches an address); the blend is the one above with the larger bound.
-// fs_temporal_sub_f32 adds a fraction per block in quarter pixels and a bilinear fetch (the last part of this file).
+// frame's, and a per-pixel blend of the new output towards the previous stabilised output fetched along the block vectors, weighted by how
+// well the source matched there.  faststyle_amd/stream.py (temporal=) keeps the two state slots and runs the launches behind compose.
+// One pipeline with options (TemporalCall, fs_kernels.h), launched by temporal_run for every entry point of the header:
+//   luma    -- elementwise, the thread layout of compose_kernel: four pixels of an output row.
+//   pyramid -- levels > 1: halves the luma once or twice (elementwise, one launch).
+//   search  -- one launch per level, coarsest first, each on a window displaced by twice the coarser level's vector (held to its bound before
+//              it reaches an address).  One workgroup of 256 threads per 16x16 block, one thread per candidate (dy, dx) in [-R, R]^2 (225 at
+//              R = 7).  The block's luma (16 rows of 16 bytes, zero outside the frame) and the previous luma's (16 + 2R)^2 window go to LDS
+//              with the clamped coordinates applied, so the inner loop has no bounds logic; a ragged block runs `rows` rows (uniform) and
+//              masks the window's dwords beyond `cols` (uniform), where the block's own bytes are zero already.  A candidate reads, per row,
+//              the five aligned dwords that hold its sixteen bytes, shifts them into place and adds four packed-byte SADs against the block's
+//              dwords (the same address in every lane: a broadcast).  Window pitch 32 bytes = 8 banks: the lanes of a 32-lane group are
+//              candidates of at most 4 consecutive dy (15 apart is one row down) and of dword columns 0 ... 3 + k, so they touch 4 rows x 8
+//              banks, each bank once per distinct address -- conflict-free by the rule that ds_read_b32 banks are (a / 4) mod 32 per 32-lane
+//              half.  The 256 keys are reduced by an LDS min tree.
+//   subpel  -- subpel > 0: a fraction per block in quarter pixels from five SADs around the whole-pixel winner (described at the kernel).
+//   blend   -- one launch per frame, elementwise, four pixels of an output row.  One body in three instantiations: along the block's whole-pixel
+//              vector, along vector plus fraction with a bilinear fetch (subpel > 0), or along the vectors of the four blocks whose centres
+//              surround the pixel (overlap 1).
+// Frames: a call covers `frames` consecutive frames.  Only the blend is recursive, so the launches before it run once over all frames with the
+// frame index f as one more grid dimension (blockIdx.y of the luma's 1-D grid, blockIdx.z of the others).  A buffer of frame f lies in the work
+// buffer's slot f, except the last frame's, which is the state's (pointer selection, no copy launch); frame f's "previous" is slot f - 1, for
+// f = 0 the state the previous call wrote (null: no previous frame).  f is uniform per workgroup and held below `frames`, so the selection
+// stays in scalar registers.  The selection costs a call of one frame 0.2 to 0.3 us per launch, so luma, pyramid, search and
+// refinement are a body with two entries: *_kernel takes one frame's pointers (frames == 1: no work buffer), *_batch_kernel selects them.
+// No value read from a tensor reaches an address except through mv and mvf, which the search and the refinement bound and every reader holds
+// to those bounds again together with the displaced coordinates.  The arithmetic is integer throughout.
 #include <cstring>
 
 #include "../../include/faststyle_io.h"
@@ -32,11 +40,16 @@ constexpr int TB = 16;                      // block edge
 constexpr int TRMAX = 7;                    // largest search radius
 constexpr int TPITCH = 32;                  // bytes per LDS window row: 16 + 2 * 7 = 30 used, the five-dword read of column 14 ends at byte 31
 constexpr int TWROWS = TB + 2 * TRMAX;      // 30
+constexpr int SPITCH = 12;                  // dwords per LDS window row of the refinement: 5 used (18 bytes, the read of dword 4 ends at byte 19)
+constexpr int SWROWS = TB + 2;              // 18
 
 // the float on the 8.8 scale, as compose_kernel's: clamped to [0, 255] (NaN: 0), times 256 (exact), truncated
 __device__ __forceinline__ int temporal_f88(float v) { return (int)(fminf(fmaxf(v, 0.f), 255.f) * 256.0f); }
 
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// v held to [-bound, bound]
+__device__ __forceinline__ int hold_to(int v, int bound) { return v < -bound ? -bound : (v > bound ? bound : v); }
 
 // acc + the four absolute byte differences of a and b
 __device__ __forceinline__ unsigned sad4(unsigned a, unsigned b, unsigned acc) {
@@ -49,6 +62,29 @@ __device__ __forceinline__ unsigned sad4(unsigned a, unsigned b, unsigned acc) {
     }
     return acc;
 #endif
+}
+
+struct FrameSel {
+    unsigned char* work;                    // slot f at work + f * slot, f < frames - 1
+    unsigned long long slot;
+    int frames;
+};
+
+// one buffer of every frame: the last frame's (in the state written), frame 0's predecessor (in the state read, or null), the offset in a slot
+struct FrameBuf {
+    unsigned char* last;
+    const unsigned char* before;
+    unsigned long long off;
+};
+
+__device__ __forceinline__ unsigned char* frame_at(const FrameSel& S, const FrameBuf& B, int f) {
+    if (f == S.frames - 1) return B.last;
+    return S.work + (size_t)f * S.slot + B.off;
+}
+
+__device__ __forceinline__ const unsigned char* frame_before(const FrameSel& S, const FrameBuf& B, int f) {
+    if (f == 0) return B.before;
+    return S.work + (size_t)(f - 1) * S.slot + B.off;
 }
 
 struct LumaArgs {
@@ -80,148 +116,12 @@ __global__ __launch_bounds__(256) void temporal_luma_kernel(const LumaArgs A, co
     temporal_luma_body(A, src, luma);
 }
 
-// One workgroup per block (blockIdx.y, blockIdx.x).  prev == nullptr (no previous frame): every vector is (0, 0).
-__global__ __launch_bounds__(256) void temporal_search_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int Ho,
-                                                              int Wo, int R, signed char* __restrict__ mv) {
-    __shared__ unsigned win[TWROWS * (TPITCH / 4)];         // the previous luma's window, row pitch 8 dwords
-    __shared__ unsigned blk[TB * (TB / 4)];                 // the block's luma, 4 dwords per row, zero outside the frame
-    __shared__ unsigned keys[256];
-    const int t = (int)threadIdx.x;
-    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
-    signed char* out = mv + ((size_t)by * gridDim.x + bx) * 2;
-    if (prev8 == nullptr) {                                 // (uniform per launch)
-        if (t == 0) { out[0] = 0; out[1] = 0; }
-        return;
-    }
-    const int y0 = by * TB, x0 = bx * TB;
-    const int rows = Ho - y0 < TB ? Ho - y0 : TB, cols = Wo - x0 < TB ? Wo - x0 : TB;        // at least 1 each
-    const int n = 2 * R + 1;
-    if (t < (TB + 2 * R) * (TPITCH / 4)) {                  // window row t / 8, dword t % 8: frame rows y0 - R ..., columns x0 - R ...
-        const int wr = t >> 3, wc = (t & 7) * 4;
-        const unsigned char* prow = prev8 + (size_t)clampi(y0 - R + wr, Ho - 1) * Wo;
-        unsigned v = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) v |= (unsigned)prow[clampi(x0 - R + wc + b, Wo - 1)] << (8 * b);
-        win[t] = v;
-    }
-    if (t < TB * (TB / 4)) {                                // block row t / 4, dword t % 4
-        const int r = t >> 2, c = (t & 3) * 4;
-        unsigned v = 0;
-        if (r < rows) {
-            const unsigned char* crow = cur8 + (size_t)(y0 + r) * Wo + x0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (c + b < cols) v |= (unsigned)crow[c + b] << (8 * b);
-        }
-        blk[t] = v;
-    }
-    __syncthreads();
-    unsigned key = 0xFFFFFFFFu;
-    if (t < n * n) {
-        const int dyi = t / n, dxi = t - dyi * n;           // dy + R, dx + R: the window's row and column of the candidate's first pixel
-        const int dy = dyi - R, dx = dxi - R;
-        unsigned m[4];                                      // the bytes of dword k that lie inside the block
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int inside = cols - 4 * k;
-            m[k] = inside >= 4 ? 0xFFFFFFFFu : (inside <= 0 ? 0u : (1u << (8 * inside)) - 1u);
-        }
-        const int sh = (dxi & 3) * 8;
-        const unsigned* wp = win + dyi * (TPITCH / 4) + (dxi >> 2);          // (dxi >> 2) + 4 <= 7: inside the row
-        unsigned sad = 0;
-        for (int r = 0; r < rows; ++r) {
-            const unsigned* w = wp + r * (TPITCH / 4);
-            const unsigned* c = blk + r * 4;
-            unsigned lo = w[0];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const unsigned hi = w[k + 1];
-                const unsigned a = (unsigned)((((unsigned long long)hi << 32) | lo) >> sh);
-                sad = sad4(a & m[k], c[k], sad);
-                lo = hi;
-            }
-        }
-        const int mag = (dy < 0 ? -dy : dy) + (dx < 0 ? -dx : dx);
-        const unsigned cost = sad + (unsigned)(((rows * cols) >> 5) * mag);              // below 2^17
-        key = (cost << 12) | ((unsigned)mag << 8) | ((unsigned)(dy + 7) << 4) | (unsigned)(dx + 7);
-    }
-    keys[t] = key;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-            const unsigned a = keys[t], b = keys[t + s];
-            keys[t] = a < b ? a : b;
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        const unsigned k = keys[0];
-        out[0] = (signed char)((int)((k >> 4) & 15u) - 7);
-        out[1] = (signed char)((int)(k & 15u) - 7);
-    }
+__global__ __launch_bounds__(256) void temporal_luma_batch_kernel(const LumaArgs A, const FrameSel S, const FrameBuf L, const float* __restrict__ src) {
+    const int f = (int)blockIdx.y;
+    if (f >= S.frames) return;
+    temporal_luma_body(A, src + (size_t)f * A.H * A.W * 3, frame_at(S, L, f));
 }
 
-struct BlendArgs {
-    int Ho, Wo, nbx;
-    int strength_q8, sensitivity, R;
-};
-
-// Thread i: row y, pixels x0 ... x0 + 3 as in the luma kernel.  dst may be cur: a thread reads its own pixels before it writes them, and no
-// other thread reads them (hence no __restrict__ on the two).  prev8 / prev88 are read at displaced positions: they are not luma / out88.
-__global__ __launch_bounds__(256) void temporal_blend_kernel(const BlendArgs A, const float* cur, const unsigned char* __restrict__ cur8,
-                                                             const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
-                                                             const signed char* __restrict__ mv, float* dst, unsigned short* __restrict__ out88) {
-    const int groups = (A.Wo + 3) >> 2;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)groups * A.Ho) return;
-    const int y = (int)(i / groups), x0 = (int)(i - (long long)y * groups) * 4;
-    const size_t row = (size_t)y * A.Wo;
-    int qy = y, dx = 0;
-    if (prev8 != nullptr) {                                 // (uniform per launch)
-        const signed char* v = mv + ((size_t)(y >> 4) * A.nbx + (x0 >> 4)) * 2;
-        const int dy = (int)v[0] < -A.R ? -A.R : ((int)v[0] > A.R ? A.R : (int)v[0]);    // (the search wrote them within R; held to it again)
-        dx = (int)v[1] < -A.R ? -A.R : ((int)v[1] > A.R ? A.R : (int)v[1]);
-        qy = clampi(y + dy, A.Ho - 1);
-    }
-    const int n = A.Wo - x0 < 4 ? A.Wo - x0 : 4;
-    const size_t at0 = (row + x0) * 3;
-    float b[12];                                            // every read of cur before the first write of dst: the two may be one tensor
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int xn = k < n ? k : n - 1;                   // (beyond the row's end: the last pixel again, never stored)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) b[3 * k + c] = cur[at0 + 3 * xn + c];
-    }
-    int F[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int xn = x0 + (k < n ? k : n - 1);
-        const int B0 = temporal_f88(b[3 * k]), B1 = temporal_f88(b[3 * k + 1]), B2 = temporal_f88(b[3 * k + 2]);
-        F[3 * k] = B0; F[3 * k + 1] = B1; F[3 * k + 2] = B2;
-        if (prev8 != nullptr) {
-            const size_t q = (size_t)qy * A.Wo + clampi(xn + dx, A.Wo - 1);
-            const int d = (int)cur8[row + xn] - (int)prev8[q];
-            const int e = d < 0 ? -d : d;
-            const int conf = 256 - e * A.sensitivity;
-            const long long w = (long long)A.strength_q8 * (conf > 0 ? conf : 0);        // 0 ... 65536
-            const int P0 = prev88[q * 3], P1 = prev88[q * 3 + 1], P2 = prev88[q * 3 + 2];
-            F[3 * k] = B0 + (int)(((long long)(P0 - B0) * w + 32768) >> 16);
-            F[3 * k + 1] = B1 + (int)(((long long)(P1 - B1) * w + 32768) >> 16);
-            F[3 * k + 2] = B2 + (int)(((long long)(P2 - B2) * w + 32768) >> 16);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k < n) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                dst[at0 + 3 * k + c] = (float)F[3 * k + c] * 0.00390625f;
-                out88[at0 + 3 * k + c] = (unsigned short)F[3 * k + c];
-            }
-        }
-}
-
-// ---- the coarse-to-fine search (fs_temporal_pyr_f32): a pyramid of halved lumas and the search above with a displaced window, per level
 struct PyrArgs {
     int H0, W0, H1, W1;
     int H2, W2;                             // 0, 0 with two levels
@@ -236,9 +136,10 @@ __device__ __forceinline__ int pyr_level1(const unsigned char* __restrict__ l0, 
     return ((int)ra[xa] + (int)ra[xb] + (int)rb[xa] + (int)rb[xb] + 2) >> 2;
 }
 
-// Levels 1 and 2 in one launch: workgroup row blockIdx.x < H1 is row y of level 1, row H1 + y is row y of level 2; thread blockIdx.y * 256 + t
-// writes the four bytes x0 = 4 (...) ... x0 + 3 of that row.  A byte of level 2 comes from its four level-1 bytes recomputed from level 0 with
-// the nested rounding and clamps, so level 2 does not wait for level 1.  Bytes throughout: the buffers are held to no alignment.
+// Levels 1 and 2 in one launch: workgroup row blockIdx.x < H1 is row y of level 1, row H1 + y is row y of level 2; thread
+// blockIdx.y * 256 + t writes the four bytes x0 = 4 (...) ... x0 + 3 of that row.  A byte of level 2 comes from its four level-1 bytes
+// recomputed from level 0 with the nested rounding and clamps, so level 2 does not wait for level 1.  Bytes throughout: the buffers are held
+// to no alignment.
 __device__ __forceinline__ void temporal_pyramid_body(const PyrArgs& A, const unsigned char* __restrict__ l0, unsigned char* __restrict__ l1,
                                                       unsigned char* __restrict__ l2) {
     const int x0 = ((int)blockIdx.y * 256 + (int)threadIdx.x) * 4;
@@ -263,29 +164,34 @@ __global__ __launch_bounds__(256) void temporal_pyramid_kernel(const PyrArgs A, 
     temporal_pyramid_body(A, l0, l1, l2);
 }
 
-// temporal_search_kernel on one level (cur8 / prev8 [H, W]) with the window's origin displaced by the block's predictor, twice the vector of
-// block (by >> 1, bx >> 1) of the coarser level (parent [.., pnbx, 2]; nullptr at the coarsest level: (0, 0)), held to `hold` per component
-// before it reaches an address.  The window is (y0 + py - R, x0 + px - R) ..., each byte clamped into the level, so the LDS layout, the
-// candidates' reads and their conflict-freedom are those of temporal_search_kernel; the winner is the predictor plus the refinement.
-__device__ __forceinline__ void temporal_search_pred_body(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int H, int W,
-                                                          int R, const signed char* __restrict__ parent, int pnbx, int hold,
-                                                          signed char* __restrict__ v) {
-    __shared__ unsigned win[TWROWS * (TPITCH / 4)];
-    __shared__ unsigned blk[TB * (TB / 4)];
+__global__ __launch_bounds__(256) void temporal_pyramid_batch_kernel(const PyrArgs A, const FrameSel S, const FrameBuf L0, const FrameBuf L1,
+                                                                     const FrameBuf L2) {
+    const int f = (int)blockIdx.z;
+    if (f >= S.frames) return;
+    temporal_pyramid_body(A, frame_at(S, L0, f), frame_at(S, L1, f), A.H2 > 0 ? frame_at(S, L2, f) : nullptr);
+}
+
+// One level (cur8 / prev8 [H, W]), one workgroup per block (blockIdx.y, blockIdx.x).  prev8 == nullptr (no previous frame): every vector is
+// (0, 0).  The window's origin is displaced by the block's predictor, twice the vector of block (by >> 1, bx >> 1) of the coarser level
+// (parent [.., pnbx, 2]; nullptr at the coarsest level: (0, 0)), held to `hold` per component before it reaches an address: the window is
+// (y0 + py - R, x0 + px - R) ..., each byte clamped into the level.  The winner is the predictor plus the refinement.
+__device__ __forceinline__ void temporal_search_body(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int H, int W, int R,
+                                                     const signed char* __restrict__ parent, int pnbx, int hold, signed char* __restrict__ v) {
+    __shared__ unsigned win[TWROWS * (TPITCH / 4)];         // the previous luma's window, row pitch 8 dwords
+    __shared__ unsigned blk[TB * (TB / 4)];                 // the block's luma, 4 dwords per row, zero outside the frame
     __shared__ unsigned keys[256];
     const int t = (int)threadIdx.x;
     const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
     signed char* out = v + ((size_t)by * gridDim.x + bx) * 2;
-    if (prev8 == nullptr) {                                 // (uniform per launch)
+    if (prev8 == nullptr) {                                 // (uniform per workgroup)
         if (t == 0) { out[0] = 0; out[1] = 0; }
         return;
     }
     int py = 0, px = 0;
     if (parent != nullptr) {                                // (uniform per launch)
         const signed char* p = parent + ((size_t)(by >> 1) * pnbx + (bx >> 1)) * 2;
-        py = 2 * (int)p[0]; px = 2 * (int)p[1];
-        py = py < -hold ? -hold : (py > hold ? hold : py);  // (the coarser search wrote them within it; held to it again)
-        px = px < -hold ? -hold : (px > hold ? hold : px);
+        py = hold_to(2 * (int)p[0], hold);                  // (the coarser search wrote them within it; held to it again)
+        px = hold_to(2 * (int)p[1], hold);
     }
     const int y0 = by * TB, x0 = bx * TB;
     const int rows = H - y0 < TB ? H - y0 : TB, cols = W - x0 < TB ? W - x0 : TB;            // at least 1 each
@@ -355,87 +261,20 @@ __device__ __forceinline__ void temporal_search_pred_body(const unsigned char* _
     }
 }
 
-__global__ __launch_bounds__(256) void temporal_search_pred_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int H,
-                                                                   int W, int R, const signed char* __restrict__ parent, int pnbx, int hold,
-                                                                   signed char* __restrict__ v) {
-    temporal_search_pred_body(cur8, prev8, H, W, R, parent, pnbx, hold, v);
+__global__ __launch_bounds__(256) void temporal_search_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int H, int W,
+                                                              int R, const signed char* __restrict__ parent, int pnbx, int hold,
+                                                              signed char* __restrict__ v) {
+    temporal_search_body(cur8, prev8, H, W, R, parent, pnbx, hold, v);
 }
 
-}  // namespace
-
-// arguments: checked by the caller (fs_api.hip: fs_temporal_pyr_f32), lay: fs_temporal_pyr_layout's for the call's Ho, Wo and levels
-int temporal_pyr_f32(const fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
-                     int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
-                     unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, float* dst, hipStream_t s) {
-    const int L = lay.levels, Ho = lay.h[0], Wo = lay.w[0];
-    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
-    LumaArgs LA;
-    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
-    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
-    const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
-    const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
-    hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, src, luma);
-    if (L > 1) {
-        PyrArgs PA;
-        PA.H0 = Ho; PA.W0 = Wo; PA.H1 = lay.h[1]; PA.W1 = lay.w[1];
-        PA.H2 = L > 2 ? lay.h[2] : 0; PA.W2 = L > 2 ? lay.w[2] : 0;
-        const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);            // (W1 >= W2; at most 2^21 columns: within grid.y)
-        hipLaunchKernelGGL(temporal_pyramid_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks), block, 0, s, PA, (const unsigned char*)luma,
-                           pyr + lay.luma_offset[1], L > 2 ? pyr + lay.luma_offset[2] : nullptr);
-    }
-    for (int l = L - 1; l >= 0; --l) {                      // coarsest first: level l reads the vectors level l + 1 wrote
-        const unsigned char* c = l ? pyr + lay.luma_offset[l] : luma;
-        const unsigned char* p = prev_luma == nullptr ? nullptr : (l ? prev_pyr + lay.luma_offset[l] : prev_luma);
-        const signed char* parent = l == L - 1 ? nullptr : (const signed char*)(pyr + lay.mv_offset[l + 1]);
-        signed char* v = l ? (signed char*)(pyr + lay.mv_offset[l]) : mv;
-        hipLaunchKernelGGL(temporal_search_pred_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l]), block, 0, s, c, p, lay.h[l], lay.w[l], radius,
-                           parent, l == L - 1 ? 0 : lay.nbx[l + 1], 2 * radius * ((1 << (L - 1 - l)) - 1), v);
-    }
-    BlendArgs BA;
-    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = lay.nbx[0];
-    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = radius * ((1 << L) - 1);
-    hipLaunchKernelGGL(temporal_blend_kernel, egrid, block, 0, s, BA, cur, (const unsigned char*)luma, prev_luma, prev_out88, (const signed char*)mv, dst,
-                       out88);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+// C: the level's luma (its predecessor: the previous luma), P: the coarser level's vectors (has_parent 0: none), V: the vectors written
+__global__ __launch_bounds__(256) void temporal_search_batch_kernel(const FrameSel S, const FrameBuf C, int H, int W, int R, const FrameBuf P, int has_parent,
+                                                                    int pnbx, int hold, const FrameBuf V) {
+    const int f = (int)blockIdx.z;
+    if (f >= S.frames) return;
+    temporal_search_body(frame_at(S, C, f), frame_before(S, C, f), H, W, R, has_parent ? (const signed char*)frame_at(S, P, f) : nullptr, pnbx, hold,
+                         (signed char*)frame_at(S, V, f));
 }
-
-// arguments: checked by the caller (fs_api.hip: fs_temporal_f32)
-int temporal_f32(const float* src, int H, int W, const float* cur, int Ho, int Wo, int strength_q8, int sensitivity, int radius, int matrix, int src_bgr,
-                 const unsigned char* prev_luma, const unsigned short* prev_out88, unsigned char* luma, unsigned short* out88, signed char* mv,
-                 float* dst, hipStream_t s) {
-    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
-    LumaArgs LA;
-    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
-    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
-    const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
-    const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
-    hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, src, luma);
-    const int nby = (Ho + TB - 1) / TB, nbx = (Wo + TB - 1) / TB;
-    hipLaunchKernelGGL(temporal_search_kernel, dim3((unsigned)nbx, (unsigned)nby), block, 0, s, (const unsigned char*)luma, prev_luma, Ho, Wo, radius, mv);
-    BlendArgs BA;
-    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = nbx;
-    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = radius;
-    hipLaunchKernelGGL(temporal_blend_kernel, egrid, block, 0, s, BA, cur, (const unsigned char*)luma, prev_luma, prev_out88, (const signed char*)mv, dst,
-                       out88);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-// ---- quarter-pixel vectors (fs_temporal_sub_f32): a fraction per block from five SADs around the whole-pixel winner, and a bilinear fetch
-//   subpel -- one workgroup of 256 threads per 16x16 block of level 0.  The previous luma's 18 x 18 window around the block displaced by its
-//             vector (one pixel more on every side, every coordinate clamped) and the block's bytes go to LDS as in the search.  Thread t has
-//             block row (t >> 2) & 15 and dword t & 3 of that row; the wave t >> 6 says which sums it forms: 0 the row above, 1 the row below,
-//             2 the columns left and right, 3 the winner itself.  A thread reads the two window dwords that hold its four bytes, shifts them
-//             into place and adds one packed-byte SAD per sum.  Window pitch 12 dwords: the lanes of a 32-lane half are 8 consecutive rows x
-//             4 dwords at dword address 12 row + k (+ a constant per wave), and 12 row mod 32 over 8 consecutive rows is a permutation of
-//             {0, 4, ..., 28} -- 32 lanes on 32 banks, conflict-free by the rule that ds_read_b32 (and ds_read2_b32) banks are (a / 4) mod 32
-//             per 32-lane half; the block's dwords are at 4 row + k, the lane's own index.  The five sums of 64 partial sums each are reduced
-//             by an LDS tree; thread 0 fits and writes the fraction.
-//   blend  -- temporal_blend_kernel with the previous luma and output fetched bilinearly at quarter-pixel positions: two rows by five columns
-//             per thread, the second row / column only where the fraction along it is not zero.
-namespace {
-
-constexpr int SPITCH = 12;                 // dwords per LDS window row of the refinement: 5 used (18 bytes, the read of dword 4 ends at byte 19)
-constexpr int SWROWS = TB + 2;              // 18
 
 // the contract's fit: m, p the SADs one pixel before / after the winner's s0 along one axis -> the fraction in quarter pixels
 __device__ __forceinline__ int subpel_fit(int s0, int m, int p, int S) {
@@ -449,10 +288,18 @@ __device__ __forceinline__ int subpel_fit(int s0, int m, int p, int S) {
     return g * (1 << (2 - S));
 }
 
-// One workgroup per block (blockIdx.y, blockIdx.x) of level 0.  prev8 == nullptr (no previous frame) or R == 0: every fraction is (0, 0).
-// mv is held to `hold` per component before it reaches an address; nothing else read from a buffer does.
+// The refinement: one workgroup of 256 threads per 16x16 block (blockIdx.y, blockIdx.x) of level 0.  prev8 == nullptr (no previous frame) or
+// R == 0: every fraction is (0, 0).  The previous luma's 18 x 18 window around the block displaced by its
+// vector (one pixel more on every side, every coordinate clamped) and the block's bytes go to LDS as in the search.  Thread t has block row
+// (t >> 2) & 15 and dword t & 3 of that row; the wave t >> 6 says which sums it forms: 0 the row above, 1 the row below, 2 the columns left and
+// right, 3 the winner itself.  A thread reads the two window dwords that hold its four bytes, shifts them into place and adds one packed-byte
+// SAD per sum.  Window pitch 12 dwords: the lanes of a 32-lane half are 8 consecutive rows x 4 dwords at dword address 12 row + k (+ a
+// constant per wave), and 12 row mod 32 over 8 consecutive rows is a permutation of {0, 4, ..., 28} -- 32 lanes on 32 banks, conflict-free by
+// the rule that ds_read_b32 (and ds_read2_b32) banks are (a / 4) mod 32 per 32-lane half; the block's dwords are at 4 row + k, the lane's own
+// index.  The five sums of 64 partial sums each are reduced by an LDS tree; thread 0 fits and writes the fraction.  mv is held to `hold` per
+// component before it reaches an address; nothing else read from a buffer does.
 __device__ __forceinline__ void temporal_subpel_body(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int Ho, int Wo,
-                                                     int R, int hold, int S, const signed char* __restrict__ mv, signed char* __restrict__ mvf) {
+                                                     int R, int hold, int Sp, const signed char* __restrict__ mv, signed char* __restrict__ mvf) {
     __shared__ unsigned win[SWROWS * SPITCH];
     __shared__ unsigned blk[TB * (TB / 4)];
     __shared__ unsigned part[5 * 64];                       // S0, Sym, Syp, Sxm, Sxp: 64 partial sums each
@@ -460,13 +307,11 @@ __device__ __forceinline__ void temporal_subpel_body(const unsigned char* __rest
     const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
     const size_t b = (size_t)by * gridDim.x + bx;
     signed char* out = mvf + b * 2;
-    if (prev8 == nullptr || R == 0) {                       // (uniform per launch)
+    if (prev8 == nullptr || R == 0) {                       // (uniform per workgroup)
         if (t == 0) { out[0] = 0; out[1] = 0; }
         return;
     }
-    int dy = (int)mv[b * 2], dx = (int)mv[b * 2 + 1];
-    dy = dy < -hold ? -hold : (dy > hold ? hold : dy);      // (the search wrote them within it; held to it again)
-    dx = dx < -hold ? -hold : (dx > hold ? hold : dx);
+    const int dy = hold_to((int)mv[b * 2], hold), dx = hold_to((int)mv[b * 2 + 1], hold);   // (the search wrote them within it; held to it again)
     const int y0 = by * TB, x0 = bx * TB;
     const int rows = Ho - y0 < TB ? Ho - y0 : TB, cols = Wo - x0 < TB ? Wo - x0 : TB;        // at least 1 each
     if (t < SWROWS * 5) {                                   // window row t / 5, dword t % 5: frame rows y0 + dy - 1 ..., columns x0 + dx - 1 ...
@@ -513,161 +358,32 @@ __device__ __forceinline__ void temporal_subpel_body(const unsigned char* __rest
     }
     if (t == 0) {
         const int s0 = (int)part[0];
-        out[0] = (signed char)subpel_fit(s0, (int)part[64], (int)part[128], S);
-        out[1] = (signed char)subpel_fit(s0, (int)part[192], (int)part[256], S);
+        out[0] = (signed char)subpel_fit(s0, (int)part[64], (int)part[128], Sp);
+        out[1] = (signed char)subpel_fit(s0, (int)part[192], (int)part[256], Sp);
     }
 }
 
 __global__ __launch_bounds__(256) void temporal_subpel_kernel(const unsigned char* __restrict__ cur8, const unsigned char* __restrict__ prev8, int Ho,
-                                                              int Wo, int R, int hold, int S, const signed char* __restrict__ mv,
+                                                              int Wo, int R, int hold, int Sp, const signed char* __restrict__ mv,
                                                               signed char* __restrict__ mvf) {
-    temporal_subpel_body(cur8, prev8, Ho, Wo, R, hold, S, mv, mvf);
+    temporal_subpel_body(cur8, prev8, Ho, Wo, R, hold, Sp, mv, mvf);
 }
 
-// temporal_blend_kernel's threads and arguments, with the block's fraction mvf beside its vector: the previous luma and output are fetched
-// at (4 (y + dy) + fy, 4 (x + dx) + fx) quarter pixels, bilinearly between the two rows and the five columns that the thread's four pixels
-// touch, every one clamped into the frame.  ay and ax are the same for the four pixels (4 x is a multiple of 4).  dst may be cur, as there.
-__global__ __launch_bounds__(256) void temporal_blend_sub_kernel(const BlendArgs A, const float* cur, const unsigned char* __restrict__ cur8,
-                                                                 const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
-                                                                 const signed char* __restrict__ mv, const signed char* __restrict__ mvf, float* dst,
-                                                                 unsigned short* __restrict__ out88) {
-    const int groups = (A.Wo + 3) >> 2;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)groups * A.Ho) return;
-    const int y = (int)(i / groups), x0 = (int)(i - (long long)y * groups) * 4;
-    const size_t row = (size_t)y * A.Wo;
-    int ay = 0, ax = 0;
-    size_t r0 = 0, r1 = 0;                                  // the two rows' first pixels
-    int col[5] = {0, 0, 0, 0, 0};
-    if (prev8 != nullptr) {                                 // (uniform per launch)
-        const size_t b = ((size_t)(y >> 4) * A.nbx + (x0 >> 4)) * 2;
-        const int dy = (int)mv[b] < -A.R ? -A.R : ((int)mv[b] > A.R ? A.R : (int)mv[b]);     // (written within these bounds; held to them again)
-        const int dx = (int)mv[b + 1] < -A.R ? -A.R : ((int)mv[b + 1] > A.R ? A.R : (int)mv[b + 1]);
-        const int fy = (int)mvf[b] < -2 ? -2 : ((int)mvf[b] > 2 ? 2 : (int)mvf[b]);
-        const int fx = (int)mvf[b + 1] < -2 ? -2 : ((int)mvf[b + 1] > 2 ? 2 : (int)mvf[b + 1]);
-        const int Y4 = 4 * (y + dy) + fy, X4 = 4 * (x0 + dx) + fx;
-        ay = Y4 & 3; ax = X4 & 3;
-        r0 = (size_t)clampi(Y4 >> 2, A.Ho - 1) * A.Wo;
-        r1 = (size_t)clampi((Y4 >> 2) + 1, A.Ho - 1) * A.Wo;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) col[j] = clampi((X4 >> 2) + j, A.Wo - 1);
-    }
-    const int n = A.Wo - x0 < 4 ? A.Wo - x0 : 4;
-    const size_t at0 = (row + x0) * 3;
-    float b[12];                                            // every read of cur before the first write of dst: the two may be one tensor
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int xn = k < n ? k : n - 1;                   // (beyond the row's end: the last pixel again, never stored)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) b[3 * k + c] = cur[at0 + 3 * xn + c];
-    }
-    const int wy0 = 4 - ay, wx0 = 4 - ax;
-    int F[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int xn = x0 + (k < n ? k : n - 1);
-        const int B0 = temporal_f88(b[3 * k]), B1 = temporal_f88(b[3 * k + 1]), B2 = temporal_f88(b[3 * k + 2]);
-        F[3 * k] = B0; F[3 * k + 1] = B1; F[3 * k + 2] = B2;
-        if (prev8 != nullptr) {
-            const size_t q00 = r0 + col[k], q01 = r0 + col[k + 1], q10 = r1 + col[k], q11 = r1 + col[k + 1];
-            int pq = (int)prev8[q00];
-            int P0 = prev88[q00 * 3], P1 = prev88[q00 * 3 + 1], P2 = prev88[q00 * 3 + 2];
-            if (ay | ax) {                                  // a weight of zero stands before whatever is not fetched
-                int l01 = 0, l10 = 0, l11 = 0, p01[3] = {0, 0, 0}, p10[3] = {0, 0, 0}, p11[3] = {0, 0, 0};
-                if (ax) {
-                    l01 = prev8[q01];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) p01[c] = prev88[q01 * 3 + c];
-                }
-                if (ay) {
-                    l10 = prev8[q10];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) p10[c] = prev88[q10 * 3 + c];
-                    if (ax) {
-                        l11 = prev8[q11];
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) p11[c] = prev88[q11 * 3 + c];
-                    }
-                }
-                pq = (wy0 * (wx0 * pq + ax * l01) + ay * (wx0 * l10 + ax * l11) + 8) >> 4;
-                P0 = (wy0 * (wx0 * P0 + ax * p01[0]) + ay * (wx0 * p10[0] + ax * p11[0]) + 8) >> 4;      // at most 16 x 65280 + 8
-                P1 = (wy0 * (wx0 * P1 + ax * p01[1]) + ay * (wx0 * p10[1] + ax * p11[1]) + 8) >> 4;
-                P2 = (wy0 * (wx0 * P2 + ax * p01[2]) + ay * (wx0 * p10[2] + ax * p11[2]) + 8) >> 4;
-            }
-            const int d = (int)cur8[row + xn] - pq;
-            const int e = d < 0 ? -d : d;
-            const int conf = 256 - e * A.sensitivity;
-            const long long w = (long long)A.strength_q8 * (conf > 0 ? conf : 0);        // 0 ... 65536
-            F[3 * k] = B0 + (int)(((long long)(P0 - B0) * w + 32768) >> 16);
-            F[3 * k + 1] = B1 + (int)(((long long)(P1 - B1) * w + 32768) >> 16);
-            F[3 * k + 2] = B2 + (int)(((long long)(P2 - B2) * w + 32768) >> 16);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k < n) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                dst[at0 + 3 * k + c] = (float)F[3 * k + c] * 0.00390625f;
-                out88[at0 + 3 * k + c] = (unsigned short)F[3 * k + c];
-            }
-        }
+__global__ __launch_bounds__(256) void temporal_subpel_batch_kernel(const FrameSel S, const FrameBuf C, int Ho, int Wo, int R, int hold, int Sp,
+                                                                    const FrameBuf MV, const FrameBuf MVF) {
+    const int f = (int)blockIdx.z;
+    if (f >= S.frames) return;
+    temporal_subpel_body(frame_at(S, C, f), frame_before(S, C, f), Ho, Wo, R, hold, Sp, (const signed char*)frame_at(S, MV, f),
+                         (signed char*)frame_at(S, MVF, f));
 }
 
-}  // namespace
+struct BlendArgs {
+    int Ho, Wo, nby, nbx;
+    int strength_q8, sensitivity, R;
+};
 
-// arguments: checked by the caller (fs_api.hip: fs_temporal_sub_f32), lay: fs_temporal_pyr_layout's for the call's Ho, Wo and levels.
-// subpel 0 is temporal_pyr_f32; above it, its launches up to the searches, the refinement, and the bilinear blend in place of the whole-pixel one.
-int temporal_sub_f32(const fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
-                     int subpel, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88, const unsigned char* prev_pyr,
-                     unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf, float* dst, hipStream_t s) {
-    if (subpel == 0)
-        return temporal_pyr_f32(lay, src, H, W, cur, strength_q8, sensitivity, radius, matrix, src_bgr, prev_luma, prev_out88, prev_pyr, luma, out88, pyr,
-                                mv, dst, s);
-    const int L = lay.levels, Ho = lay.h[0], Wo = lay.w[0];
-    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
-    LumaArgs LA;
-    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
-    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
-    const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
-    const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
-    hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, src, luma);
-    if (L > 1) {
-        PyrArgs PA;
-        PA.H0 = Ho; PA.W0 = Wo; PA.H1 = lay.h[1]; PA.W1 = lay.w[1];
-        PA.H2 = L > 2 ? lay.h[2] : 0; PA.W2 = L > 2 ? lay.w[2] : 0;
-        const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);
-        hipLaunchKernelGGL(temporal_pyramid_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks), block, 0, s, PA, (const unsigned char*)luma,
-                           pyr + lay.luma_offset[1], L > 2 ? pyr + lay.luma_offset[2] : nullptr);
-    }
-    for (int l = L - 1; l >= 0; --l) {                      // coarsest first, as in temporal_pyr_f32
-        const unsigned char* c = l ? pyr + lay.luma_offset[l] : luma;
-        const unsigned char* p = prev_luma == nullptr ? nullptr : (l ? prev_pyr + lay.luma_offset[l] : prev_luma);
-        const signed char* parent = l == L - 1 ? nullptr : (const signed char*)(pyr + lay.mv_offset[l + 1]);
-        signed char* v = l ? (signed char*)(pyr + lay.mv_offset[l]) : mv;
-        hipLaunchKernelGGL(temporal_search_pred_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l]), block, 0, s, c, p, lay.h[l], lay.w[l], radius,
-                           parent, l == L - 1 ? 0 : lay.nbx[l + 1], 2 * radius * ((1 << (L - 1 - l)) - 1), v);
-    }
-    const int hold = radius * ((1 << L) - 1);
-    hipLaunchKernelGGL(temporal_subpel_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0]), block, 0, s, (const unsigned char*)luma, prev_luma, Ho, Wo,
-                       radius, hold, subpel, (const signed char*)mv, mvf);
-    BlendArgs BA;
-    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = lay.nbx[0];
-    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = hold;
-    hipLaunchKernelGGL(temporal_blend_sub_kernel, egrid, block, 0, s, BA, cur, (const unsigned char*)luma, prev_luma, prev_out88, (const signed char*)mv,
-                       (const signed char*)mvf, dst, out88);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-// ---- overlapped block vectors (fs_temporal_obmc_f32): every pixel weighs the vectors of the four blocks whose centres surround it
-//   blend  -- the blends' threads: four pixels of an output row.  They share their four blocks (the block row changes between rows y = 16 b + 7
-//             and 16 b + 8, the block column between x = 16 b + 7 and 16 b + 8, a multiple of 4), so the four vectors are read once per thread
-//             and only the column window weight differs per pixel.  A thread whose four held quarter-pixel vectors are equal runs the body of
-//             temporal_blend_sub_kernel on that vector: one fetch per pixel, no division (Pbar = P and cbar = conf there).  The others fetch
-//             along the four vectors, sum in 64 bits and divide once per channel.  Waves diverge only along motion edges.
-namespace {
-
-// the rows, columns and weights of temporal_blend_sub_kernel's fetch for a thread's four pixels displaced by (qy, qx) quarter pixels
+// the rows, columns and weights of the fetch for a thread's four pixels (y, x0 ... x0 + 3) displaced by (qy, qx) quarter pixels: two rows by
+// five columns, every one clamped into the frame; ay and ax are the same for the four pixels (4 x is a multiple of 4)
 struct Tap {
     size_t r0, r1;
     int col[5];
@@ -685,14 +401,16 @@ __device__ __forceinline__ Tap make_tap(const BlendArgs& A, int y, int x0, int q
     return t;
 }
 
-// pixel k of the thread: the previous luma and output at the tap, bilinear; a weight of zero stands before whatever is not fetched
+// pixel k of the thread: the previous luma and output at the tap, bilinear; a weight of zero stands before whatever is not fetched.  FRAC
+// false: the caller's vectors are whole pixels (ay = ax = 0), nothing but the first position is fetched and no branch stands for it.
+template <bool FRAC>
 __device__ __forceinline__ void tap_fetch(const Tap& t, int k, const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88, int& pq,
                                           int P[3]) {
     const size_t q00 = t.r0 + t.col[k], q01 = t.r0 + t.col[k + 1], q10 = t.r1 + t.col[k], q11 = t.r1 + t.col[k + 1];
     pq = (int)prev8[q00];
 #pragma unroll
     for (int c = 0; c < 3; ++c) P[c] = prev88[q00 * 3 + c];
-    if (t.ay | t.ax) {
+    if (FRAC && (t.ay | t.ax)) {
         const int wy0 = 4 - t.ay, wx0 = 4 - t.ax;
         int l01 = 0, l10 = 0, l11 = 0, p01[3] = {0, 0, 0}, p10[3] = {0, 0, 0}, p11[3] = {0, 0, 0};
         if (t.ax) {
@@ -716,6 +434,23 @@ __device__ __forceinline__ void tap_fetch(const Tap& t, int k, const unsigned ch
     }
 }
 
+// how well the source matched: 256 where the current luma c8 equals the fetched previous luma pq, less `sensitivity` per step apart, at least 0
+__device__ __forceinline__ int confidence(int c8, int pq, const BlendArgs& A) {
+    const int d = c8 - pq;
+    const int conf = 256 - (d < 0 ? -d : d) * A.sensitivity;
+    return conf > 0 ? conf : 0;
+}
+
+// F += (P - F) w / 2^16, rounded; w = strength_q8 x confidence, 0 ... 65536
+__device__ __forceinline__ void step_towards(int F[3], const int P[3], long long w) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) F[c] += (int)(((long long)(P[c] - F[c]) * w + 32768) >> 16);
+}
+
+__device__ __forceinline__ void blend_towards(int F[3], const int P[3], int c8, int pq, const BlendArgs& A) {
+    step_towards(F, P, (long long)A.strength_q8 * confidence(c8, pq, A));
+}
+
 // floor(num / den) for num < 2^36 and 0 < den <= 2^19 with a quotient below 2^16: a float estimate (off by less than one) and an exact
 // integer fix-up, which is right whatever the estimate was
 __device__ __forceinline__ int floor_div(unsigned long long num, unsigned den) {
@@ -726,41 +461,60 @@ __device__ __forceinline__ int floor_div(unsigned long long num, unsigned den) {
     return (int)q;
 }
 
-// temporal_blend_sub_kernel's threads and arguments (mvf == nullptr: every fraction is zero, the whole-pixel vectors of temporal_blend_kernel),
-// nby beside A.nbx.  dst may be cur, as there.  mv and mvf are held to their bounds and the block indices clamped before any of them reaches
-// an address; nothing else read from a buffer does.
-__global__ __launch_bounds__(256) void temporal_blend_obmc_kernel(const BlendArgs A, int nby, const float* cur, const unsigned char* __restrict__ cur8,
-                                                                  const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
-                                                                  const signed char* __restrict__ mv, const signed char* __restrict__ mvf, float* dst,
-                                                                  unsigned short* __restrict__ out88) {
+enum BlendMode { BLEND_WHOLE, BLEND_SUB, BLEND_OBMC };
+
+// The blends.  Thread i: row y, pixels x0 ... x0 + 3 as in the luma kernel (they lie in one block).  prev8 == nullptr (no previous frame,
+// uniform per launch): F = to88(cur).  dst may be cur: a thread reads its own pixels before it writes them, and no other thread reads them
+// (hence no __restrict__ on the two).  prev8 / prev88 are read at displaced positions: they are not cur8 / out88.  mv and mvf are held to
+// their bounds and the block indices clamped before any of them reaches an address; nothing else read from a buffer does.
+//   BLEND_WHOLE -- along the block's vector mv (mvf is not read); the tap's fractions are zero.
+//   BLEND_SUB   -- along 4 mv + mvf quarter pixels, fetched bilinearly: the second row / column only where the fraction along it is not zero.
+//   BLEND_OBMC  -- every pixel weighs the vectors of the four blocks whose centres surround it (mvf == nullptr: every fraction is zero).  The
+//                  thread's four pixels share their four blocks (the block row changes between rows y = 16 b + 7 and 16 b + 8, the block
+//                  column between x = 16 b + 7 and 16 b + 8, a multiple of 4), so the four vectors are read once per thread and only the
+//                  column window weight differs per pixel.  A thread whose four held quarter-pixel vectors are equal blends as BLEND_SUB
+//                  along that vector: one fetch per pixel, no division (Pbar = P and cbar = conf there).  The others fetch along the four
+//                  vectors, sum in 64 bits and divide once per channel.  Waves diverge only along motion edges.
+template <BlendMode MODE>
+__device__ __forceinline__ void temporal_blend_body(const BlendArgs& A, const float* cur, const unsigned char* __restrict__ cur8,
+                                                    const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
+                                                    const signed char* __restrict__ mv, const signed char* __restrict__ mvf, float* dst,
+                                                    unsigned short* __restrict__ out88) {
     const int groups = (A.Wo + 3) >> 2;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)groups * A.Ho) return;
     const int y = (int)(i / groups), x0 = (int)(i - (long long)y * groups) * 4;
     const size_t row = (size_t)y * A.Wo;
-    int qy[4] = {0, 0, 0, 0}, qx[4] = {0, 0, 0, 0};         // the held vectors in quarter pixels of the candidates (row, column): (0, 0) (0, 1) (1, 0) (1, 1)
-    const int ty = 2 * y - 15, tx = 2 * x0 - 15;            // (tx + 2 k for pixel k: the same tx >> 5 for the four)
+    int qy[4] = {0, 0, 0, 0}, qx[4] = {0, 0, 0, 0};         // the held vectors in quarter pixels; BLEND_OBMC: of the candidates (row, column) (0, 0) (0, 1) (1, 0) (1, 1)
+    const int ty = 2 * y - 15, tx = 2 * x0 - 15;            // BLEND_OBMC (tx + 2 k for pixel k: the same tx >> 5 for the four)
     const int wy1 = ty & 31;                                // the window weight of the second block row; 32 - wy1 of the first
     bool same = true;
-    if (prev8 != nullptr) {                                 // (uniform per launch)
-        const int j0 = ty >> 5, i0 = tx >> 5;
-        const int bj[2] = {clampi(j0, nby - 1), clampi(j0 + 1, nby - 1)}, bi[2] = {clampi(i0, A.nbx - 1), clampi(i0 + 1, A.nbx - 1)};
-        const signed char* __restrict__ fr = mvf != nullptr ? mvf : mv;                  // (no fractions: bytes that can be read, masked away below)
-        const int fmask = mvf != nullptr ? -1 : 0;          // (uniform per launch)
-        int raw[16];                                        // the sixteen loads ahead of their first use, with no branch between them: one wait
+    if (prev8 != nullptr) {
+        if (MODE == BLEND_OBMC) {
+            const int j0 = ty >> 5, i0 = tx >> 5;
+            const int bj[2] = {clampi(j0, A.nby - 1), clampi(j0 + 1, A.nby - 1)}, bi[2] = {clampi(i0, A.nbx - 1), clampi(i0 + 1, A.nbx - 1)};
+            const signed char* __restrict__ fr = mvf != nullptr ? mvf : mv;                  // (no fractions: bytes that can be read, masked away below)
+            const int fmask = mvf != nullptr ? -1 : 0;      // (uniform per launch)
+            int raw[16];                                    // the sixteen loads ahead of their first use, with no branch between them: one wait
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const size_t b = ((size_t)bj[c >> 1] * A.nbx + bi[c & 1]) * 2;
-            raw[4 * c] = (int)mv[b]; raw[4 * c + 1] = (int)mv[b + 1]; raw[4 * c + 2] = (int)fr[b]; raw[4 * c + 3] = (int)fr[b + 1];
-        }
+            for (int c = 0; c < 4; ++c) {
+                const size_t b = ((size_t)bj[c >> 1] * A.nbx + bi[c & 1]) * 2;
+                raw[4 * c] = (int)mv[b]; raw[4 * c + 1] = (int)mv[b + 1]; raw[4 * c + 2] = (int)fr[b]; raw[4 * c + 3] = (int)fr[b + 1];
+            }
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int dy = raw[4 * c] < -A.R ? -A.R : (raw[4 * c] > A.R ? A.R : raw[4 * c]);        // (written within these bounds; held to them again)
-            const int dx = raw[4 * c + 1] < -A.R ? -A.R : (raw[4 * c + 1] > A.R ? A.R : raw[4 * c + 1]);
-            const int fy = (raw[4 * c + 2] < -2 ? -2 : (raw[4 * c + 2] > 2 ? 2 : raw[4 * c + 2])) & fmask;
-            const int fx = (raw[4 * c + 3] < -2 ? -2 : (raw[4 * c + 3] > 2 ? 2 : raw[4 * c + 3])) & fmask;
-            qy[c] = 4 * dy + fy; qx[c] = 4 * dx + fx;
-            same = same && qy[c] == qy[0] && qx[c] == qx[0];
+            for (int c = 0; c < 4; ++c) {                   // (written within these bounds; held to them again)
+                qy[c] = 4 * hold_to(raw[4 * c], A.R) + (hold_to(raw[4 * c + 2], 2) & fmask);
+                qx[c] = 4 * hold_to(raw[4 * c + 1], A.R) + (hold_to(raw[4 * c + 3], 2) & fmask);
+                same = same && qy[c] == qy[0] && qx[c] == qx[0];
+            }
+        } else {
+            const size_t b = ((size_t)(y >> 4) * A.nbx + (x0 >> 4)) * 2;
+            qy[0] = 4 * hold_to((int)mv[b], A.R);           // (written within these bounds; held to them again)
+            qx[0] = 4 * hold_to((int)mv[b + 1], A.R);
+            if (MODE == BLEND_SUB) {
+                qy[0] += hold_to((int)mvf[b], 2);
+                qx[0] += hold_to((int)mvf[b + 1], 2);
+            }
         }
     }
     const int n = A.Wo - x0 < 4 ? A.Wo - x0 : 4;
@@ -779,20 +533,15 @@ __global__ __launch_bounds__(256) void temporal_blend_obmc_kernel(const BlendArg
         for (int c = 0; c < 3; ++c) F[3 * k + c] = temporal_f88(b[3 * k + c]);
         c8[k] = prev8 != nullptr ? (int)cur8[row + x0 + (k < n ? k : n - 1)] : 0;
     }
-    if (prev8 != nullptr && same) {                         // the four vectors agree: the whole-block blend along that vector
+    if (prev8 != nullptr && same) {                         // one vector for the four pixels
         const Tap t = make_tap(A, y, x0, qy[0], qx[0]);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             int pq, P[3];
-            tap_fetch(t, k, prev8, prev88, pq, P);          // (beyond the row's end: whatever lies there, clamped; never stored)
-            const int d = c8[k] - pq;
-            const int e = d < 0 ? -d : d;
-            const int conf = 256 - e * A.sensitivity;
-            const long long w = (long long)A.strength_q8 * (conf > 0 ? conf : 0);        // 0 ... 65536
-#pragma unroll
-            for (int c = 0; c < 3; ++c) F[3 * k + c] += (int)(((long long)(P[c] - F[3 * k + c]) * w + 32768) >> 16);
+            tap_fetch<MODE != BLEND_WHOLE>(t, k, prev8, prev88, pq, P);        // (beyond the row's end: whatever lies there, clamped; never stored)
+            blend_towards(F + 3 * k, P, c8[k], pq, A);
         }
-    } else if (prev8 != nullptr) {
+    } else if (MODE == BLEND_OBMC && prev8 != nullptr) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {                       // pixel by pixel: the sums of one pixel are live at a time
             unsigned D = 0;                                 // at most 2^18
@@ -803,11 +552,8 @@ __global__ __launch_bounds__(256) void temporal_blend_obmc_kernel(const BlendArg
             for (int c = 0; c < 4; ++c) {
                 const Tap t = make_tap(A, y, x0 + k, qy[c], qx[c]);
                 int pq, P[3];
-                tap_fetch(t, 0, prev8, prev88, pq, P);      // (beyond the row's end: whatever lies there, clamped; never stored)
-                const int d = c8[k] - pq;
-                const int e = d < 0 ? -d : d;
-                int conf = 256 - e * A.sensitivity;
-                conf = conf > 0 ? conf : 0;
+                tap_fetch<true>(t, 0, prev8, prev88, pq, P);                   // (beyond the row's end: whatever lies there, clamped; never stored)
+                const int conf = confidence(c8[k], pq, A);
                 const unsigned wc = (unsigned)(((c >> 1) ? wy1 : 32 - wy1) * ((c & 1) ? wx1 : 32 - wx1) * conf);
                 D += wc;
                 cmax = conf > cmax ? conf : cmax;
@@ -816,12 +562,10 @@ __global__ __launch_bounds__(256) void temporal_blend_obmc_kernel(const BlendArg
             }
             if (D == 0) continue;                           // F = B
             const int cbar = cmax < (int)(D >> 8) ? cmax : (int)(D >> 8);
-            const long long w = (long long)A.strength_q8 * cbar;                         // 0 ... 65536
+            int Pbar[3];
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const int Pbar = floor_div(2 * N[ch] + D, 2 * D);                        // the rounded weighted mean, 0 ... 65280
-                F[3 * k + ch] += (int)(((long long)(Pbar - F[3 * k + ch]) * w + 32768) >> 16);
-            }
+            for (int ch = 0; ch < 3; ++ch) Pbar[ch] = floor_div(2 * N[ch] + D, 2 * D);   // the rounded weighted mean, 0 ... 65280
+            step_towards(F + 3 * k, Pbar, (long long)A.strength_q8 * cbar);
         }
     }
 #pragma unroll
@@ -835,109 +579,24 @@ __global__ __launch_bounds__(256) void temporal_blend_obmc_kernel(const BlendArg
         }
 }
 
-}  // namespace
-
-// arguments: checked by the caller (fs_api.hip: fs_temporal_obmc_f32).  overlap 0 is temporal_sub_f32; with 1 its launches with the blend
-// replaced by temporal_blend_obmc_kernel (mvf null with subpel 0: no refinement launch, whole-pixel vectors).
-int temporal_obmc_f32(const fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int strength_q8, int sensitivity, int radius,
-                      int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
-                      const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf,
-                      float* dst, hipStream_t s) {
-    if (overlap == 0)
-        return temporal_sub_f32(lay, src, H, W, cur, strength_q8, sensitivity, radius, subpel, matrix, src_bgr, prev_luma, prev_out88, prev_pyr, luma, out88,
-                                pyr, mv, mvf, dst, s);
-    const int L = lay.levels, Ho = lay.h[0], Wo = lay.w[0];
-    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
-    LumaArgs LA;
-    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
-    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
-    const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
-    const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
-    hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, src, luma);
-    if (L > 1) {
-        PyrArgs PA;
-        PA.H0 = Ho; PA.W0 = Wo; PA.H1 = lay.h[1]; PA.W1 = lay.w[1];
-        PA.H2 = L > 2 ? lay.h[2] : 0; PA.W2 = L > 2 ? lay.w[2] : 0;
-        const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);
-        hipLaunchKernelGGL(temporal_pyramid_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks), block, 0, s, PA, (const unsigned char*)luma,
-                           pyr + lay.luma_offset[1], L > 2 ? pyr + lay.luma_offset[2] : nullptr);
-    }
-    for (int l = L - 1; l >= 0; --l) {                      // coarsest first, as in temporal_pyr_f32
-        const unsigned char* c = l ? pyr + lay.luma_offset[l] : luma;
-        const unsigned char* p = prev_luma == nullptr ? nullptr : (l ? prev_pyr + lay.luma_offset[l] : prev_luma);
-        const signed char* parent = l == L - 1 ? nullptr : (const signed char*)(pyr + lay.mv_offset[l + 1]);
-        signed char* v = l ? (signed char*)(pyr + lay.mv_offset[l]) : mv;
-        hipLaunchKernelGGL(temporal_search_pred_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l]), block, 0, s, c, p, lay.h[l], lay.w[l], radius,
-                           parent, l == L - 1 ? 0 : lay.nbx[l + 1], 2 * radius * ((1 << (L - 1 - l)) - 1), v);
-    }
-    const int hold = radius * ((1 << L) - 1);
-    if (subpel > 0)
-        hipLaunchKernelGGL(temporal_subpel_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0]), block, 0, s, (const unsigned char*)luma, prev_luma, Ho,
-                           Wo, radius, hold, subpel, (const signed char*)mv, mvf);
-    BlendArgs BA;
-    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = lay.nbx[0];
-    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = hold;
-    hipLaunchKernelGGL(temporal_blend_obmc_kernel, egrid, block, 0, s, BA, lay.nby[0], cur, (const unsigned char*)luma, prev_luma, prev_out88,
-                       (const signed char*)mv, subpel > 0 ? (const signed char*)mvf : nullptr, dst, out88);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+__global__ __launch_bounds__(256) void temporal_blend_kernel(const BlendArgs A, const float* cur, const unsigned char* __restrict__ cur8,
+                                                             const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
+                                                             const signed char* __restrict__ mv, float* dst, unsigned short* __restrict__ out88) {
+    temporal_blend_body<BLEND_WHOLE>(A, cur, cur8, prev8, prev88, mv, nullptr, dst, out88);
 }
 
-// ---- batches of consecutive frames (fs_temporal_batch_f32): only the blend is recursive, so the launches before it run once over all frames
-//   The kernels are the bodies above with the frame index f as one more grid dimension (blockIdx.y of the luma's 1-D grid, blockIdx.z of the
-//   others).  A buffer of frame f lies in the work buffer's slot f, except the last frame's, which is the state's (pointer selection, no copy
-//   launch); frame f's "previous" is slot f - 1, for f = 0 the state the previous call wrote (null: no previous frame).  f is uniform per
-//   workgroup and held below `frames`, so the selection stays in scalar registers; no value read from a tensor takes part in it.
-namespace {
-
-struct FrameSel {
-    unsigned char* work;                    // slot f at work + f * slot, f < frames - 1
-    unsigned long long slot;
-    int frames;
-};
-
-// one buffer of every frame: the last frame's (in the state written), frame 0's predecessor (in the state read, or null), the offset in a slot
-struct FrameBuf {
-    unsigned char* last;
-    const unsigned char* before;
-    unsigned long long off;
-};
-
-__device__ __forceinline__ unsigned char* frame_at(const FrameSel& S, const FrameBuf& B, int f) {
-    return f == S.frames - 1 ? B.last : S.work + (size_t)f * S.slot + B.off;
+__global__ __launch_bounds__(256) void temporal_blend_sub_kernel(const BlendArgs A, const float* cur, const unsigned char* __restrict__ cur8,
+                                                                 const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
+                                                                 const signed char* __restrict__ mv, const signed char* __restrict__ mvf, float* dst,
+                                                                 unsigned short* __restrict__ out88) {
+    temporal_blend_body<BLEND_SUB>(A, cur, cur8, prev8, prev88, mv, mvf, dst, out88);
 }
 
-__device__ __forceinline__ const unsigned char* frame_before(const FrameSel& S, const FrameBuf& B, int f) {
-    return f == 0 ? B.before : S.work + (size_t)(f - 1) * S.slot + B.off;
-}
-
-__global__ __launch_bounds__(256) void temporal_luma_batch_kernel(const LumaArgs A, const FrameSel S, const FrameBuf L, const float* __restrict__ src) {
-    const int f = (int)blockIdx.y;
-    if (f >= S.frames) return;
-    temporal_luma_body(A, src + (size_t)f * A.H * A.W * 3, frame_at(S, L, f));
-}
-
-__global__ __launch_bounds__(256) void temporal_pyramid_batch_kernel(const PyrArgs A, const FrameSel S, const FrameBuf L0, const FrameBuf L1,
-                                                                     const FrameBuf L2) {
-    const int f = (int)blockIdx.z;
-    if (f >= S.frames) return;
-    temporal_pyramid_body(A, frame_at(S, L0, f), frame_at(S, L1, f), A.H2 > 0 ? frame_at(S, L2, f) : nullptr);
-}
-
-// C: the level's luma (its predecessor: the previous luma), P: the coarser level's vectors (has_parent 0: none), V: the vectors written
-__global__ __launch_bounds__(256) void temporal_search_batch_kernel(const FrameSel S, const FrameBuf C, int H, int W, int R, const FrameBuf P, int has_parent,
-                                                                    int pnbx, int hold, const FrameBuf V) {
-    const int f = (int)blockIdx.z;
-    if (f >= S.frames) return;
-    temporal_search_pred_body(frame_at(S, C, f), frame_before(S, C, f), H, W, R, has_parent ? (const signed char*)frame_at(S, P, f) : nullptr, pnbx, hold,
-                              (signed char*)frame_at(S, V, f));
-}
-
-__global__ __launch_bounds__(256) void temporal_subpel_batch_kernel(const FrameSel S, const FrameBuf C, int Ho, int Wo, int R, int hold, int Sp,
-                                                                    const FrameBuf MV, const FrameBuf MVF) {
-    const int f = (int)blockIdx.z;
-    if (f >= S.frames) return;
-    temporal_subpel_body(frame_at(S, C, f), frame_before(S, C, f), Ho, Wo, R, hold, Sp, (const signed char*)frame_at(S, MV, f),
-                         (signed char*)frame_at(S, MVF, f));
+__global__ __launch_bounds__(256) void temporal_blend_obmc_kernel(const BlendArgs A, const float* cur, const unsigned char* __restrict__ cur8,
+                                                                  const unsigned char* __restrict__ prev8, const unsigned short* __restrict__ prev88,
+                                                                  const signed char* __restrict__ mv, const signed char* __restrict__ mvf, float* dst,
+                                                                  unsigned short* __restrict__ out88) {
+    temporal_blend_body<BLEND_OBMC>(A, cur, cur8, prev8, prev88, mv, mvf, dst, out88);
 }
 
 inline uint64_t up16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
@@ -963,64 +622,79 @@ BatchLay batch_lay(const fs_temporal_pyr_info& lay, int subpel, int frames) {
 
 }  // namespace
 
-// arguments: checked by the caller (fs_api.hip: fs_temporal_batch_f32), frames > 1
-int temporal_batch_f32(const fs_temporal_pyr_info& lay, const float* src, int H, int W, const float* cur, int frames, int strength_q8, int sensitivity,
-                       int radius, int subpel, int overlap, int matrix, int src_bgr, const unsigned char* prev_luma, const unsigned short* prev_out88,
-                       const unsigned char* prev_pyr, unsigned char* luma, unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf,
-                       unsigned char* work, float* dst, hipStream_t s) {
-    const int L = lay.levels, Ho = lay.h[0], Wo = lay.w[0], N = frames;
-    const BatchLay B = batch_lay(lay, subpel, N);
+// arguments: checked by the caller (fs_api.hip)
+int temporal_run(const TemporalCall& c, hipStream_t s) {
+    fs_temporal_pyr_info lay;
+    if (fs_temporal_pyr_layout(c.Ho, c.Wo, c.levels, &lay)) return -1;                   // (cannot happen: the caller checked all three)
+    const int L = c.levels, Ho = c.Ho, Wo = c.Wo, N = c.frames;
+    const BatchLay B = batch_lay(lay, c.subpel, N);
     FrameSel S;
-    S.work = work; S.slot = B.slot; S.frames = N;
-    const FrameBuf FL = {luma, prev_luma, B.luma_off};
-    const FrameBuf FMV = {(unsigned char*)mv, nullptr, B.mv_off}, FMVF = {(unsigned char*)mvf, nullptr, B.mvf_off};
-    FrameBuf FPL[FS_TEMPORAL_MAX_LEVELS], FPV[FS_TEMPORAL_MAX_LEVELS];                    // the levels' lumas and vectors; entry 0: level 0's
-    FPL[0] = FL; FPV[0] = FMV;
+    S.work = c.work; S.slot = B.slot; S.frames = N;
+    const FrameBuf FMV = {(unsigned char*)c.mv, nullptr, B.mv_off}, FMVF = {(unsigned char*)c.mvf, nullptr, B.mvf_off};
+    FrameBuf FPL[FS_TEMPORAL_MAX_LEVELS], FPV[FS_TEMPORAL_MAX_LEVELS];                    // the levels' lumas and vectors
+    FPL[0] = {c.luma, c.prev_luma, B.luma_off}; FPV[0] = FMV;
     for (int l = 1; l < L; ++l) {
-        FPL[l] = {pyr + lay.luma_offset[l], prev_luma == nullptr ? nullptr : prev_pyr + lay.luma_offset[l], B.pyr_off + lay.luma_offset[l]};
-        FPV[l] = {pyr + lay.mv_offset[l], nullptr, B.pyr_off + lay.mv_offset[l]};
+        FPL[l] = {c.pyr + lay.luma_offset[l], c.prev_luma == nullptr ? nullptr : c.prev_pyr + lay.luma_offset[l], B.pyr_off + lay.luma_offset[l]};
+        FPV[l] = {c.pyr + lay.mv_offset[l], nullptr, B.pyr_off + lay.mv_offset[l]};
     }
-    const int kr = matrix ? 13933 : 19595, kg = matrix ? 46871 : 38470, kb = matrix ? 4732 : 7471;      // each triple sums to 65536
+    const int kr = c.matrix ? 13933 : 19595, kg = c.matrix ? 46871 : 38470, kb = c.matrix ? 4732 : 7471;  // each triple sums to 65536
     LumaArgs LA;
-    LA.H = H; LA.W = W; LA.Ho = Ho; LA.Wo = Wo;
-    LA.k0 = src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = src_bgr ? kr : kb;
+    LA.H = c.H; LA.W = c.W; LA.Ho = Ho; LA.Wo = Wo;
+    LA.k0 = c.src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = c.src_bgr ? kr : kb;
     const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
     const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
-    hipLaunchKernelGGL(temporal_luma_batch_kernel, dim3(egrid.x, (unsigned)N), block, 0, s, LA, S, FL, src);
+    if (N == 1)                                             // (one frame: the entries without a frame index, here and below)
+        hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, c.src, c.luma);
+    else
+        hipLaunchKernelGGL(temporal_luma_batch_kernel, dim3(egrid.x, (unsigned)N), block, 0, s, LA, S, FPL[0], c.src);
     if (L > 1) {
         PyrArgs PA;
         PA.H0 = Ho; PA.W0 = Wo; PA.H1 = lay.h[1]; PA.W1 = lay.w[1];
         PA.H2 = L > 2 ? lay.h[2] : 0; PA.W2 = L > 2 ? lay.w[2] : 0;
-        const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);
-        hipLaunchKernelGGL(temporal_pyramid_batch_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks, (unsigned)N), block, 0, s, PA, S, FL, FPL[1],
-                           L > 2 ? FPL[2] : FPL[1]);
+        const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);            // (W1 >= W2; at most 2^21 columns: within grid.y)
+        if (N == 1)
+            hipLaunchKernelGGL(temporal_pyramid_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks), block, 0, s, PA, (const unsigned char*)c.luma, FPL[1].last,
+                               L > 2 ? FPL[2].last : nullptr);
+        else
+            hipLaunchKernelGGL(temporal_pyramid_batch_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks, (unsigned)N), block, 0, s, PA, S, FPL[0], FPL[1],
+                               L > 2 ? FPL[2] : FPL[1]);
     }
-    for (int l = L - 1; l >= 0; --l)                        // coarsest first, as in temporal_pyr_f32
-        hipLaunchKernelGGL(temporal_search_batch_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l], (unsigned)N), block, 0, s, S, FPL[l], lay.h[l],
-                           lay.w[l], radius, l == L - 1 ? FPV[l] : FPV[l + 1], l == L - 1 ? 0 : 1, l == L - 1 ? 0 : lay.nbx[l + 1],
-                           2 * radius * ((1 << (L - 1 - l)) - 1), FPV[l]);
-    const int hold = radius * ((1 << L) - 1);
-    if (subpel > 0)
-        hipLaunchKernelGGL(temporal_subpel_batch_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0], (unsigned)N), block, 0, s, S, FL, Ho, Wo, radius,
-                           hold, subpel, FMV, FMVF);
+    for (int l = L - 1; l >= 0; --l) {                      // coarsest first: level l reads the vectors level l + 1 wrote
+        const bool top = l == L - 1;
+        const int pnbx = top ? 0 : lay.nbx[l + 1], lhold = 2 * c.radius * ((1 << (L - 1 - l)) - 1);
+        if (N == 1)
+            hipLaunchKernelGGL(temporal_search_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l]), block, 0, s, (const unsigned char*)FPL[l].last,
+                               FPL[l].before, lay.h[l], lay.w[l], c.radius, top ? nullptr : (const signed char*)FPV[l + 1].last, pnbx, lhold,
+                               (signed char*)FPV[l].last);
+        else
+            hipLaunchKernelGGL(temporal_search_batch_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l], (unsigned)N), block, 0, s, S, FPL[l], lay.h[l],
+                               lay.w[l], c.radius, top ? FPV[l] : FPV[l + 1], top ? 0 : 1, pnbx, lhold, FPV[l]);
+    }
+    const int hold = c.radius * ((1 << L) - 1);
+    if (c.subpel > 0 && N == 1)
+        hipLaunchKernelGGL(temporal_subpel_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0]), block, 0, s, (const unsigned char*)c.luma, c.prev_luma,
+                           Ho, Wo, c.radius, hold, c.subpel, (const signed char*)c.mv, c.mvf);
+    else if (c.subpel > 0)
+        hipLaunchKernelGGL(temporal_subpel_batch_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0], (unsigned)N), block, 0, s, S, FPL[0], Ho, Wo,
+                           c.radius, hold, c.subpel, FMV, FMVF);
     BlendArgs BA;
-    BA.Ho = Ho; BA.Wo = Wo; BA.nbx = lay.nbx[0];
-    BA.strength_q8 = strength_q8; BA.sensitivity = sensitivity; BA.R = hold;
+    BA.Ho = Ho; BA.Wo = Wo; BA.nby = lay.nby[0]; BA.nbx = lay.nbx[0];
+    BA.strength_q8 = c.strength_q8; BA.sensitivity = c.sensitivity; BA.R = hold;
     const size_t image = (size_t)Ho * Wo * 3;
     for (int i = 0; i < N; ++i) {                           // in order: frame i reads the out88 frame i - 1 wrote (the two in `work` alternate)
-        const bool last = i == N - 1;
-        const unsigned char* c8 = last ? luma : work + (size_t)i * B.slot + B.luma_off;
-        const unsigned char* p8 = i == 0 ? prev_luma : work + (size_t)(i - 1) * B.slot + B.luma_off;
-        const unsigned short* p88 = i == 0 ? prev_out88 : (const unsigned short*)(work + B.o88_off + (size_t)((i - 1) & 1) * B.o88_size);
-        unsigned short* o88 = last ? out88 : (unsigned short*)(work + B.o88_off + (size_t)(i & 1) * B.o88_size);
-        const signed char* v = (const signed char*)(last ? (unsigned char*)mv : work + (size_t)i * B.slot + B.mv_off);
-        const signed char* vf = subpel > 0 ? (const signed char*)(last ? (unsigned char*)mvf : work + (size_t)i * B.slot + B.mvf_off) : nullptr;
-        if (overlap)
-            hipLaunchKernelGGL(temporal_blend_obmc_kernel, egrid, block, 0, s, BA, lay.nby[0], cur + i * image, c8, p8, p88, v, vf, dst + i * image, o88);
-        else if (subpel > 0)
-            hipLaunchKernelGGL(temporal_blend_sub_kernel, egrid, block, 0, s, BA, cur + i * image, c8, p8, p88, v, vf, dst + i * image, o88);
+        const bool last = i == N - 1;                       // (i == 0 and the last frame take state pointers only: `work` may be null with one frame)
+        const unsigned char* c8 = last ? c.luma : c.work + (size_t)i * B.slot + B.luma_off;
+        const unsigned char* p8 = i == 0 ? c.prev_luma : c.work + (size_t)(i - 1) * B.slot + B.luma_off;
+        const unsigned short* p88 = i == 0 ? c.prev_out88 : (const unsigned short*)(c.work + B.o88_off + (size_t)((i - 1) & 1) * B.o88_size);
+        unsigned short* o88 = last ? c.out88 : (unsigned short*)(c.work + B.o88_off + (size_t)(i & 1) * B.o88_size);
+        const signed char* v = (const signed char*)(last ? (unsigned char*)c.mv : c.work + (size_t)i * B.slot + B.mv_off);
+        const signed char* vf = c.subpel > 0 ? (const signed char*)(last ? (unsigned char*)c.mvf : c.work + (size_t)i * B.slot + B.mvf_off) : nullptr;
+        if (c.overlap)
+            hipLaunchKernelGGL(temporal_blend_obmc_kernel, egrid, block, 0, s, BA, c.cur + i * image, c8, p8, p88, v, vf, c.dst + i * image, o88);
+        else if (c.subpel > 0)
+            hipLaunchKernelGGL(temporal_blend_sub_kernel, egrid, block, 0, s, BA, c.cur + i * image, c8, p8, p88, v, vf, c.dst + i * image, o88);
         else
-            hipLaunchKernelGGL(temporal_blend_kernel, egrid, block, 0, s, BA, cur + i * image, c8, p8, p88, v, dst + i * image, o88);
+            hipLaunchKernelGGL(temporal_blend_kernel, egrid, block, 0, s, BA, c.cur + i * image, c8, p8, p88, v, c.dst + i * image, o88);
     }
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -1078,7 +1078,7 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
         up = self.mem.upload_u8
         slot = (up(np.zeros((Ho, Wo), np.uint8)), up(np.zeros((Ho, Wo, 3, 2), np.uint8)), up(np.zeros(((Ho + 15) // 16, (Wo + 15) // 16, 2), np.uint8)))
         if subpel != 0:
-            self._temporal_sub_check(levels, subpel)
+            self._temporal_whole(levels=levels, subpel=subpel)
         if levels != 1:
             slot = slot + (up(np.zeros((int(self.temporal_pyr_layout(Ho, Wo, levels).pyr_bytes),), np.uint8)),)
         if subpel != 0:
@@ -1108,106 +1108,44 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
         fs_temporal_pyr_f32, the coarse-to-fine search, on slots of temporal_state(Ho, Wo, levels).  subpel 1 / 2: fs_temporal_sub_f32, vectors
         in half / quarter pixels and a bilinear fetch, on slots of temporal_state(Ho, Wo, levels, subpel).  overlap 1: fs_temporal_obmc_f32,
         every pixel blended along the vectors of the four blocks around it, on the slots that (levels, subpel) take without it."""
-        self._sync_stream()
-        if overlap != 0:
-            return self._temporal_obmc_f32(src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel, overlap)
-        if subpel != 0:
-            return self._temporal_sub_f32(src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel)
-        if levels != 1:
-            return self._temporal_pyr_f32(src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels)
-        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
-        if len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,):
-            ss, cs, ds = ss[1:], cs[1:], ds[1:]
-        if len(ss) != 3 or len(cs) != 3 or ss[2] != 3 or cs[2] != 3 or ds != cs:
-            raise L.FaststyleError("temporal_f32: source %s / current %s / destination %s do not belong together (one image per call)" %
-                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
-        Ho, Wo = cs[:2]
-        want = ((Ho, Wo), (Ho, Wo, 3, 2), ((Ho + 15) // 16, (Wo + 15) // 16, 2))
-        for name, slot in (("state", state), ("prev", prev)):
-            if slot is not None and (len(slot) != 3 or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
-                raise L.FaststyleError("temporal_f32: %s is not the slot of a %dx%d output (temporal_state)" % (name, Ho, Wo))
-        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
-        p8 = self.mem.ptr_u8
-        L.check(self.lib, self.lib.fs_temporal_f32(self.ctx, self.mem.ptr(src), ss[0], ss[1], self.mem.ptr(cur), Ho, Wo, int(strength_q8),
-                                                   int(sensitivity), int(radius), int(matrix), 1 if src_bgr else 0,
-                                                   None if prev is None else p8(prev[0]), None if prev is None else p8(prev[1]),
-                                                   p8(state[0]), p8(state[1]), p8(state[2]), self.mem.ptr(dst)), "fs_temporal_f32")
-        return dst
-
-    def _temporal_pyr_f32(self, src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels):
-        """temporal_f32 with levels > 1: the same shape checks with the fourth buffer held against the layout, then fs_temporal_pyr_f32."""
-        if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= levels <= 3:
-            raise L.FaststyleError("temporal_f32: levels must be a whole number in [1, 3], got %r" % (levels,))
-        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
-        if len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,):
-            ss, cs, ds = ss[1:], cs[1:], ds[1:]
-        if len(ss) != 3 or len(cs) != 3 or ss[2] != 3 or cs[2] != 3 or ds != cs:
-            raise L.FaststyleError("temporal_f32: source %s / current %s / destination %s do not belong together (one image per call)" %
-                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
-        Ho, Wo = cs[:2]
-        lay = self.temporal_pyr_layout(Ho, Wo, levels)
-        want = ((Ho, Wo), (Ho, Wo, 3, 2), ((Ho + 15) // 16, (Wo + 15) // 16, 2), (int(lay.pyr_bytes),))
-        for name, slot in (("state", state), ("prev", prev)):
-            if slot is not None and (len(slot) != 4 or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
-                raise L.FaststyleError("temporal_f32: %s is not the slot of a %dx%d output with %d levels (temporal_state)" % (name, Ho, Wo, levels))
-        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
-        p8 = self.mem.ptr_u8
-        pl, po, pp = (None, None, None) if prev is None else (p8(prev[0]), p8(prev[1]), p8(prev[3]))
-        L.check(self.lib, self.lib.fs_temporal_pyr_f32(self.ctx, self.mem.ptr(src), ss[0], ss[1], self.mem.ptr(cur), Ho, Wo, int(strength_q8),
-                                                       int(sensitivity), int(radius), int(levels), int(matrix), 1 if src_bgr else 0, pl, po, pp,
-                                                       p8(state[0]), p8(state[1]), p8(state[3]), p8(state[2]), self.mem.ptr(dst)),
-                "fs_temporal_pyr_f32")
-        return dst
+        return self._temporal_call("temporal_f32", False, src, cur, dst, state, None, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels,
+                                   subpel, overlap)
 
     @staticmethod
-    def _temporal_sub_check(levels, subpel):
-        for name, v, lo, hi in (("levels", levels, 1, 3), ("subpel", subpel, 0, 2)):
+    def _temporal_whole(who="temporal_f32", **options):
+        """The temporal options given by name are whole numbers in their ranges."""
+        for name, v in options.items():
+            lo, hi = {"levels": (1, 3), "subpel": (0, 2), "overlap": (0, 1)}[name]
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-                raise L.FaststyleError("temporal_f32: %s must be a whole number in [%d, %d], got %r" % (name, lo, hi, v))
+                raise L.FaststyleError("%s: %s must be a whole number in [%d, %d], got %r" % (who, name, lo, hi, v))
 
-    def _temporal_sub_f32(self, src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel):
-        """temporal_f32 with subpel > 0: the shape checks with the slot held against (levels, subpel) -- the pyramid buffer fourth when levels
-        > 1, mvf last --, then fs_temporal_sub_f32."""
-        self._temporal_sub_check(levels, subpel)
-        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
-        if len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,):
-            ss, cs, ds = ss[1:], cs[1:], ds[1:]
-        if len(ss) != 3 or len(cs) != 3 or ss[2] != 3 or cs[2] != 3 or ds != cs:
-            raise L.FaststyleError("temporal_f32: source %s / current %s / destination %s do not belong together (one image per call)" %
-                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
-        Ho, Wo = cs[:2]
-        blocks = ((Ho + 15) // 16, (Wo + 15) // 16, 2)
-        want = ((Ho, Wo), (Ho, Wo, 3, 2), blocks)
-        if levels > 1:
-            want += ((int(self.temporal_pyr_layout(Ho, Wo, levels).pyr_bytes),),)
-        want += (blocks,)
-        for name, slot in (("state", state), ("prev", prev)):
-            if slot is not None and (len(slot) != len(want) or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
-                raise L.FaststyleError("temporal_f32: %s is not the slot of a %dx%d output with %d levels and subpel %d (temporal_state)" %
-                                       (name, Ho, Wo, levels, subpel))
-        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
-        p8 = self.mem.ptr_u8
-        pyr = (lambda slot: p8(slot[3])) if levels > 1 else (lambda slot: None)
-        pl, po, pp = (None, None, None) if prev is None else (p8(prev[0]), p8(prev[1]), pyr(prev))
-        L.check(self.lib, self.lib.fs_temporal_sub_f32(self.ctx, self.mem.ptr(src), ss[0], ss[1], self.mem.ptr(cur), Ho, Wo, int(strength_q8),
-                                                       int(sensitivity), int(radius), int(levels), int(subpel), int(matrix),
-                                                       1 if src_bgr else 0, pl, po, pp, p8(state[0]), p8(state[1]), pyr(state), p8(state[2]),
-                                                       p8(state[-1]), self.mem.ptr(dst)), "fs_temporal_sub_f32")
-        return dst
+    # the single-frame entry points, narrowest first: (function, takes levels and the pyramid buffers, takes subpel and mvf, takes overlap)
+    _TEMPORAL_ENTRIES = (("fs_temporal_f32", False, False, False), ("fs_temporal_pyr_f32", True, False, False),
+                         ("fs_temporal_sub_f32", True, True, False), ("fs_temporal_obmc_f32", True, True, True))
 
-    def _temporal_obmc_f32(self, src, cur, dst, state, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel, overlap):
-        """temporal_f32 with overlap > 0: the shape checks with the slot held against (levels, subpel) as without it -- the pyramid buffer
-        fourth when levels > 1, mvf last when subpel > 0 --, then fs_temporal_obmc_f32."""
-        self._temporal_sub_check(levels, subpel)
-        if isinstance(overlap, bool) or not isinstance(overlap, (int, np.integer)) or not 0 <= overlap <= 1:
-            raise L.FaststyleError("temporal_f32: overlap must be a whole number in [0, 1], got %r" % (overlap,))
+    def _temporal_call(self, who, batch, src, cur, dst, state, work, prev, strength_q8, sensitivity, radius, matrix, src_bgr, levels, subpel, overlap):
+        """temporal_f32 (one image; the narrowest entry point that takes the keys that are not at their defaults, so that every exported
+        wrapper is reached through it) and temporal_batch_f32 (batch: N frames, fs_temporal_batch_f32): the options' and shapes' checks, the
+        slots held against (levels, subpel) -- the pyramid buffer fourth when levels > 1, mvf last when subpel > 0 --, then the call."""
+        self._sync_stream()
+        fn, has_levels, has_subpel, has_overlap = ("fs_temporal_batch_f32", True, True, True) if batch else \
+            self._TEMPORAL_ENTRIES[3 if overlap != 0 else 2 if subpel != 0 else 1 if levels != 1 else 0]
+        if has_levels:                                      # (an option the function lacks is at its default)
+            self._temporal_whole(levels=levels)
+        if has_subpel:
+            self._temporal_whole(subpel=subpel)
+        if has_overlap:
+            self._temporal_whole(who, overlap=overlap)
         ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
-        if len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,):
-            ss, cs, ds = ss[1:], cs[1:], ds[1:]
-        if len(ss) != 3 or len(cs) != 3 or ss[2] != 3 or cs[2] != 3 or ds != cs:
-            raise L.FaststyleError("temporal_f32: source %s / current %s / destination %s do not belong together (one image per call)" %
-                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
-        Ho, Wo = cs[:2]
+        if not batch and not (len(ss) == 4 and len(cs) == 4 and ss[0] == 1 and cs[0] == 1 and ds[:1] == (1,)):
+            ss, cs, ds = (1,) + ss, (1,) + cs, (1,) + ds                                    # (one image: a leading axis of 1 is taken)
+        if len(ss) != 4 or len(cs) != 4 or ss[3] != 3 or cs[3] != 3 or ds != cs or ss[0] != cs[0]:
+            raise L.FaststyleError("%s: source %s / current %s / destination %s do not belong together (%s)" %
+                                   (who, tuple(src.shape), tuple(cur.shape), tuple(dst.shape),
+                                    "[N,H,W,3] / [N,Ho,Wo,3] each" if batch else "one image per call"))
+        N, Ho, Wo = cs[:3]
+        if not 1 <= N <= 64:
+            raise L.FaststyleError("%s: 1 to 64 frames per call, got %d" % (who, N))
         blocks = ((Ho + 15) // 16, (Wo + 15) // 16, 2)
         want = ((Ho, Wo), (Ho, Wo, 3, 2), blocks)
         if levels > 1:
@@ -1216,16 +1154,24 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
             want += (blocks,)
         for name, slot in (("state", state), ("prev", prev)):
             if slot is not None and (len(slot) != len(want) or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
-                raise L.FaststyleError("temporal_f32: %s is not the slot of a %dx%d output with %d levels and subpel %d (temporal_state)" %
-                                       (name, Ho, Wo, levels, subpel))
+                raise L.FaststyleError("%s: %s is not the slot of a %dx%d output%s (temporal_state)" % (
+                    who, name, Ho, Wo, " with %d levels and subpel %d" % (levels, subpel) if has_subpel else
+                    " with %d levels" % levels if has_levels else ""))
+        nbytes = 0 if work is None else int(np.prod(work.shape))
+        if batch:
+            need = int(self.temporal_batch_layout(Ho, Wo, N, levels, subpel).work_bytes)
+            if nbytes < need:
+                raise L.FaststyleError("%s: %d frames of %dx%d need a work buffer of %d bytes (temporal_batch_work), got %d" %
+                                       (who, N, Ho, Wo, need, nbytes))
         matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
         p8 = self.mem.ptr_u8
         pyr = (lambda slot: p8(slot[3])) if levels > 1 else (lambda slot: None)
         pl, po, pp = (None, None, None) if prev is None else (p8(prev[0]), p8(prev[1]), pyr(prev))
-        L.check(self.lib, self.lib.fs_temporal_obmc_f32(self.ctx, self.mem.ptr(src), ss[0], ss[1], self.mem.ptr(cur), Ho, Wo, int(strength_q8),
-                                                        int(sensitivity), int(radius), int(levels), int(subpel), int(overlap), int(matrix),
-                                                        1 if src_bgr else 0, pl, po, pp, p8(state[0]), p8(state[1]), pyr(state), p8(state[2]),
-                                                        p8(state[-1]) if subpel > 0 else None, self.mem.ptr(dst)), "fs_temporal_obmc_f32")
+        args = [self.ctx, self.mem.ptr(src), ss[1], ss[2], self.mem.ptr(cur), Ho, Wo] + [N] * batch + [int(strength_q8), int(sensitivity), int(radius)] + \
+            [int(levels)] * has_levels + [int(subpel)] * has_subpel + [int(overlap)] * has_overlap + [int(matrix), 1 if src_bgr else 0, pl, po] + \
+            [pp] * has_levels + [p8(state[0]), p8(state[1])] + [pyr(state)] * has_levels + [p8(state[2])] + \
+            [p8(state[-1]) if subpel > 0 else None] * has_subpel + [None if work is None else p8(work), nbytes] * batch + [self.mem.ptr(dst)]
+        L.check(self.lib, getattr(self.lib, fn)(*args), fn)
         return dst
 
     def temporal_batch_layout(self, Ho, Wo, frames, levels=1, subpel=0):
@@ -1247,42 +1193,8 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
         [N,Ho,Wo,3] (dst may be cur), state the slot that receives frame N - 1's state, prev the slot the previous call wrote (None: no previous
         frame before frame 0), both temporal_state(Ho, Wo, levels, subpel)'s; work temporal_batch_work's for at least N frames.  dst[i] is what
         the i-th of N chained temporal_f32 calls gives, bit for bit."""
-        self._sync_stream()
-        self._temporal_sub_check(levels, subpel)
-        if isinstance(overlap, bool) or not isinstance(overlap, (int, np.integer)) or not 0 <= overlap <= 1:
-            raise L.FaststyleError("temporal_batch_f32: overlap must be a whole number in [0, 1], got %r" % (overlap,))
-        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
-        if len(ss) != 4 or len(cs) != 4 or ss[3] != 3 or cs[3] != 3 or ds != cs or ss[0] != cs[0]:
-            raise L.FaststyleError("temporal_batch_f32: source %s / current %s / destination %s do not belong together ([N,H,W,3] / [N,Ho,Wo,3] each)" %
-                                   (tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
-        N, Ho, Wo = cs[:3]
-        if not 1 <= N <= 64:
-            raise L.FaststyleError("temporal_batch_f32: 1 to 64 frames per call, got %d" % N)
-        blocks = ((Ho + 15) // 16, (Wo + 15) // 16, 2)
-        want = ((Ho, Wo), (Ho, Wo, 3, 2), blocks)
-        if levels > 1:
-            want += ((int(self.temporal_pyr_layout(Ho, Wo, levels).pyr_bytes),),)
-        if subpel > 0:
-            want += (blocks,)
-        for name, slot in (("state", state), ("prev", prev)):
-            if slot is not None and (len(slot) != len(want) or tuple(tuple(int(d) for d in b.shape) for b in slot) != want):
-                raise L.FaststyleError("temporal_batch_f32: %s is not the slot of a %dx%d output with %d levels and subpel %d (temporal_state)" %
-                                       (name, Ho, Wo, levels, subpel))
-        need = int(self.temporal_batch_layout(Ho, Wo, N, levels, subpel).work_bytes)
-        nbytes = 0 if work is None else int(np.prod(work.shape))
-        if nbytes < need:
-            raise L.FaststyleError("temporal_batch_f32: %d frames of %dx%d need a work buffer of %d bytes (temporal_batch_work), got %d" %
-                                   (N, Ho, Wo, need, nbytes))
-        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
-        p8 = self.mem.ptr_u8
-        pyr = (lambda slot: p8(slot[3])) if levels > 1 else (lambda slot: None)
-        pl, po, pp = (None, None, None) if prev is None else (p8(prev[0]), p8(prev[1]), pyr(prev))
-        L.check(self.lib, self.lib.fs_temporal_batch_f32(self.ctx, self.mem.ptr(src), ss[1], ss[2], self.mem.ptr(cur), Ho, Wo, N, int(strength_q8),
-                                                         int(sensitivity), int(radius), int(levels), int(subpel), int(overlap), int(matrix),
-                                                         1 if src_bgr else 0, pl, po, pp, p8(state[0]), p8(state[1]), pyr(state), p8(state[2]),
-                                                         p8(state[-1]) if subpel > 0 else None, None if work is None else p8(work), nbytes,
-                                                         self.mem.ptr(dst)), "fs_temporal_batch_f32")
-        return dst
+        return self._temporal_call("temporal_batch_f32", True, src, cur, dst, state, work, prev, strength_q8, sensitivity, radius, matrix, src_bgr,
+                                   levels, subpel, overlap)
 
     def temporal_batch_vectors(self, work, state, Ho, Wo, frames, levels=1, subpel=0):
         """For tests and motion_vectors(): the vectors of every frame of the last temporal_batch_f32 call as host arrays -> (mv int8
