@@ -223,6 +223,7 @@ PROTOTYPES = {
     "fs_yuv_deep_to_f32": (c_int, [c_void_p, POINTER(fs_yuv_desc), c_void_p, c_int, c_int, c_void_p]),
     "fs_f32_to_yuv_deep": (c_int, [c_void_p, POINTER(fs_yuv_desc), c_void_p, c_int, c_int, c_void_p]),
     "fs_compose_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fs_mix_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "fs_temporal_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "fs_temporal_pyr_layout": (c_int, [c_int, c_int, c_int, POINTER(fs_temporal_pyr_info)]),

@@ -157,4 +157,17 @@ def stylize_webcam_parser():
         ('--frame_filter', dict(default=argparse.SUPPRESS, choices=['box', 'bilinear', 'bicubic', 'lanczos'], metavar='F',
                                 help="(addition) with --video_depth stream, a --video_in of 9 to 16 bits and --frame_size: resample the stream's fp32 "
                                      "frames to W x H with this filter on the device (without it --frame_size refuses such a stream)")),
+        ('--model_path2', dict(default=argparse.SUPPRESS, metavar='CKPT',
+                               help="(addition) checkpoint prefix of a second trained net (same --upsample_method): every frame goes through both "
+                                    "and the two fp32 outputs are mixed on the device ahead of every later stage; needs --style_mix, --mix_mask or "
+                                    "--mix_fade; with --frames_dir, --video_in and the camera")),
+        ('--style_mix', dict(default=argparse.SUPPRESS, type=float, metavar='T',
+                             help="(addition) share of the second model, 0..1 (default 1): 0 shows --model_path, 1 --model_path2; a model nobody "
+                                  "will see is not run")),
+        ('--mix_mask', dict(default=argparse.SUPPRESS, metavar='FILE',
+                            help="(addition) a grey image of the net's input size (after --frame_size): 0 shows --model_path at that pixel, 255 "
+                                 "the mix, values between blend")),
+        ('--mix_fade', dict(default=argparse.SUPPRESS, nargs=2, type=int, metavar=('F0', 'F1'),
+                            help="(addition) cross-fade: the share of the second model rises from 0 at frame F0 to --style_mix at frame F1 "
+                                 "(0-based, 0 <= F0 < F1); with --frames_dir and --video_in")),
     ])

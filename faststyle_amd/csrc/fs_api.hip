@@ -240,6 +240,18 @@ int fs_compose_f32(fs_ctx* ctx, const float* src, int H, int W, const float* net
     const int rc = fs::compose_f32(src, H, W, net, Ho, Wo, N, strength_q8, keep_color ? 1 : 0, matrix, bgr & 1, bgr >> 1, mask, dst, ctx->stream);
     return rc ? fail(rc, "fs_compose_f32: launch failed (%d)", rc) : 0;
 }
+int fs_mix_f32(fs_ctx* ctx, const float* a, const float* b, int H, int W, int Ho, int Wo, int N, int weight_q8, const int* weight_dev,
+               const unsigned char* mask, float* dst) {
+    if (!ctx || !a || !b || !dst) return fail(-1, "fs_mix_f32: null argument");
+    if (N < 1 || N > 65535) return fail(-1, "fs_mix_f32: N must be in [1, 65535], got %d", N);
+    if (H < 1 || W < 1 || Ho < H || Ho - H > 3 || Wo < W || Wo - W > 3)
+        return fail(-1, "fs_mix_f32: a %dx%d net input does not belong to %dx%d net outputs (at least the input's size, at most 3 more)", H, W, Ho, Wo);
+    if (!weight_dev && (weight_q8 < 0 || weight_q8 > 256)) return fail(-2, "fs_mix_f32: weight_q8 must be in [0, 256], got %d", weight_q8);
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)dst | (uintptr_t)weight_dev) & 3)
+        return fail(-5, "fs_mix_f32: a, b, dst and weight_dev must be 4-byte aligned");
+    const int rc = fs::mix_f32(a, b, H, W, Ho, Wo, N, weight_dev ? 0 : weight_q8, weight_dev, mask, dst, ctx->stream);
+    return rc ? fail(rc, "fs_mix_f32: launch failed (%d)", rc) : 0;
+}
 // The checks of every fs_temporal_*_f32 entry point, once: fn is the called function's name, c its arguments with the options its signature
 // lacks at their defaults (levels 1, subpel 0, overlap 0, frames 1, null buffers), which pass their checks -- so a narrower function checks
 // what it always did, in the same order.

@@ -694,6 +694,9 @@ int f32_to_yuv_deep(const ::fs_yuv_desc& desc, const float* src, int swap_rb, in
 // the net's output blended towards its input on the 8.8 scale (fs_compose.hip): the launch (argument checks are in fs_api.hip)
 int compose_f32(const float* src, int H, int W, const float* net, int Ho, int Wo, int N, int strength_q8, int keep_color, int matrix, int bgr,
                 int src_swap, const unsigned char* mask, float* dst, hipStream_t s);
+// two nets' outputs merged on the 8.8 scale, by a weight per image and a mask (fs_mix.hip): the launch (argument checks are in fs_api.hip)
+int mix_f32(const float* a, const float* b, int H, int W, int Ho, int Wo, int N, int weight_q8, const int* weight_dev, const unsigned char* mask,
+            float* dst, hipStream_t s);
 // temporal stabilisation (fs_temporal.hip): one call of any of the fs_temporal_*_f32 entry points, in the argument order of
 // fs_temporal_batch_f32.  An entry point without an option leaves it at levels 1, subpel 0, overlap 0, frames 1 and its buffer null (pyr and
 // prev_pyr, mvf, work).  fs_api.hip checks a call; temporal_run launches a checked one: luma, pyramid (levels > 1), one search per level,

@@ -997,6 +997,63 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
                 "fs_compose_f32")
         return dst
 
+    # ------------------------------------------------------------------ two nets' outputs merged (csrc/fs_mix.hip)
+    def i32_buffer(self, values):
+        """A device buffer of int32 entries holding ``values``: the memory backend's uint8 buffer of four bytes per entry (both backends
+        allocate at 16 bytes or better), which mix_f32(weights=) and i32_upload take."""
+        return self.mem.upload_u8(np.ascontiguousarray(values, dtype="<i4").reshape(-1).view(np.uint8))
+
+    def i32_staging(self, n):
+        """A host staging buffer of n int32 entries for i32_upload (pinned on the GPU engine): (numpy int32 view, the buffer)."""
+        if hasattr(self.mem, "torch"):
+            t = self.mem.torch.zeros(4 * int(n), dtype=self.mem.torch.uint8, pin_memory=True)
+            return t.numpy().view("<i4"), t
+        a = np.zeros(int(n), "<i4")
+        return a, a.view(np.uint8)
+
+    def i32_upload(self, buf, values, staging):
+        """``values`` -> the entries of an i32_buffer, through ``staging`` (i32_staging's) with an asynchronous copy on the current stream:
+        the host does not wait, and the caller rewrites the staging buffer only after that copy has completed."""
+        staging[0][...] = np.asarray(values, dtype="<i4").reshape(-1)
+        if hasattr(self.mem, "torch"):
+            buf.copy_(staging[1], non_blocking=True)
+        else:
+            buf[...] = staging[1]
+        return buf
+
+    def _i32_ptr(self, buf, n, what):
+        """The address of a device buffer of n int32 entries: an i32_buffer, or the backend's own int32 array"""
+        if str(buf.dtype).endswith("int32"):
+            ok, ptr = int(np.prod(tuple(buf.shape))) == n, (buf.data_ptr() if hasattr(buf, "data_ptr") else buf.ctypes.data)
+        else:
+            ok, ptr = str(buf.dtype).endswith("uint8") and int(np.prod(tuple(buf.shape))) == 4 * n, None
+            ptr = self.mem.ptr_u8(buf) if ok else None
+        if not ok:
+            raise L.FaststyleError("%s: the weights are a device buffer of %d int32 entries (i32_buffer), got %s %s" %
+                                   (what, n, tuple(buf.shape), buf.dtype))
+        return ptr
+
+    def mix_f32(self, a, b, dst, weight_q8=256, weights=None, mask=None, in_hw=None):
+        """fs_mix_f32: a, b and dst device float32 [Ho,Wo,3] / [N,Ho,Wo,3] (two nets' outputs and the mixed tensor; dst may be a or b, a may
+        be b) -> dst = a + (b - a) * weight / 256 * mask on the 8.8 scale.  weight_q8 in [0, 256] serves every image; weights: a device
+        buffer of N int32 entries (i32_buffer), one weight per image, read and clamped to [0, 256] by the kernel, takes its place.  mask:
+        device uint8 [H,W] at the net's input size in_hw = (H, W), H <= Ho <= H + 3 and W <= Wo <= W + 3; in_hw defaults to the mask's shape,
+        without a mask to (Ho, Wo)."""
+        self._sync_stream()
+        sa, sb, sd = (tuple(int(d) for d in t.shape) for t in (a, b, dst))
+        ms = None if mask is None else tuple(int(d) for d in mask.shape)
+        if in_hw is None:
+            in_hw = ms if ms is not None and len(ms) == 2 else sa[-3:-1]
+        in_hw = tuple(int(d) for d in in_hw)
+        if len(sa) not in (3, 4) or sa[-1] != 3 or sb != sa or sd != sa or len(in_hw) != 2 or (ms is not None and ms != in_hw):
+            raise L.FaststyleError("mix_f32: outputs %s and %s / destination %s / mask %s / input size %s do not belong together" %
+                                   (sa, sb, sd, ms, in_hw))
+        N = sa[0] if len(sa) == 4 else 1
+        L.check(self.lib, self.lib.fs_mix_f32(self.ctx, self.mem.ptr(a), self.mem.ptr(b), in_hw[0], in_hw[1], sa[-3], sa[-2], N, int(weight_q8),
+                                              None if weights is None else self._i32_ptr(weights, N, "mix_f32"),
+                                              None if mask is None else self.mem.ptr_u8(mask), self.mem.ptr(dst)), "fs_mix_f32")
+        return dst
+
     # ------------------------------------------------------------------ resampling between fp32 tensors (csrc/fs_resample.hip)
     def resample_f32(self, src, plan, dst):
         """fs_resample_f32: src device float32 [Hs,Ws,3] / [N,Hs,Ws,3] -> dst device float32 [Hd,Wd,3] / [N,Hd,Wd,3], Pillow's resize of

@@ -89,6 +89,17 @@ of the source at its own size, so that the source's edges return at the delivery
 ``source=`` of exactly the delivery's size that is resized to the net's, and reads the buffer the lane holds that source in anyway: the pixel
 frames, the decoded RGBX of JPEG and 8-bit ``yuv=`` sources, or the fp32 planes of a deep source with ``resample=``.  Not together with
 ``filter=``.
+
+Two styles per stream: with ``mix=dict(variables=, weight=1.0, mask=None)`` the lane holds a second parameter set with a workspace of its
+own, runs a second forward pass behind the first and merges the two fp32 outputs with one launch (fs_mix_f32, csrc/fs_mix.hip) into a mixed
+tensor of the lane's own, which compose, the temporal stage, delivery and every output conversion take where they took the net's output.
+``weight`` in [0, 1] (quantised as compose's strength) is the share of the second model, ``mask`` a host uint8 [H, W] at the net's input
+size, 0 shows the first model and 255 the mix.  The weight lives in a device buffer of one int32 per image, so that ``set_mix(weight)`` --
+a number, or ``batch`` numbers for a pass of consecutive frames -- changes it between passes without a new graph: the values go up with an
+asynchronous copy on the lane's stream ahead of the replay.  A model nobody will see is not run: model B is live if any weight of the pass
+is above 0, model A if there is a mask or any weight is below 1; the launch then reads the live model's output twice.  The head graph is
+captured per liveness kind ('a', 'b', 'ab') when the kind first occurs; ``last_forwards()`` names the last pass's.  Both forwards stay on the
+lane's one stream.  Without ``mix=`` nothing is allocated or launched and the lane captures the graph it always captured.
 """
 import ctypes
 
@@ -117,7 +128,7 @@ class FrameStylizer(object):
 
     def __init__(self, eng, variables, height, width, upsample_method="resize", batch=1, swap_rb=True, use_graph=True,
                  bf16=False, jpeg=None, jpeg_threads=4, source=None, yuv_out=None, compose=None, temporal=None, deliver=None,
-                 _temporal_slots=None):
+                 mix=None, _temporal_slots=None):
         self.eng = eng
         self.variables = variables
         self.method = upsample_method
@@ -179,6 +190,10 @@ class FrameStylizer(object):
         self._mask = None
         if compose is not None:
             self._compose_setup(dict(compose))
+        self.mix = None                  # with mix=: dict(mask=) -- the weights are state (set_mix), not options
+        self._mixed = None               # ... the mixed tensor compose and every later stage then read instead of the net's output
+        if mix is not None:
+            self._mix_setup(dict(mix))
         self.temporal = None             # with temporal=: dict(strength_q8=, sensitivity=, radius=, matrix=, source_bgr=) as the launch takes them
         self._stab = None                # ... the stabilised tensor every output conversion then reads
         self._tslots = None              # ... the two state slots (Engine.temporal_state), shared by the lanes of a PipelinedStylizer
@@ -342,6 +357,79 @@ class FrameStylizer(object):
         self.compose = dict(strength_q8=int(np.floor(s * 256.0 + 0.5)), keep_color=bool(kw.get("keep_color", False)), matrix=matrix,
                             mask=mask is not None, source_swapped=bool(kw.get("source_swapped", False)))
         self._composed = self.eng.mem.empty(self.out_shape)
+
+    MIX_KEYS = ("variables", "weight", "mask")
+
+    def _mix_q8_of(self, weight):
+        """set_mix's argument -> the batch's weights by 256: a number serves every image, a sequence names ``batch`` consecutive frames'.
+        Quantised as compose's strength, floor(t * 256 + 0.5)."""
+        B = self.shape[0]
+        try:
+            t = np.asarray(weight, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise L.FaststyleError("mix weight %r is not a number" % (weight,))
+        if t.ndim > 1 or (t.ndim == 1 and t.shape[0] != B):
+            raise L.FaststyleError("mix weight is a number or a sequence of %d numbers (the batch), got %r" % (B, weight))
+        if not np.all((t >= 0.0) & (t <= 1.0)):                  # (NaN fails both comparisons)
+            raise L.FaststyleError("mix weight must be in [0, 1], got %r" % (weight,))
+        return tuple(int(v) for v in np.broadcast_to(np.floor(t * 256.0 + 0.5).astype(np.int64), (B,)))
+
+    def _mix_setup(self, opt):
+        """The mix stage's fixed parts: the second parameter set's own workspace, the two nets' output tensors (one per model whichever
+        graph writes them), the mask on the device (once), the mixed tensor, the weight buffer and its host staging."""
+        kw = {k: opt.pop(k) for k in self.MIX_KEYS if k in opt}
+        if opt:
+            raise L.FaststyleError("mix takes %s, got also %r" % (", ".join(self.MIX_KEYS), opt))
+        if kw.get("variables") is None:
+            raise L.FaststyleError("mix needs variables, the second model's parameters")
+        e, mem = self.eng, self.eng.mem
+        q8 = self._mix_q8_of(kw.get("weight", 1.0))
+        mask = kw.get("mask")
+        self._mix_mask = None
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 or mask.shape != self.shape[1:3]:
+                raise L.FaststyleError("mix mask shape %s dtype %s, the net's input takes uint8 %s" % (mask.shape, mask.dtype, self.shape[1:3]))
+            self._mix_mask = mem.upload_u8(mask)
+        self.variables2 = kw["variables"]
+        self._ws2 = e.new_tnet_workspace(self.shape[0], self.shape[1], self.shape[2], self.bf16)
+        self._mix_ya = mem.empty(self.out_shape)
+        self._mix_yb = mem.empty(self.out_shape)
+        self._mixed = mem.empty(self.out_shape)
+        self._mix_q8 = q8                                        # the weights of the passes that follow (set_mix)
+        self._mix_w = e.i32_buffer(q8)                           # ... on the device, where the launch reads them
+        self._mix_w_q8 = q8                                      # ... as the device buffer holds them (or will, behind the copies enqueued)
+        self._mix_stage = e.i32_staging(self.shape[0])
+        self._mix_kind = None                                    # the liveness kind of the pass under way: 'a', 'b' or 'ab'
+        self._mix_graphs = {}                                    # captured heads by (kind, JPEG frames)
+        self.mix = dict(mask=mask is not None)
+
+    def set_mix(self, weight):
+        """The share of the second model in the passes that follow: a number in [0, 1], or ``batch`` numbers for a pass of consecutive
+        frames (mix= only).  Nothing is enqueued here; the next pass uploads the values ahead of its launches."""
+        if self.mix is None:
+            raise L.FaststyleError("set_mix: this stylizer was built without mix=")
+        self._mix_q8 = self._mix_q8_of(weight)
+
+    def _mix_prepare(self):
+        """Ahead of a pass (and of the capture of its graph): the weights into the device buffer where they changed -- an asynchronous
+        copy on the current stream, the lane's, from the lane's staging words, which the previous pass's download has long left behind --
+        and the liveness kind: B runs if any weight is above 0, A if there is a mask or any weight is below 256."""
+        q8 = self._mix_q8
+        if q8 != self._mix_w_q8:
+            self.eng.i32_upload(self._mix_w, q8, self._mix_stage)
+            self._mix_w_q8 = q8
+        a = self.mix["mask"] or min(q8) < 256
+        b = max(q8) > 0
+        self._mix_kind = "ab" if a and b else ("b" if b else "a")
+
+    def last_forwards(self):
+        """The models the last pass ran: ('a',), ('b',) or ('a', 'b') (mix= only)."""
+        if self.mix is None:
+            raise L.FaststyleError("last_forwards: this stylizer was built without mix=")
+        if self._y is None:
+            raise L.FaststyleError("last_forwards: this stylizer has not run a frame yet")
+        return tuple(self._mix_kind)
 
     YUV_KEYS = ("sampling", "siting", "matrix", "full_range", "components", "bits")
 
@@ -533,17 +621,37 @@ class FrameStylizer(object):
             e.cvresize_u8(self._pix_dst, self._src_plan, self._in_u8, swap_rb=self._src_swap)
         if not self._src_deep:                               # (a deep source has written self._in_f32 itself)
             e.u8_to_f32(self._in_u8, self._in_f32)
-        self._y = e.tnet_forward(self.variables, self._in_f32, upsample_method=self.method, bf16=self.bf16, frozen=True,   # one checkpoint, many frames
-                                 workspace=self._ws)
-        y = self._y
+        if self.mix is not None:                             # two models: the live ones, one behind the other, then their merge
+            y = self._mix_pass()
+        else:
+            self._y = e.tnet_forward(self.variables, self._in_f32, upsample_method=self.method, bf16=self.bf16, frozen=True,   # one checkpoint, many frames
+                                     workspace=self._ws)
+            y = self._y
         if self.compose is not None:                         # strength / colour / mask: every conversion below reads the composed tensor
             c = self.compose                                 # (the tensors are B,G,R exactly when the output conversion swaps)
-            y = e.compose_f32(self._in_f32, self._y, self._composed, strength_q8=c["strength_q8"], keep_color=c["keep_color"], matrix=c["matrix"],
+            y = e.compose_f32(self._in_f32, y, self._composed, strength_q8=c["strength_q8"], keep_color=c["keep_color"], matrix=c["matrix"],
                               bgr=self.swap_rb, mask=self._mask, src_swapped=c["source_swapped"])
         if self.temporal is not None:                        # the output conversions belong to the tail (_tail), which reads this
             self._cur = y
             return
         self._outputs(y)
+
+    def _mix_pass(self):
+        """The forward passes of the live models into the lane's two output tensors, on the lane's one stream, and fs_mix_f32 of the two; a
+        model that is not live lends the other's output, so that there is one arithmetic path (its weights are all 0, or all 256 without a
+        mask: the result is to88 of the live output either way).  Each parameter set has its own workspace: with both live the frozen-filter
+        check of fs_tnet_forward, which remembers one (parameters, workspace) pair, never matches and both re-layouts are rebuilt per pass;
+        a wrong reuse is impossible, since a workspace only ever holds its own parameter set's filters."""
+        e, kind = self.eng, self._mix_kind
+        if "a" in kind:
+            e.tnet_forward(self.variables, self._in_f32, upsample_method=self.method, bf16=self.bf16, frozen=True, workspace=self._ws,
+                           out=self._mix_ya)
+        if "b" in kind:
+            e.tnet_forward(self.variables2, self._in_f32, upsample_method=self.method, bf16=self.bf16, frozen=True, workspace=self._ws2,
+                           out=self._mix_yb)
+        self._y = self._mix_ya
+        return e.mix_f32(self._mix_ya if "a" in kind else self._mix_yb, self._mix_yb if "b" in kind else self._mix_ya, self._mixed,
+                         weights=self._mix_w, mask=self._mix_mask, in_hw=self.shape[1:3])
 
     def _outputs(self, y):
         """The output conversions of y: the net's output, the composed or the stabilised tensor; with deliver= of its top-left H x W
@@ -598,7 +706,9 @@ class FrameStylizer(object):
         whatever the input buffers hold, and the JPEG pass consumes its coefficients: callers capture BEFORE they upload a JPEG frame."""
         self.eng.invalidate_frozen()                       # the warm-up rebuilds the filters in self._ws whatever the library remembers
         g = self._captured(lambda: self._device_pass(jpeg_in))
-        if jpeg_in:
+        if self.mix is not None:                           # (one head per liveness kind; _mix_prepare has named this pass's)
+            self._mix_graphs[(self._mix_kind, jpeg_in)] = g
+        elif jpeg_in:
             self._graph_jpeg = g
         else:
             self._graph = g                                # (replays raw pointers into self._ws, which lives as long as this object)
@@ -608,8 +718,14 @@ class FrameStylizer(object):
         the tail follows: eager, or the replay of the graph of its kind (a first frame's, or the parity's), captured when first needed.
         before_tail: called between the two (a PipelinedStylizer's wait for the previous frame's tail on another stream)."""
         self._hi_jpeg = jpeg_in
+        if self.mix is not None:
+            self._mix_prepare()                            # (the weights go up ahead of the launches that read them)
         if not self._use_graph:
             self._device_pass(jpeg_in)
+        elif self.mix is not None:
+            if (self._mix_kind, jpeg_in) not in self._mix_graphs:      # (a JPEG pass's: captured by _upload_jpeg, ahead of the upload)
+                self._capture(jpeg_in)
+            self._mix_graphs[(self._mix_kind, jpeg_in)].replay()
         elif jpeg_in:
             self._graph_jpeg.replay()                      # (captured by _upload_jpeg, ahead of the upload)
         else:
@@ -641,7 +757,11 @@ class FrameStylizer(object):
     def _upload_jpeg(self, staging):
         """Decoded coefficients (decode_frames' staging) -> the device coefficient buffer, on the current stream."""
         mem = self.eng.mem
-        if self._use_graph and self._graph_jpeg is None:
+        if self.mix is not None:
+            self._mix_prepare()
+            if self._use_graph and (self._mix_kind, True) not in self._mix_graphs:
+                self._capture(True)
+        elif self._use_graph and self._graph_jpeg is None:
             self._capture(True)
         if hasattr(mem, "torch"):
             self._src_coef.copy_(staging[1], non_blocking=True)
@@ -653,6 +773,8 @@ class FrameStylizer(object):
         self._graph = None
         self._graph_jpeg = None
         self._tail_graphs = {}
+        if getattr(self, "mix", None) is not None:
+            self._mix_graphs = {}
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
@@ -671,7 +793,29 @@ class FrameStylizer(object):
         """For tests and inspection: a host float32 copy [B,Ho,Wo,3] of the net's output tensor of the last pass (synchronises)."""
         if self._y is None:
             raise L.FaststyleError("net_output: this stylizer has not run a frame yet")
+        if self.mix is not None and "a" not in self._mix_kind:
+            raise L.FaststyleError("net_output: the last pass did not run the first model (every weight was 1 and there is no mask)")
         return np.array(self.eng.mem.to_numpy(self._y), dtype=np.float32, copy=True).reshape(self.out_shape)
+
+    def net_output2(self):
+        """For tests and inspection: a host float32 copy [B,Ho,Wo,3] of the second model's output tensor of the last pass (synchronises);
+        a stylizer built without mix= has none, and a pass whose weights were all 0 did not run that model."""
+        if self.mix is None:
+            raise L.FaststyleError("net_output2: this stylizer was built without mix=")
+        if self._y is None:
+            raise L.FaststyleError("net_output2: this stylizer has not run a frame yet")
+        if "b" not in self._mix_kind:
+            raise L.FaststyleError("net_output2: the last pass did not run the second model (every weight was 0)")
+        return np.array(self.eng.mem.to_numpy(self._mix_yb), dtype=np.float32, copy=True)
+
+    def mixed_output(self):
+        """For tests and inspection: a host float32 copy [B,Ho,Wo,3] of the mixed tensor of the last pass (synchronises); a stylizer built
+        without mix= has none."""
+        if self.mix is None:
+            raise L.FaststyleError("mixed_output: this stylizer was built without mix=")
+        if self._y is None:
+            raise L.FaststyleError("mixed_output: this stylizer has not run a frame yet")
+        return np.array(self.eng.mem.to_numpy(self._mixed), dtype=np.float32, copy=True)
 
     def composed_output(self):
         """For tests and inspection: a host float32 copy [B,Ho,Wo,3] of the composed tensor of the last pass (synchronises); a stylizer built
@@ -803,7 +947,11 @@ class PipelinedStylizer(object):
     right behind frame n - 1's tail on the other lane's stream; the forward passes of two frames still overlap, and frame n + 1 overwrites
     the slot frame n reads only behind that chain.  Results equal the one-lane results, in order, for any depth.  reset() forgets the
     previous frame and is allowed with nothing in flight.  With temporal sequence=True and batch=N all of this goes by pass of N frames; every
-    lane has its own work buffer."""
+    lane has its own work buffer.
+
+    mix= is handed to every lane: each has its own second workspace, output tensors, mixed tensor, weight buffer and pinned staging words.
+    set_mix(weight) applies to the frames submitted after it: submit() hands the weights to the frame's lane, which uploads them on its own
+    stream ahead of its replay.  Results equal the one-lane results, in order, for any depth, also with temporal= and sequence lanes."""
 
     def __init__(self, eng, variables, height, width, depth=2, jpeg_threads=4, **kw):
         if not hasattr(eng.mem, "torch"):
@@ -821,6 +969,8 @@ class PipelinedStylizer(object):
         self.temporal = self.lanes[0].temporal
         self._tail_done = [torch.cuda.Event() for _ in self.lanes] if self.temporal is not None else None
         self._tframe = 0                                         # (temporal=) frames since construction or reset()
+        self.mix = self.lanes[0].mix
+        self._mix_q8 = self.lanes[0]._mix_q8 if self.mix is not None else None      # (mix=) the weights of the frames submitted from now on
         self.host_in = [torch.empty(ln.in_shape, dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
         self.host_out = [torch.empty(tuple(ln._result.shape), dtype=torch.uint8, pin_memory=True) for ln in self.lanes]
         self.jpeg = self.lanes[0].jpeg
@@ -876,6 +1026,8 @@ class PipelinedStylizer(object):
             if self._tframe > 0:
                 done = self._tail_done[(self._n - 1) % self.depth]
                 before_tail = lambda: st.wait_event(done)
+        if self.mix is not None:                                  # the lane uploads them on its stream, from its own pinned words,
+            ln._mix_q8 = self._mix_q8                             # ahead of its replay (its previous frame was fetched: the words are free)
         st.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(st):
             if files is not None:
@@ -911,6 +1063,13 @@ class PipelinedStylizer(object):
             raise L.FaststyleError("reset: %d frames in flight -- fetch() them first" % len(self._pending))
         self._tframe = 0
 
+    def set_mix(self, weight):
+        """The share of the second model in the frames submitted after this call (mix= only): a number in [0, 1], or ``batch`` numbers for
+        a pass of consecutive frames.  Frames in flight keep the weights they were submitted with."""
+        if self.mix is None:
+            raise L.FaststyleError("set_mix: this stylizer was built without mix=")
+        self._mix_q8 = self.lanes[0]._mix_q8_of(weight)
+
     def next_input(self):
         """The pinned input buffer of the lane the next submit() uses, as a numpy array of the lane's in_shape: a reader fills it in place
         (y4m.Reader.read_frame_into) and hands it -- or its first row, for a single frame -- to submit(), which then copies nothing on the
@@ -935,10 +1094,12 @@ class PipelinedStylizer(object):
         out = self.host_out[k].numpy().copy()
         return out[0] if single else out
 
-    def run(self, frames, not_taken=None):
+    def run(self, frames, not_taken=None, before_submit=None):
         """Results of ``frames`` in order, `depth` of them in flight.  JPEG frames (bytes) are decoded ahead on the thread pool, one frame
         per decode thread beyond the submitted ones: the Huffman pass of the next frames overlaps device work.  not_taken: called with the bytes of a
-        frame that raised FrameNotTaken, returns its pixels (the driver's PIL decode); without it the exception reaches the caller."""
+        frame that raised FrameNotTaken, returns its pixels (the driver's PIL decode); without it the exception reaches the caller.
+        before_submit: called ahead of every submit(), in order (a driver's set_mix() of that frame: frames are decoded ahead, so the
+        iterable itself runs ahead of the submits)."""
         import collections
         ahead = collections.deque()                              # (frame, decode future or None), in order
         it = iter(frames)
@@ -969,6 +1130,8 @@ class PipelinedStylizer(object):
                     f = not_taken(f)
             if len(self._pending) >= self.depth:
                 yield self.fetch()
+            if before_submit is not None:
+                before_submit()
             self.submit(f, _decoded=staged)
         while self._pending:
             yield self.fetch()

@@ -440,6 +440,35 @@ int fs_f32_to_yuv_deep(fs_ctx* ctx, const fs_yuv_desc* desc, const float* src, i
 int fs_compose_f32(fs_ctx* ctx, const float* src, int H, int W, const float* net, int Ho, int Wo, int N, int strength_q8, int keep_color,
                    int matrix, int bgr, const unsigned char* mask, float* dst);
 
+/* ---- Two styles per stream (csrc/fs_mix.hip): the fp32 outputs of two nets merged by a weight per image and an optional region mask, one
+ * elementwise launch between the two forward passes and fs_compose_f32 (or whichever stage or output conversion follows: each consumes the
+ * mixed tensor unchanged).  The arithmetic below is the contract (tests/test_mix.py restates it in numpy and compares exactly); it is
+ * integer throughout, on compose's unsigned 8.8 scale.
+ *
+ * Inputs per image: a and b [Ho, Wo, 3] fp32, the two nets' outputs; optionally mask [H, W] u8 at the net's INPUT size, H <= Ho <= H + 3 and
+ * W <= Wo <= W + 3 as in compose, read at (min(y, H - 1), min(x, W - 1)) and shared by the N images; a weight t in [0, 256], one for all
+ * images (weight_q8) or one int32 per image in device memory (weight_dev; weight_q8 is then ignored and every value read is clamped to
+ * [0, 256]).  No value read from a tensor, the mask or the weight buffer reaches an address.
+ *
+ * For output pixel (y, x) and channel c, to88 being compose's:
+ *   A_c = to88(a), B_c = to88(b).
+ *   weight     m = the mask byte, 255 without a mask; m' = m + (m >> 7); w = t * m', in [0, 65536].
+ *   result     F_c = A_c + (((int64)(B_c - A_c) * w + 32768) >> 16), the shift arithmetic (a floor); the output is (float)F_c * 0.00390625f,
+ *              which is exact.  No clamp: F is a convex combination of two values in [0, 65280] and the rounding cannot pass either end
+ *              (with D = B - A >= 0 the rounded term lies in [0, D], with D < 0 in [D, 0]) -- the argument DESIGN.md section 7h gives.
+ * Hence: t 0 or a mask byte 0 gives F = A = to88(a); t 256 without a mask or with mask byte 255 gives F = B = to88(b); t 128 between 0 and 255
+ * gives 32640; a == b gives to88 of it; and F >> 8 is the byte fs_f32_to_u8 writes, so a u8 / JPEG / 8-bit YCbCr conversion behind weight 0
+ * writes byte for byte what it writes for a, behind weight 256 what it writes for b. */
+
+/* N images: a, b, dst [N, Ho, Wo, 3]; mask [H, W] or null; weight_dev N int32 in device memory or null.  dst may be a or b and a may be b (a
+ * thread reads its pixels before it writes them).  Asynchronous on the ctx stream, allocates nothing, can be captured into a hipGraph -- with
+ * weight_dev one captured graph serves every weight; grid.y is the image.  A refused call launches nothing.  Errors: -1 null a / b / dst, N
+ * outside [1, 65535], H or W below 1, Ho outside [H, H + 3] or Wo outside [W, W + 3]; -2 weight_q8 outside [0, 256] when weight_dev is null;
+ * -5 a, b, dst or weight_dev not 4-byte aligned (Wo a multiple of 4 with the three tensors 16-byte aligned takes 16-byte accesses, and with
+ * W == Wo and a 4-byte aligned mask dwords; anything else single floats and bytes, with the same values). */
+int fs_mix_f32(fs_ctx* ctx, const float* a, const float* b, int H, int W, int Ho, int Wo, int N, int weight_q8, const int* weight_dev,
+               const unsigned char* mask, float* dst);
+
 /* ---- Temporal stabilisation (csrc/fs_temporal.hip): a recursive, motion-compensated blend of the tensor the output conversions would read
  * towards the previous frame's stabilised output, three launches behind the forward pass (or fs_compose_f32).  The arithmetic below is the
  * contract (tests/test_temporal.py restates it in numpy and compares for equality); it is integer throughout, on compose's unsigned 8.8 scale.

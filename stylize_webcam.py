@@ -62,6 +62,14 @@ frame at a time up to the net's own batch numerics.  A stream's last pass is pad
 are written.  Latency grows by N frames, so live pipes keep 1.  ``--precision bf16`` runs the net's mixed-precision path (resize-conv models
 only: not with --upsample_method deconv) with --frames_dir, --video_in and the camera.  Without the flags, or with ``--video_batch 1`` /
 ``--precision fp32``, nothing changes.
+
+Two styles: ``--model_path2 CKPT`` names a second model of the same --upsample_method; every frame goes through both nets and their fp32
+outputs are mixed on the device, one launch ahead of every stage above (faststyle_amd/stream.py, mix=).  ``--style_mix T`` (0..1, default 1)
+is the share of the second model, ``--mix_mask FILE`` (a grey image of the net's input size: 0 shows --model_path, 255 the mix) puts one style
+on a region and the other around it, and ``--mix_fade F0 F1`` cross-fades over the 0-based frames F0..F1 of --frames_dir or --video_in: frame
+n has the weight T min(max(n - F0, 0), F1 - F0) / (F1 - F0), in 256ths, rounded half up.  A model nobody will see is not run: before and
+after a fade the frames cost one forward pass and are, byte for byte, those of the run with that model alone (8-bit outputs; deep outputs
+are that model's on the 8.8 grid).  --model_path2 needs one of the three, and each of them needs it.
 """
 import os
 import sys
@@ -226,6 +234,64 @@ def deliver_dict(delivery, source_size, net_size, guided=None):
     return dict(height=H, width=W, filter=delivery[1])
 
 
+def mix_options(args, camera=False):
+    """--model_path2 / --style_mix / --mix_mask / --mix_fade -> dict(model_path2=, weight=, mask= uint8 [H,W] or None, fade= (F0, F1) or None),
+    None when none of them is given.  The flags are absent from the namespace unless given.  --model_path2 without one of the other three,
+    one of them without it, a value outside its range, an unreadable mask or --mix_fade with the camera loop is a SystemExit here, before
+    anything is loaded."""
+    given = [f for f in ('style_mix', 'mix_mask', 'mix_fade') if hasattr(args, f)]
+    if not hasattr(args, 'model_path2'):
+        if given:
+            raise SystemExit('--%s needs --model_path2: it mixes two models' % given[0])
+        return None
+    if not given:
+        raise SystemExit('--model_path2 needs --style_mix, --mix_mask or --mix_fade: they say how the two models are mixed')
+    t = getattr(args, 'style_mix', 1.0)
+    if not 0.0 <= t <= 1.0:                                      # (NaN fails both comparisons)
+        raise SystemExit('--style_mix %r is outside [0, 1]' % t)
+    fade = getattr(args, 'mix_fade', None)
+    if fade is not None:
+        if camera:
+            raise SystemExit('--mix_fade counts the frames of --frames_dir or --video_in: the camera loop has no frame numbers to fade between')
+        if not 0 <= fade[0] < fade[1]:
+            raise SystemExit('--mix_fade %d %d: 0-based frame numbers with 0 <= F0 < F1' % tuple(fade))
+        fade = tuple(fade)
+    mask = None
+    if hasattr(args, 'mix_mask'):
+        from PIL import Image
+        try:
+            mask = np.array(Image.open(args.mix_mask).convert('L'), dtype=np.uint8)
+        except (IOError, OSError) as e:
+            raise SystemExit('--mix_mask %s: %s' % (args.mix_mask, e))
+    return dict(model_path2=args.model_path2, weight=t, mask=mask, fade=fade)
+
+
+def check_mix_mask_size(args, mix, W, H):
+    """SystemExit unless the --mix_mask (if any) has the net's input size W x H."""
+    if mix is not None and mix['mask'] is not None and mix['mask'].shape != (H, W):
+        raise SystemExit('--mix_mask %s is %d by %d, the net takes frames of %d by %d' % ((args.mix_mask,) + mix['mask'].shape[::-1] + (W, H)))
+
+
+def fade_weight(mix, n):
+    """The share of the second model in frame n (0-based) by 256, an integer computed on the host: T_q8 = floor(T * 256 + 0.5) without
+    --mix_fade; with it d = F1 - F0, k = min(max(n - F0, 0), d) and (2 T_q8 k + d) // (2 d), T_q8 k / d rounded half up."""
+    t_q8 = int(np.floor(mix['weight'] * 256.0 + 0.5))
+    if mix['fade'] is None:
+        return t_q8
+    f0, f1 = mix['fade']
+    d = f1 - f0
+    k = min(max(n - f0, 0), d)
+    return (2 * t_q8 * k + d) // (2 * d)
+
+
+def mix_dict(eng, args, mix):
+    """The mix= dict of the lanes (faststyle_amd/stream.py) for mix_options' answer: loads the second checkpoint.  A fade starts at frame 0's
+    weight; the driver sets every later frame's (set_mix takes shares of 1, and q8 / 256 is quantised back to q8 exactly)."""
+    from faststyle_amd import ckpt
+    variables2 = eng.mem.from_numpy(eng.flatten_params(ckpt.load_checkpoint(mix['model_path2']), upsample_method=args.upsample_method))
+    return dict(variables=variables2, weight=fade_weight(mix, 0) / 256.0, mask=mix['mask'])
+
+
 def check_mask_size(args, compose, W, H):
     """SystemExit unless the mask (if any) has the net's input size W x H."""
     if compose is not None and 'mask' in compose and compose['mask'].shape != (H, W):
@@ -246,8 +312,10 @@ def run_frames_dir(args):
     delivery = delivery_options(args)
     guided = guided_options(args)
     bf16 = batch_options(args)[1]
+    mix = mix_options(args)
     first_size = None
-    if delivery is not None or (compose is not None and 'mask' in compose and (args.frame_size or args.resolution) is None):
+    if delivery is not None or (((compose is not None and 'mask' in compose) or (mix is not None and mix['mask'] is not None)) and
+                                (args.frame_size or args.resolution) is None):
         try:
             with Image.open(os.path.join(args.frames_dir, names[0])) as im:
                 first_size = im.size
@@ -255,6 +323,8 @@ def run_frames_dir(args):
             raise SystemExit('%s: %s' % (os.path.join(args.frames_dir, names[0]), e))
     if compose is not None and 'mask' in compose:                # (the first frame's size, before the model is loaded; later sizes: build())
         check_mask_size(args, compose, *(args.frame_size or args.resolution or first_size))
+    if mix is not None and mix['mask'] is not None:
+        check_mix_mask_size(args, mix, *(args.frame_size or args.resolution or first_size))
     if delivery is not None:                                     # ('source': the first frame's own size, for every frame; checked before the model is loaded)
         delivery = (tuple(first_size) if delivery[0] == 'source' else delivery[0], delivery[1])
         deliver_dict(delivery, first_size, tuple(args.frame_size or args.resolution or first_size), guided)
@@ -277,6 +347,14 @@ def run_frames_dir(args):
         kw = dict(kw, temporal=temporal)
     if bf16:
         kw = dict(kw, bf16=True)
+    count = [0]                                                  # frames handed to a stylizer so far: --mix_fade goes by it
+    before = None
+    if mix is not None:                                          # (both nets are fed and shown alike: the channel handling does not change)
+        kw = dict(kw, mix=mix_dict(eng, args, mix))
+        if mix['fade'] is not None:
+            def before(st):
+                st.set_mix(fade_weight(mix, count[0]) / 256.0)
+                count[0] += 1
 
     def save(n, img_out):
         if jpg:
@@ -322,6 +400,7 @@ def run_frames_dir(args):
         W, H = args.frame_size if args.frame_size is not None else (Ws, Hs)
         print('Resolution is: {0} by {1}'.format(W, H))
         check_mask_size(args, compose, W, H)
+        check_mix_mask_size(args, mix, W, H)
         more = dict(kw, source=source) if source is not None else kw
         if delivery is not None:
             more = dict(more, deliver=deliver_dict(delivery, (Ws, Hs), (W, H), guided))
@@ -348,10 +427,12 @@ def run_frames_dir(args):
             nxt[0] = item
 
         if depth > 1:
-            for out in st.run(segment(), not_taken=not_taken):
+            for out in st.run(segment(), not_taken=not_taken, before_submit=None if before is None else (lambda st=st: before(st))):
                 save(pend.popleft(), out)
         else:
             for frame in segment():
+                if before is not None:
+                    before(st)
                 try:
                     out = st(frame)                                          # = cvtColor(astype(uint8)(Y), BGR2RGB)
                 except stream.FrameNotTaken:
@@ -387,6 +468,7 @@ def run_video(args):
     delivery = delivery_options(args)
     guided = guided_options(args, args.video_matrix)
     batch, bf16 = batch_options(args)
+    mix = mix_options(args)
     frame_filter = getattr(args, 'frame_filter', None)
     to_stdout = args.video_out == '-'
     log = sys.stderr if to_stdout else sys.stdout
@@ -422,6 +504,7 @@ def run_video(args):
             raise SystemExit('--video_in %s: %s' % (args.video_in, e))
         W, H = args.frame_size if args.frame_size is not None else (Ws, Hs)
         check_mask_size(args, compose, W, H)
+        check_mix_mask_size(args, mix, W, H)
         deliver = None
         if delivery is not None:                                             # (a size the kernel or the output layout does not take: said before the model is loaded)
             deliver = deliver_dict(delivery, (Ws, Hs), (W, H), guided)
@@ -464,6 +547,16 @@ def run_video(args):
             kw.update(batch=batch)
             if temporal is not None:
                 kw.update(temporal=dict(temporal, sequence=True))
+        if mix is not None:
+            kw.update(mix=mix_dict(eng, args, mix))
+        fading = mix is not None and mix['fade'] is not None
+        sent = [0]                                                           # frames handed to the lanes so far: --mix_fade goes by it
+
+        def set_weights(n):
+            """The weights of the next pass of n consecutive frames (a last pass's padding counts on: it is never written)"""
+            ws = [fade_weight(mix, sent[0] + i) / 256.0 for i in range(n)]
+            st.set_mix(ws if batch > 1 else ws[0])
+            sent[0] += n
         depth = int(os.environ.get('FS_FRAMES_IN_FLIGHT', '2')) if hasattr(eng.mem, 'torch') else 1
         if depth > 1:
             st = stream.PipelinedStylizer(eng, variables, H, W, depth=depth, upsample_method=args.upsample_method, **kw)
@@ -518,6 +611,8 @@ def run_video(args):
                         break
                     buf[got:] = buf[got - 1]
                     real.append(got)
+                    if fading:
+                        set_weights(batch)
                     if depth > 1:
                         st.submit(buf)
                     else:
@@ -535,6 +630,8 @@ def run_video(args):
                     except y4m.Y4MError as e:
                         failed = e
                         break
+                    if fading:
+                        set_weights(1)
                     st.submit(buf[0])
                 while st.in_flight:
                     emit(st.fetch())
@@ -547,6 +644,8 @@ def run_video(args):
                     except y4m.Y4MError as e:
                         failed = e
                         break
+                    if fading:
+                        set_weights(1)
                     emit(st(buf))
         finally:
             st.release()
@@ -563,6 +662,7 @@ def run_video(args):
 
 
 def run_webcam(args):
+    mix = mix_options(args, camera=True)
     try:
         import cv2
     except ImportError:
@@ -586,9 +686,12 @@ def run_webcam(args):
         deliver_dict(delivery, (x_cam, y_cam), (x_new, y_new), guided)
     print('Resolution is: {0} by {1}'.format(x_new, y_new))
     check_mask_size(args, compose, x_new, y_new)
+    check_mix_mask_size(args, mix, x_new, y_new)
     print('Loading up model...')
     eng, variables = _load(args)
     more = dict(temporal=temporal) if temporal is not None else {}
+    if mix is not None:
+        more['mix'] = mix_dict(eng, args, mix)
     if bf16:
         more['bf16'] = True
     if guided is not None:

@@ -51,6 +51,13 @@ resident, the two alternating over three repeats.  (b) the raw-video loop over a
 and bf16, without and with --temporal_strength 0.6: eight legs that alternate in the one run, rates from the difference between n and n / 4
 frames; written to profiles/video_batch.json with the digest of the kernel sources.  "video_batch_kernels" as the third argument runs the
 720p (3, 2, 1) graphs of (a) alone: under a kernel trace that run gives the kernels' shares.
+"video" with "mix" as the fifth argument (pipe_bench.py 1280 4 video profiles/video_mix.json mix): two styles per stream.  (a) the device time
+of one 720p launch of mix_kernel (fs_mix_f32; the graph-of-200 scheme, data resident): without and with a mask, wide and narrow path, with the
+weight as an argument and from device memory, and compose_kernel in plain mode the same way in the same run, three alternating repeats; the
+device time of one 720p forward pass of one model and of two models alternating (what a mixed lane captures: both filter re-layouts rebuilt
+per pass), whose difference is the second forward's.  (b) the 720p raw-video loop with one model and with --model_path2 ... --style_mix 0.5,
+and (c) with --mix_fade over the middle tenth of the frames: three legs that alternate in the one run, rates from the difference between n
+and n / 4 frames; written to profiles/video_mix.json with the digest of the kernel sources.  "mix_kernels" as the third argument runs (a) alone.
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -187,6 +194,135 @@ def compose_kernel_times(W=1280, H=720, launches=200):
            "compose_keep_color_narrow_path": kernel_timed(lambda: eng.compose_f32(off, net, dst, **kw))}
     for k, v in res.items():
         print("video: %8.1f us per 720p launch: %s" % (v, k))
+    return res
+
+
+def mix_kernel_times(W=1280, H=720, launches=200, repeats=3):
+    """-> dict: device microseconds per 720p launch of mix_kernel (fs_mix_f32) and of compose_kernel in plain mode, timed as kernel_times
+    does and alternating over the repeats (the median and every repeat); and per 720p forward pass of one model and of two models
+    alternating on workspaces of their own under frozen=True, as a mixed lane runs them."""
+    from faststyle_amd import ckpt
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    eng = engine.Engine()
+    mem = eng.mem
+    rng = np.random.default_rng(2)
+    a = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    b = mem.from_numpy(rng.uniform(0, 255, (1, H, W, 3)).astype(np.float32))
+    dst = mem.empty((1, H, W, 3))
+    mask = mem.upload_u8(rng.integers(0, 256, (H, W), dtype=np.uint8))
+    off = mem.view(mem.from_numpy(np.zeros(H * W * 3 + 4, np.float32)), 1, (1, H, W, 3))
+    moff = mem.view(mem.upload_u8(np.zeros(H * W + 4, np.uint8)), 1, (H, W))
+    wdev = eng.i32_buffer([128])
+    cases = [("mix", lambda: eng.mix_f32(a, b, dst, weight_q8=128)),
+             ("mix_weight_from_memory", lambda: eng.mix_f32(a, b, dst, weights=wdev)),
+             ("mix_mask", lambda: eng.mix_f32(a, b, dst, weights=wdev, mask=mask)),
+             ("mix_narrow_path", lambda: eng.mix_f32(off, b, dst, weight_q8=128)),
+             ("mix_mask_narrow_path", lambda: eng.mix_f32(off, b, dst, weight_q8=128, mask=moff)),
+             ("compose_plain", lambda: eng.compose_f32(a, b, dst, strength_q8=128)),
+             ("compose_plain_mask", lambda: eng.compose_f32(a, b, dst, strength_q8=128, mask=mask))]
+    times = {name: [] for name, _ in cases}
+    for _ in range(repeats):
+        for name, fn in cases:
+            times[name].append(kernel_timed(fn, launches))
+    res = {name: {"us": sorted(v)[len(v) // 2], "all_repeats": v} for name, v in times.items()}
+    res["bytes_moved"] = 3 * H * W * 3 * 4
+    # the forward passes: one model alone (its filters re-laid out once, outside the graph), and two models one behind the other
+    models = [mem.from_numpy(eng.flatten_params(ckpt.load_checkpoint(os.path.join(root, "models", m + "_final.ckpt")))) for m in ("starry", "candy")]
+    ws = [eng.new_tnet_workspace(1, H, W) for _ in models]
+    ys = [mem.empty((1,) + tuple(eng.tnet_out_shape(H, W)) + (3,)) for _ in models]
+    fwd = lambda k: eng.tnet_forward(models[k], a, frozen=True, workspace=ws[k], out=ys[k])
+    ftimes = {"forward_one_model": [], "forward_two_models_alternating": []}
+    for _ in range(repeats):
+        eng.invalidate_frozen()
+        ftimes["forward_one_model"].append(kernel_timed(lambda: fwd(0), 20))
+        eng.invalidate_frozen()
+        ftimes["forward_two_models_alternating"].append(kernel_timed(lambda: (fwd(0), fwd(1)), 20))
+    for name, v in ftimes.items():
+        res[name] = {"us": sorted(v)[len(v) // 2], "all_repeats": v}
+    res["second_forward_us"] = res["forward_two_models_alternating"]["us"] - res["forward_one_model"]["us"]
+    res["filter_relayouts_us_per_frame"] = res["forward_two_models_alternating"]["us"] - 2 * res["forward_one_model"]["us"]
+    for k, v in res.items():
+        if isinstance(v, dict):
+            print("mix: %8.1f us per 720p launch: %s (repeats: %s)" % (v["us"], k, ", ".join("%.1f" % t for t in v["all_repeats"])))
+    print("mix: %8.1f us per 720p frame: the second forward; of it %.1f us the two filter re-layouts" %
+          (res["second_forward_us"], res["filter_relayouts_us_per_frame"]))
+    return res
+
+
+def video_mix(n, repeats=3, out_json=None):
+    """-> dict: mix_kernel_times and the three legs of the 720p raw-video loop (one model, two models at --style_mix 0.5, a --mix_fade over
+    the middle tenth of the frames); prints them and writes profiles/video_mix.json (after the kernel times and after every repeat)."""
+    import contextlib
+    import json
+    import shutil
+    from PIL import Image
+    from faststyle_amd import build as fsbuild
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import stylize_webcam
+    n = max(40, n // 40 * 40)
+    w, h = 1280, 720
+    dst = out_json or os.path.join(root, "profiles", "video_mix.json")
+    res = {"frames": n, "frames_in_flight": 2, "host_threads": "1 driver", "host_cores": os.cpu_count(), "omp_num_threads": os.environ.get("OMP_NUM_THREADS"),
+           "video": "720p 4:2:0 YUV4MPEG2 (full range, BT.601), file to file of 8-bit 4:2:0",
+           "method": "rate = (n - n/4) / (t(n) - t(n/4)), median of %d alternating repeats" % repeats, "source_digest": fsbuild.source_digest()}
+
+    def save():
+        with open(dst, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+    res["kernel_us_per_720p_launch"] = mix_kernel_times()
+    save()
+    d = tempfile.mkdtemp()
+    rng = np.random.default_rng(0)
+    base = rng.integers(0, 256, (90, 160, 3), dtype=np.uint8)
+    planes = []
+    for k in range(16):      # 16 distinct natural-ish frames (upsampled noise), reused; PIL's matrix, box-averaged chroma
+        ycc = np.asarray(Image.fromarray(np.roll(base, 5 * k, axis=1)).resize((w, h), Image.BICUBIC).convert("YCbCr"), np.uint16)
+        sub = (ycc[0::2, 0::2, 1:] + ycc[0::2, 1::2, 1:] + ycc[1::2, 0::2, 1:] + ycc[1::2, 1::2, 1:] + 2) >> 2
+        planes.append(b"FRAME\n" + ycc[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 1].astype(np.uint8).tobytes())
+    for count in (n, n // 4):
+        with open(os.path.join(d, "720p_%d.y4m" % count), "wb") as f:
+            f.write(b"YUV4MPEG2 W%d H%d F30:1 Ip A1:1 C420jpeg XCOLORRANGE=FULL\n" % (w, h))
+            for k in range(count):
+                f.write(planes[k % 16])
+    parser = stylize_webcam.setup_parser()
+    out = os.path.join(d, "out.y4m")
+    second = ["--model_path2", os.path.join(root, "models", "candy_final.ckpt")]
+    # (the fade covers the middle tenth of each run's own frames: nine tenths of either run cost one forward pass)
+    legs = [("video_y4m_720p_one_model", lambda count: []),
+            ("video_y4m_720p_two_models_style_mix_0.5", lambda count: second + ["--style_mix", "0.5"]),
+            ("video_y4m_720p_two_models_mix_fade_middle_tenth", lambda count: second + ["--mix_fade", str(count * 9 // 20), str(count * 11 // 20)])]
+
+    def run(count, flags):
+        args = parser.parse_args(["--model_path", os.path.join(root, "models", "starry_final.ckpt"), "--video_in", os.path.join(d, "720p_%d.y4m" % count),
+                                  "--video_out", out] + flags)
+        with contextlib.redirect_stdout(io.StringIO()):
+            t0 = time.time()
+            stylize_webcam.run_video(args)
+            dt = time.time() - t0
+        assert os.path.getsize(out) > count * w * h * 3 // 2
+        os.remove(out)
+        return dt
+
+    run(n // 4, [])                                               # warm-up: library load, first kernels
+    times = {name: [] for name, _ in legs}
+    res["legs"] = {}
+    try:
+        for _ in range(repeats):                                  # legs alternate: a drifting clock touches all of them alike
+            for name, flags in legs:
+                times[name].append((run(n, flags(n)), run(n // 4, flags(n // 4))))
+                print("video_mix: %s: %.2f s for %d frames, %.2f s for %d" % ((name,) + (times[name][-1][0], n, times[name][-1][1], n // 4)), flush=True)
+            for name, _ in legs:
+                rates = sorted((n - n // 4) / (a - b) for a, b in times[name])
+                res["legs"][name] = {"frames_per_s": rates[len(rates) // 2], "all_repeats": rates, "seconds_n_and_quarter": times[name]}
+            save()
+    finally:
+        shutil.rmtree(d)
+    for name, _ in legs:
+        r = res["legs"][name]
+        print("video_mix: %7.0f frames/s %s (repeats: %s)" % (r["frames_per_s"], name, ", ".join("%.0f" % v for v in r["all_repeats"])))
     return res
 
 
@@ -731,6 +867,12 @@ def main():
     threads = int(sys.argv[2]) if len(sys.argv) > 2 else None
     if len(sys.argv) > 5 and sys.argv[3] == "video" and sys.argv[5] == "batch":
         video_batch(n, out_json=sys.argv[4])
+        return
+    if len(sys.argv) > 5 and sys.argv[3] == "video" and sys.argv[5] == "mix":
+        video_mix(n, out_json=sys.argv[4])
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "mix_kernels":
+        mix_kernel_times()
         return
     if len(sys.argv) > 3 and sys.argv[3] == "video_batch_kernels":
         temporal_batch_kernel_times(sizes=((720, 1280),), modes=((3, 2, 1),), repeats=1)
