@@ -105,6 +105,16 @@ class fs_temporal_batch_info(Structure):
                 ("mv_offset", c_uint64), ("mv_stride", c_uint64), ("mvf_offset", c_uint64), ("mvf_stride", c_uint64), ("work_bytes", c_uint64)]
 
 
+class fs_temporal_streams_info(Structure):
+    """include/faststyle_io.h: what fs_temporal_streams_layout reports."""
+    _fields_ = [("streams", ctypes.c_int32), ("levels", ctypes.c_int32), ("subpel", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("luma_offset", c_uint64), ("out88_offset", c_uint64), ("pyr_offset", c_uint64), ("mv_offset", c_uint64), ("mvf_offset", c_uint64),
+                ("slot_stride", c_uint64), ("stream_stride", c_uint64), ("state_bytes", c_uint64)]
+
+
+FS_TS_PREV, FS_TS_SLOT, FS_TS_SKIP = 1, 2, 4     # include/faststyle_io.h: the bits of a stream's control word (fs_temporal_streams_f32)
+
+
 class fs_yuv_desc(Structure):
     """include/faststyle_io.h: one planar YCbCr frame geometry, filled by fs_yuv_plan."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
@@ -239,6 +249,10 @@ PROTOTYPES = {
     "fs_temporal_batch_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
+    "fs_temporal_streams_layout": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_temporal_streams_info)]),
+    # ctx, src, H, W, cur, Ho, Wo, streams, strength_q8, sensitivity, radius, levels, subpel, overlap, matrix, src_bgr, ctl, state, state_bytes, dst
+    "fs_temporal_streams_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fs_resample_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(fs_resample_info)]),
     "fs_resample_tables": (c_int, [POINTER(fs_resample_info), c_void_p, c_size_t]),
     "fs_resample_f32": (c_int, [c_void_p, POINTER(fs_resample_info), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -150,6 +150,10 @@ def stylize_webcam_parser():
                                help="(addition) with --video_in: N consecutive frames per pass through the net, 1..64 (default 1); with "
                                     "--temporal_strength the stage runs over the N frames in order; the results are written in order, a stream's "
                                     "last frames included; latency grows by N frames, so live pipes keep 1")),
+        ('--video_also', dict(default=argparse.SUPPRESS, action='append', nargs=2, metavar=('IN', 'OUT'),
+                              help="(addition) with --video_in and --video_out, repeatable (up to 63 times): one more YUV4MPEG2 stream of the same "
+                                   "size and format, stylized in the same passes -- a batch across streams, which costs no latency; with "
+                                   "--temporal_strength every stream is stabilised on its own; not with --video_batch")),
         ('--precision', dict(default=argparse.SUPPRESS, choices=['fp32', 'bf16'],
                              help="(addition) arithmetic of the net: fp32 (default) or bf16, the mixed-precision path of resize-conv models "
                                   "(about twice the frame rate, about 52 dB against fp32; not with --upsample_method deconv); with --frames_dir, "

@@ -254,12 +254,15 @@ int fs_mix_f32(fs_ctx* ctx, const float* a, const float* b, int H, int W, int Ho
 }
 // The checks of every fs_temporal_*_f32 entry point, once: fn is the called function's name, c its arguments with the options its signature
 // lacks at their defaults (levels 1, subpel 0, overlap 0, frames 1, null buffers), which pass their checks -- so a narrower function checks
-// what it always did, in the same order.
+// what it always did, in the same order.  A streams call (fs_temporal_streams_f32: streams, ctl or state given) has its state in one buffer:
+// the checks of the eight state pointers do not apply to it, every other one does, and its own come last.
 static int temporal_check(const char* fn, const fs_ctx* ctx, const fs::TemporalCall& c) {
-    if (!ctx || !c.src || !c.cur || !c.luma || !c.out88 || !c.mv || !c.dst) return fail(-1, "%s: null argument", fn);
+    const bool st = c.streams != 0 || c.ctl || c.state;
+    if (!ctx || !c.src || !c.cur || !c.dst) return fail(-1, "%s: null argument", fn);
+    if (!st && (!c.luma || !c.out88 || !c.mv)) return fail(-1, "%s: null argument", fn);
     if ((c.prev_luma == nullptr) != (c.prev_out88 == nullptr))
         return fail(-1, "%s: prev_luma and prev_out88 are both given or both null (no previous frame)", fn);
-    if (c.prev_luma == c.luma || c.prev_out88 == c.out88)
+    if (!st && (c.prev_luma == c.luma || c.prev_out88 == c.out88))
         return fail(-1, "%s: the previous frame's state is read at displaced positions and cannot be the state written", fn);
     if (c.H < 1 || c.W < 1 || c.Ho < c.H || c.Ho - c.H > 3 || c.Wo < c.W || c.Wo - c.W > 3)
         return fail(-1, "%s: a %dx%d source does not belong to a %dx%d output (at least the source's size, at most 3 more)", fn, c.H, c.W, c.Ho, c.Wo);
@@ -271,8 +274,8 @@ static int temporal_check(const char* fn, const fs_ctx* ctx, const fs::TemporalC
     if (c.overlap < 0 || c.overlap > 1) return fail(-2, "%s: overlap must be 0 (whole blocks) or 1 (the four nearest blocks), got %d", fn, c.overlap);
     if (c.matrix != 0 && c.matrix != 1) return fail(-2, "%s: matrix must be 0 (BT.601) or 1 (BT.709), got %d", fn, c.matrix);
     if (c.src_bgr != 0 && c.src_bgr != 1) return fail(-2, "%s: src_bgr must be 0 or 1, got %d", fn, c.src_bgr);
-    if (c.subpel > 0 && !c.mvf) return fail(-1, "%s: null mvf with subpel %d", fn, c.subpel);
-    if (c.levels > 1) {
+    if (!st && c.subpel > 0 && !c.mvf) return fail(-1, "%s: null mvf with subpel %d", fn, c.subpel);
+    if (!st && c.levels > 1) {
         if (!c.pyr) return fail(-1, "%s: null pyr with %d levels", fn, c.levels);
         if ((c.prev_pyr == nullptr) != (c.prev_luma == nullptr))
             return fail(-1, "%s: with %d levels prev_pyr is given exactly when prev_luma and prev_out88 are", fn, c.levels);
@@ -288,6 +291,17 @@ static int temporal_check(const char* fn, const fs_ctx* ctx, const fs::TemporalC
             return fail(-1, "%s: %d frames need a work buffer of %llu bytes (fs_temporal_batch_layout), got %s of %llu", fn, c.frames,
                         (unsigned long long)blay.work_bytes, c.work ? "one" : "null", (unsigned long long)c.work_bytes);
         if ((uintptr_t)c.work & 15) return fail(-5, "%s: work must be 16-byte aligned", fn);
+    }
+    if (st) {
+        if (c.streams < 1 || c.streams > 64) return fail(-1, "%s: streams must be in [1, 64], got %d", fn, c.streams);
+        fs_temporal_streams_info slay;
+        if (fs_temporal_streams_layout(c.Ho, c.Wo, c.levels, c.subpel, c.streams, &slay)) return -1;   // (cannot happen: checked above; the message is its own)
+        if (!c.ctl || !c.state || c.state_bytes < slay.state_bytes)
+            return fail(-1, "%s: %d streams need %d control words and a state buffer of %llu bytes (fs_temporal_streams_layout), got %s and %s of %llu",
+                        fn, c.streams, c.streams, (unsigned long long)slay.state_bytes, c.ctl ? "them" : "null", c.state ? "one" : "null",
+                        (unsigned long long)c.state_bytes);
+        if ((uintptr_t)c.state & 15) return fail(-5, "%s: state must be 16-byte aligned", fn);
+        if ((uintptr_t)c.ctl & 3) return fail(-5, "%s: ctl must be 4-byte aligned", fn);
     }
     return 0;
 }
@@ -330,6 +344,13 @@ int fs_temporal_batch_f32(fs_ctx* ctx, const float* src, int H, int W, const flo
     return temporal_call("fs_temporal_batch_f32", ctx, {src, H, W, cur, Ho, Wo, frames, strength_q8, sensitivity, radius, levels, subpel, overlap,
                                                         matrix, src_bgr, prev_luma, prev_out88, prev_pyr, luma, out88, pyr, mv, mvf,
                                                         static_cast<unsigned char*>(work), work_bytes, dst});
+}
+int fs_temporal_streams_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int streams, int strength_q8,
+                            int sensitivity, int radius, int levels, int subpel, int overlap, int matrix, int src_bgr, const int* ctl, void* state,
+                            size_t state_bytes, float* dst) {
+    return temporal_call("fs_temporal_streams_f32", ctx, {src, H, W, cur, Ho, Wo, 1, strength_q8, sensitivity, radius, levels, subpel, overlap, matrix,
+                                                          src_bgr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                                                          dst, streams, ctl, static_cast<unsigned char*>(state), state_bytes});
 }
 int fs_resample_f32(fs_ctx* ctx, const fs_resample_info* plan, const void* tables_dev, const float* src, int src_rows, int src_pitch, int N, float* dst) {
     if (!ctx || !plan || !src || !dst) return fail(-1, "fs_resample_f32: null argument");

@@ -719,6 +719,14 @@ struct TemporalCall {
     unsigned char* work;
     size_t work_bytes;
     float* dst;
+    // fs_temporal_streams_f32 only (every other entry point leaves them 0 / null): one frame of each of `streams` independent streams per call,
+    // src / cur / dst hold one image per stream, `frames` is 1 and the eight state pointers above are null -- the state of all streams is
+    // `state` (fs_temporal_streams_layout), and the device words ctl[s] say per stream what the pointers say per call.  Every launch then runs
+    // once over all streams, the blend included.
+    int streams;
+    const int* ctl;
+    unsigned char* state;
+    size_t state_bytes;
 };
 int temporal_run(const TemporalCall& c, hipStream_t s);
 // resampling between fp32 tensors (fs_resample.hip): whether a plan is what fs_resample_plan fills, and the one launch (argument checks are in

@@ -25,8 +25,16 @@
 // f = 0 the state the previous call wrote (null: no previous frame).  f is uniform per workgroup and held below `frames`, so the selection
 // stays in scalar registers.  The selection costs a call of one frame 0.2 to 0.3 us per launch, so luma, pyramid, search and
 // refinement are a body with two entries: *_kernel takes one frame's pointers (frames == 1: no work buffer), *_batch_kernel selects them.
+// Streams: a call covers `streams` independent streams, one frame of each (fs_temporal_streams_f32).  Nothing is recursive inside such a pass,
+// so every launch, the blend included, runs once over all streams with the stream index s as one more grid dimension (blockIdx.y of the 1-D
+// grids, blockIdx.z of the others), held below `streams`: the third set of entries, *_streams_kernel, of the same bodies.  The state of all
+// streams is one buffer, per stream two slots of [luma | out88 | pyr | mv | mvf] (fs_temporal_streams_layout).  What differs per stream --
+// whether it has a previous frame, which slot it writes, whether it takes part -- is the device word ctl[s] (FS_TS_PREV, FS_TS_SLOT,
+// FS_TS_SKIP), read once per workgroup: s is uniform, so the read and the pointer selection stay in scalar registers, as the frame selection
+// does.  A skipped stream's workgroups return before their first access and before any barrier.
 // No value read from a tensor reaches an address except through mv and mvf, which the search and the refinement bound and every reader holds
-// to those bounds again together with the displaced coordinates.  The arithmetic is integer throughout.
+// to those bounds again together with the displaced coordinates, and through the slot index (ctl[s] >> 1) & 1 of a streams call, which the
+// mask bounds.  The arithmetic is integer throughout.
 #include <cstring>
 
 #include "../../include/faststyle_io.h"
@@ -87,6 +95,31 @@ __device__ __forceinline__ const unsigned char* frame_before(const FrameSel& S, 
     return S.work + (size_t)(f - 1) * S.slot + B.off;
 }
 
+// the streams of a call: the control words, the state of all streams, the strides of a slot and of a stream (two slots)
+struct StreamSel {
+    const int* ctl;
+    unsigned char* state;
+    unsigned long long slot, stream;
+    int streams;
+};
+
+// the two slots of stream s: wr the one this pass writes, rd the one it reads (null: a first frame).  False: nothing of s is touched.
+struct StreamAt {
+    unsigned char* wr;
+    const unsigned char* rd;
+};
+
+__device__ __forceinline__ bool stream_at(const StreamSel& T, int s, StreamAt& at) {
+    if (s >= T.streams) return false;
+    const int c = T.ctl[s] & 7;                             // (uniform per workgroup)
+    if (c & FS_TS_SKIP) return false;
+    const int w = (c >> 1) & 1;                             // the only value from the control buffer that reaches an address: 0 or 1
+    unsigned char* base = T.state + (size_t)s * T.stream;
+    at.wr = base + (size_t)w * T.slot;
+    at.rd = (c & FS_TS_PREV) ? base + (size_t)(w ^ 1) * T.slot : nullptr;
+    return true;
+}
+
 struct LumaArgs {
     int H, W, Ho, Wo;
     int k0, k1, k2;                         // luma weights by 2^16 of the channels as stored (k0 is kb when channel 0 is blue)
@@ -120,6 +153,15 @@ __global__ __launch_bounds__(256) void temporal_luma_batch_kernel(const LumaArgs
     const int f = (int)blockIdx.y;
     if (f >= S.frames) return;
     temporal_luma_body(A, src + (size_t)f * A.H * A.W * 3, frame_at(S, L, f));
+}
+
+// (loff: the luma's offset in a slot, here and below)
+__global__ __launch_bounds__(256) void temporal_luma_streams_kernel(const LumaArgs A, const StreamSel T, unsigned long long loff,
+                                                                    const float* __restrict__ src) {
+    const int s = (int)blockIdx.y;
+    StreamAt at;
+    if (!stream_at(T, s, at)) return;
+    temporal_luma_body(A, src + (size_t)s * A.H * A.W * 3, at.wr + loff);
 }
 
 struct PyrArgs {
@@ -169,6 +211,13 @@ __global__ __launch_bounds__(256) void temporal_pyramid_batch_kernel(const PyrAr
     const int f = (int)blockIdx.z;
     if (f >= S.frames) return;
     temporal_pyramid_body(A, frame_at(S, L0, f), frame_at(S, L1, f), A.H2 > 0 ? frame_at(S, L2, f) : nullptr);
+}
+
+__global__ __launch_bounds__(256) void temporal_pyramid_streams_kernel(const PyrArgs A, const StreamSel T, unsigned long long l0off,
+                                                                       unsigned long long l1off, unsigned long long l2off) {
+    StreamAt at;
+    if (!stream_at(T, (int)blockIdx.z, at)) return;
+    temporal_pyramid_body(A, at.wr + l0off, at.wr + l1off, A.H2 > 0 ? at.wr + l2off : nullptr);
 }
 
 // One level (cur8 / prev8 [H, W]), one workgroup per block (blockIdx.y, blockIdx.x).  prev8 == nullptr (no previous frame): every vector is
@@ -276,6 +325,16 @@ __global__ __launch_bounds__(256) void temporal_search_batch_kernel(const FrameS
                          (signed char*)frame_at(S, V, f));
 }
 
+// coff: the level's luma in a slot (its predecessor: the same place in the slot read), poff: the coarser level's vectors, voff: those written
+__global__ __launch_bounds__(256) void temporal_search_streams_kernel(const StreamSel T, unsigned long long coff, int H, int W, int R,
+                                                                      unsigned long long poff, int has_parent, int pnbx, int hold,
+                                                                      unsigned long long voff) {
+    StreamAt at;
+    if (!stream_at(T, (int)blockIdx.z, at)) return;         // (before the body's first barrier, the whole workgroup alike)
+    temporal_search_body(at.wr + coff, at.rd ? at.rd + coff : nullptr, H, W, R, has_parent ? (const signed char*)(at.wr + poff) : nullptr, pnbx, hold,
+                         (signed char*)(at.wr + voff));
+}
+
 // the contract's fit: m, p the SADs one pixel before / after the winner's s0 along one axis -> the fraction in quarter pixels
 __device__ __forceinline__ int subpel_fit(int s0, int m, int p, int S) {
     const int E = (m > p ? m : p) - s0;
@@ -375,6 +434,14 @@ __global__ __launch_bounds__(256) void temporal_subpel_batch_kernel(const FrameS
     if (f >= S.frames) return;
     temporal_subpel_body(frame_at(S, C, f), frame_before(S, C, f), Ho, Wo, R, hold, Sp, (const signed char*)frame_at(S, MV, f),
                          (signed char*)frame_at(S, MVF, f));
+}
+
+__global__ __launch_bounds__(256) void temporal_subpel_streams_kernel(const StreamSel T, unsigned long long coff, int Ho, int Wo, int R, int hold,
+                                                                      int Sp, unsigned long long mvoff, unsigned long long mvfoff) {
+    StreamAt at;
+    if (!stream_at(T, (int)blockIdx.z, at)) return;         // (before the body's first barrier, the whole workgroup alike)
+    temporal_subpel_body(at.wr + coff, at.rd ? at.rd + coff : nullptr, Ho, Wo, R, hold, Sp, (const signed char*)(at.wr + mvoff),
+                         (signed char*)(at.wr + mvfoff));
 }
 
 struct BlendArgs {
@@ -599,6 +666,39 @@ __global__ __launch_bounds__(256) void temporal_blend_obmc_kernel(const BlendArg
     temporal_blend_body<BLEND_OBMC>(A, cur, cur8, prev8, prev88, mv, mvf, dst, out88);
 }
 
+// where the blend's buffers lie in a slot (mvf: ignored where has_mvf is 0)
+struct StreamBlend {
+    unsigned long long luma, out88, mv, mvf;
+    int has_mvf;
+};
+
+// stream s blends image s of cur into image s of dst: "no previous frame" is uniform per workgroup here, not per launch
+template <BlendMode MODE>
+__device__ __forceinline__ void temporal_blend_streams(const BlendArgs& A, const StreamSel& T, const StreamBlend& O, const float* cur, float* dst) {
+    const int s = (int)blockIdx.y;
+    StreamAt at;
+    if (!stream_at(T, s, at)) return;
+    const size_t image = (size_t)s * A.Ho * A.Wo * 3;
+    temporal_blend_body<MODE>(A, cur + image, at.wr + O.luma, at.rd ? at.rd + O.luma : nullptr,
+                              at.rd ? (const unsigned short*)(at.rd + O.out88) : nullptr, (const signed char*)(at.wr + O.mv),
+                              O.has_mvf ? (const signed char*)(at.wr + O.mvf) : nullptr, dst + image, (unsigned short*)(at.wr + O.out88));
+}
+
+__global__ __launch_bounds__(256) void temporal_blend_streams_kernel(const BlendArgs A, const StreamSel T, const StreamBlend O, const float* cur,
+                                                                     float* dst) {
+    temporal_blend_streams<BLEND_WHOLE>(A, T, O, cur, dst);
+}
+
+__global__ __launch_bounds__(256) void temporal_blend_sub_streams_kernel(const BlendArgs A, const StreamSel T, const StreamBlend O, const float* cur,
+                                                                         float* dst) {
+    temporal_blend_streams<BLEND_SUB>(A, T, O, cur, dst);
+}
+
+__global__ __launch_bounds__(256) void temporal_blend_obmc_streams_kernel(const BlendArgs A, const StreamSel T, const StreamBlend O, const float* cur,
+                                                                          float* dst) {
+    temporal_blend_streams<BLEND_OBMC>(A, T, O, cur, dst);
+}
+
 inline uint64_t up16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
 
 // the work buffer: frames - 1 slots of [luma | pyr | mv | mvf], then min(frames - 1, 2) out88 frames (a blend reads its predecessor's only)
@@ -620,22 +720,46 @@ BatchLay batch_lay(const fs_temporal_pyr_info& lay, int subpel, int frames) {
     return b;
 }
 
+// a slot of a streams call: [luma | out88 | pyr | mv | mvf], every part at a multiple of 16
+struct StreamLay {
+    uint64_t luma_off, o88_off, pyr_off, mv_off, mvf_off, slot;
+};
+
+StreamLay stream_lay(const fs_temporal_pyr_info& lay, int subpel) {
+    StreamLay t;
+    const uint64_t blocks = up16((uint64_t)lay.nby[0] * (uint64_t)lay.nbx[0] * 2);
+    t.luma_off = 0;
+    t.o88_off = up16((uint64_t)lay.h[0] * (uint64_t)lay.w[0]);
+    t.pyr_off = t.o88_off + up16((uint64_t)lay.h[0] * (uint64_t)lay.w[0] * 6);
+    t.mv_off = t.pyr_off + lay.pyr_bytes;   // (a multiple of 16 already)
+    t.mvf_off = t.mv_off + blocks;
+    t.slot = t.mvf_off + (subpel > 0 ? blocks : 0);
+    return t;
+}
+
 }  // namespace
 
 // arguments: checked by the caller (fs_api.hip)
 int temporal_run(const TemporalCall& c, hipStream_t s) {
     fs_temporal_pyr_info lay;
     if (fs_temporal_pyr_layout(c.Ho, c.Wo, c.levels, &lay)) return -1;                   // (cannot happen: the caller checked all three)
-    const int L = c.levels, Ho = c.Ho, Wo = c.Wo, N = c.frames;
-    const BatchLay B = batch_lay(lay, c.subpel, N);
+    const int L = c.levels, Ho = c.Ho, Wo = c.Wo, N = c.frames, St = c.streams;         // (St > 0: one frame of each of St streams, N is 1)
+    BatchLay B = batch_lay(lay, c.subpel, N);
+    const StreamLay TL = stream_lay(lay, c.subpel);
+    StreamSel T;
+    T.ctl = c.ctl; T.state = c.state; T.slot = TL.slot; T.stream = 2 * TL.slot; T.streams = St;
+    if (St > 0) {                                           // (the offsets below are then those in a stream's slot; the pointers beside them are null)
+        B.luma_off = TL.luma_off; B.pyr_off = TL.pyr_off; B.mv_off = TL.mv_off; B.mvf_off = TL.mvf_off;
+    }
     FrameSel S;
     S.work = c.work; S.slot = B.slot; S.frames = N;
     const FrameBuf FMV = {(unsigned char*)c.mv, nullptr, B.mv_off}, FMVF = {(unsigned char*)c.mvf, nullptr, B.mvf_off};
     FrameBuf FPL[FS_TEMPORAL_MAX_LEVELS], FPV[FS_TEMPORAL_MAX_LEVELS];                    // the levels' lumas and vectors
     FPL[0] = {c.luma, c.prev_luma, B.luma_off}; FPV[0] = FMV;
     for (int l = 1; l < L; ++l) {
-        FPL[l] = {c.pyr + lay.luma_offset[l], c.prev_luma == nullptr ? nullptr : c.prev_pyr + lay.luma_offset[l], B.pyr_off + lay.luma_offset[l]};
-        FPV[l] = {c.pyr + lay.mv_offset[l], nullptr, B.pyr_off + lay.mv_offset[l]};
+        FPL[l] = {St > 0 ? nullptr : c.pyr + lay.luma_offset[l], c.prev_luma == nullptr ? nullptr : c.prev_pyr + lay.luma_offset[l],
+                  B.pyr_off + lay.luma_offset[l]};
+        FPV[l] = {St > 0 ? nullptr : c.pyr + lay.mv_offset[l], nullptr, B.pyr_off + lay.mv_offset[l]};
     }
     const int kr = c.matrix ? 13933 : 19595, kg = c.matrix ? 46871 : 38470, kb = c.matrix ? 4732 : 7471;  // each triple sums to 65536
     LumaArgs LA;
@@ -643,7 +767,9 @@ int temporal_run(const TemporalCall& c, hipStream_t s) {
     LA.k0 = c.src_bgr ? kb : kr; LA.k1 = kg; LA.k2 = c.src_bgr ? kr : kb;
     const long long threads = ((long long)(Wo + 3) >> 2) * Ho;
     const dim3 egrid((unsigned)((threads + 255) / 256)), block(256);
-    if (N == 1)                                             // (one frame: the entries without a frame index, here and below)
+    if (St > 0)                                             // (streams: the entries that select by ctl[s], here and below)
+        hipLaunchKernelGGL(temporal_luma_streams_kernel, dim3(egrid.x, (unsigned)St), block, 0, s, LA, T, FPL[0].off, c.src);
+    else if (N == 1)                                        // (one frame: the entries without a frame index, here and below)
         hipLaunchKernelGGL(temporal_luma_kernel, egrid, block, 0, s, LA, c.src, c.luma);
     else
         hipLaunchKernelGGL(temporal_luma_batch_kernel, dim3(egrid.x, (unsigned)N), block, 0, s, LA, S, FPL[0], c.src);
@@ -652,7 +778,10 @@ int temporal_run(const TemporalCall& c, hipStream_t s) {
         PA.H0 = Ho; PA.W0 = Wo; PA.H1 = lay.h[1]; PA.W1 = lay.w[1];
         PA.H2 = L > 2 ? lay.h[2] : 0; PA.W2 = L > 2 ? lay.w[2] : 0;
         const unsigned chunks = (unsigned)((((PA.W1 + 3) >> 2) + 255) / 256);            // (W1 >= W2; at most 2^21 columns: within grid.y)
-        if (N == 1)
+        if (St > 0)
+            hipLaunchKernelGGL(temporal_pyramid_streams_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks, (unsigned)St), block, 0, s, PA, T, FPL[0].off,
+                               FPL[1].off, L > 2 ? FPL[2].off : FPL[1].off);
+        else if (N == 1)
             hipLaunchKernelGGL(temporal_pyramid_kernel, dim3((unsigned)(PA.H1 + PA.H2), chunks), block, 0, s, PA, (const unsigned char*)c.luma, FPL[1].last,
                                L > 2 ? FPL[2].last : nullptr);
         else
@@ -662,7 +791,10 @@ int temporal_run(const TemporalCall& c, hipStream_t s) {
     for (int l = L - 1; l >= 0; --l) {                      // coarsest first: level l reads the vectors level l + 1 wrote
         const bool top = l == L - 1;
         const int pnbx = top ? 0 : lay.nbx[l + 1], lhold = 2 * c.radius * ((1 << (L - 1 - l)) - 1);
-        if (N == 1)
+        if (St > 0)
+            hipLaunchKernelGGL(temporal_search_streams_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l], (unsigned)St), block, 0, s, T, FPL[l].off,
+                               lay.h[l], lay.w[l], c.radius, top ? FPV[l].off : FPV[l + 1].off, top ? 0 : 1, pnbx, lhold, FPV[l].off);
+        else if (N == 1)
             hipLaunchKernelGGL(temporal_search_kernel, dim3((unsigned)lay.nbx[l], (unsigned)lay.nby[l]), block, 0, s, (const unsigned char*)FPL[l].last,
                                FPL[l].before, lay.h[l], lay.w[l], c.radius, top ? nullptr : (const signed char*)FPV[l + 1].last, pnbx, lhold,
                                (signed char*)FPV[l].last);
@@ -671,7 +803,10 @@ int temporal_run(const TemporalCall& c, hipStream_t s) {
                                lay.w[l], c.radius, top ? FPV[l] : FPV[l + 1], top ? 0 : 1, pnbx, lhold, FPV[l]);
     }
     const int hold = c.radius * ((1 << L) - 1);
-    if (c.subpel > 0 && N == 1)
+    if (c.subpel > 0 && St > 0)
+        hipLaunchKernelGGL(temporal_subpel_streams_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0], (unsigned)St), block, 0, s, T, FPL[0].off, Ho,
+                           Wo, c.radius, hold, c.subpel, FMV.off, FMVF.off);
+    else if (c.subpel > 0 && N == 1)
         hipLaunchKernelGGL(temporal_subpel_kernel, dim3((unsigned)lay.nbx[0], (unsigned)lay.nby[0]), block, 0, s, (const unsigned char*)c.luma, c.prev_luma,
                            Ho, Wo, c.radius, hold, c.subpel, (const signed char*)c.mv, c.mvf);
     else if (c.subpel > 0)
@@ -681,7 +816,17 @@ int temporal_run(const TemporalCall& c, hipStream_t s) {
     BA.Ho = Ho; BA.Wo = Wo; BA.nby = lay.nby[0]; BA.nbx = lay.nbx[0];
     BA.strength_q8 = c.strength_q8; BA.sensitivity = c.sensitivity; BA.R = hold;
     const size_t image = (size_t)Ho * Wo * 3;
-    for (int i = 0; i < N; ++i) {                           // in order: frame i reads the out88 frame i - 1 wrote (the two in `work` alternate)
+    if (St > 0) {                                           // nothing recursive inside the pass: one blend over all streams
+        const StreamBlend O = {TL.luma_off, TL.o88_off, TL.mv_off, TL.mvf_off, c.subpel > 0 ? 1 : 0};
+        const dim3 sgrid(egrid.x, (unsigned)St);
+        if (c.overlap)
+            hipLaunchKernelGGL(temporal_blend_obmc_streams_kernel, sgrid, block, 0, s, BA, T, O, c.cur, c.dst);
+        else if (c.subpel > 0)
+            hipLaunchKernelGGL(temporal_blend_sub_streams_kernel, sgrid, block, 0, s, BA, T, O, c.cur, c.dst);
+        else
+            hipLaunchKernelGGL(temporal_blend_streams_kernel, sgrid, block, 0, s, BA, T, O, c.cur, c.dst);
+    }
+    for (int i = 0; St == 0 && i < N; ++i) {                // in order: frame i reads the out88 frame i - 1 wrote (the two in `work` alternate)
         const bool last = i == N - 1;                       // (i == 0 and the last frame take state pointers only: `work` may be null with one frame)
         const unsigned char* c8 = last ? c.luma : c.work + (size_t)i * B.slot + B.luma_off;
         const unsigned char* p8 = i == 0 ? c.prev_luma : c.work + (size_t)(i - 1) * B.slot + B.luma_off;
@@ -723,6 +868,27 @@ int fs_temporal_batch_layout(int Ho, int Wo, int levels, int subpel, int frames,
         b.work_bytes = B.bytes;
     }
     *info = b;
+    return 0;
+}
+
+int fs_temporal_streams_layout(int Ho, int Wo, int levels, int subpel, int streams, fs_temporal_streams_info* info) {
+    using namespace fs;
+    if (!info) return set_error(-1, "fs_temporal_streams_layout: null argument");
+    if (Ho < 1 || Wo < 1) return set_error(-1, "fs_temporal_streams_layout: a %dx%d output has a side below 1", Ho, Wo);
+    if (streams < 1 || streams > 64) return set_error(-1, "fs_temporal_streams_layout: streams must be in [1, 64], got %d", streams);
+    if (levels < 1 || levels > FS_TEMPORAL_MAX_LEVELS)
+        return set_error(-2, "fs_temporal_streams_layout: levels must be in [1, %d], got %d", FS_TEMPORAL_MAX_LEVELS, levels);
+    if (subpel < 0 || subpel > 2) return set_error(-2, "fs_temporal_streams_layout: subpel must be 0 (whole), 1 (half) or 2 (quarter pixels), got %d", subpel);
+    fs_temporal_pyr_info lay;
+    if (fs_temporal_pyr_layout(Ho, Wo, levels, &lay)) return -1;                    // (cannot happen: checked above)
+    const StreamLay TL = stream_lay(lay, subpel);
+    fs_temporal_streams_info t;
+    memset(&t, 0, sizeof(t));
+    t.streams = streams; t.levels = levels; t.subpel = subpel;
+    t.luma_offset = TL.luma_off; t.out88_offset = TL.o88_off; t.pyr_offset = TL.pyr_off; t.mv_offset = TL.mv_off; t.mvf_offset = TL.mvf_off;
+    t.slot_stride = TL.slot; t.stream_stride = 2 * TL.slot;
+    t.state_bytes = (uint64_t)streams * t.stream_stride;
+    *info = t;
     return 0;
 }
 

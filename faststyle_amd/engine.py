@@ -1268,6 +1268,69 @@ class Engine(JpegHost, CvResizeHost, ResampleHost, YuvHost):
         mv = gather(int(lay.mv_offset), int(lay.mv_stride), state[2])
         return mv, (gather(int(lay.mvf_offset), int(lay.mvf_stride), state[-1]) if subpel > 0 else None)
 
+    def temporal_streams_layout(self, Ho, Wo, streams, levels=1, subpel=0):
+        """fs_temporal_streams_layout: where the parts of a slot lie, the strides of a slot and of a stream and the size of the state buffer of
+        `streams` independent streams (host only)."""
+        info = L.fs_temporal_streams_info()
+        L.check(self.lib, self.lib.fs_temporal_streams_layout(int(Ho), int(Wo), int(levels), int(subpel), int(streams), ctypes.byref(info)),
+                "fs_temporal_streams_layout")
+        return info
+
+    def temporal_streams_state(self, Ho, Wo, streams, levels=1, subpel=0):
+        """The state of temporal_streams_f32 as one device uint8 buffer (the memory backend's) of temporal_streams_layout's state_bytes."""
+        return self.mem.upload_u8(np.zeros((int(self.temporal_streams_layout(Ho, Wo, streams, levels, subpel).state_bytes),), np.uint8))
+
+    def temporal_streams_f32(self, src, cur, dst, ctl, state, strength_q8=256, sensitivity=16, radius=7, matrix="bt601", src_bgr=False, levels=1,
+                             subpel=0, overlap=0):
+        """fs_temporal_streams_f32: temporal_f32 over one frame of each of S independent streams -- src device float32 [S,H,W,3], cur and dst
+        [S,Ho,Wo,3] (dst may be cur), ctl a device buffer of S int32 control words (i32_buffer; FS_TS_PREV, FS_TS_SLOT, FS_TS_SKIP per stream),
+        state temporal_streams_state's for at least S streams.  Stream s gets what temporal_f32 gives image s with the slot the word names,
+        bit for bit; a skipped stream is not touched."""
+        self._sync_stream()
+        who = "temporal_streams_f32"
+        self._temporal_whole(who, levels=levels, subpel=subpel, overlap=overlap)
+        ss, cs, ds = (tuple(int(d) for d in t.shape) for t in (src, cur, dst))
+        if len(ss) != 4 or len(cs) != 4 or ss[3] != 3 or cs[3] != 3 or ds != cs or ss[0] != cs[0]:
+            raise L.FaststyleError("%s: source %s / current %s / destination %s do not belong together ([S,H,W,3] / [S,Ho,Wo,3] each)" %
+                                   (who, tuple(src.shape), tuple(cur.shape), tuple(dst.shape)))
+        S, Ho, Wo = cs[:3]
+        if not 1 <= S <= 64:
+            raise L.FaststyleError("%s: 1 to 64 streams per call, got %d" % (who, S))
+        need = int(self.temporal_streams_layout(Ho, Wo, S, levels, subpel).state_bytes)
+        nbytes = int(np.prod(state.shape))
+        if not str(state.dtype).endswith("uint8") or nbytes < need:
+            raise L.FaststyleError("%s: %d streams of %dx%d need a state buffer of %d bytes (temporal_streams_state), got %s of %d" %
+                                   (who, S, Ho, Wo, need, state.dtype, nbytes))
+        matrix = {"bt601": 0, "bt709": 1}.get(matrix, matrix)
+        L.check(self.lib, self.lib.fs_temporal_streams_f32(self.ctx, self.mem.ptr(src), ss[1], ss[2], self.mem.ptr(cur), Ho, Wo, S, int(strength_q8),
+                                                           int(sensitivity), int(radius), int(levels), int(subpel), int(overlap), int(matrix),
+                                                           1 if src_bgr else 0, self._i32_ptr(ctl, S, who), self.mem.ptr_u8(state), nbytes,
+                                                           self.mem.ptr(dst)), "fs_temporal_streams_f32")
+        return dst
+
+    def temporal_streams_slot(self, state, ctl_host, stream, Ho, Wo, levels=1, subpel=0, written=True):
+        """For tests and inspection: one slot of one stream as host arrays -> dict(luma uint8 [Ho,Wo], out88 uint16 [Ho,Wo,3], pyr uint8
+        [pyr_bytes], mv int8 [nby,nbx,2], mvf likewise or None with subpel 0): the slot that the pass with the host control words ctl_host
+        wrote, or with written=False the other one (synchronises)."""
+        S = len(ctl_host)
+        lay = self.temporal_streams_layout(Ho, Wo, S, levels, subpel)
+        Ho, Wo = int(Ho), int(Wo)
+        nby, nbx = (Ho + 15) // 16, (Wo + 15) // 16
+        w = (int(ctl_host[stream]) >> 1 & 1) ^ (0 if written else 1)
+        base = int(stream) * int(lay.stream_stride) + w * int(lay.slot_stride)
+        raw = np.array(self.mem.to_numpy(state), dtype=np.uint8, copy=True).reshape(-1)[base:base + int(lay.slot_stride)]
+        part = lambda off, n: raw[int(off):int(off) + n]
+        return dict(luma=part(lay.luma_offset, Ho * Wo).reshape(Ho, Wo), out88=part(lay.out88_offset, Ho * Wo * 6).view("<u2").reshape(Ho, Wo, 3),
+                    pyr=part(lay.pyr_offset, int(lay.mv_offset - lay.pyr_offset)), mv=part(lay.mv_offset, nby * nbx * 2).view(np.int8).reshape(nby, nbx, 2),
+                    mvf=part(lay.mvf_offset, nby * nbx * 2).view(np.int8).reshape(nby, nbx, 2) if subpel > 0 else None)
+
+    def temporal_streams_vectors(self, state, ctl_host, Ho, Wo, levels=1, subpel=0):
+        """For tests and motion_vectors(): every stream's vectors from the slot that the pass with the host control words ctl_host wrote (a
+        skipped stream's: from the slot the word names, whatever it holds) -> (mv int8 [S,nby,nbx,2], mvf likewise or None with subpel 0)
+        (synchronises)."""
+        slots = [self.temporal_streams_slot(state, ctl_host, s, Ho, Wo, levels, subpel) for s in range(len(ctl_host))]
+        return np.stack([t["mv"] for t in slots]), (np.stack([t["mvf"] for t in slots]) if subpel > 0 else None)
+
     def synth_uniform(self, out, seed, rank, batch_index):
         """Uniform [0,255) float32 values into ``out``: Philox4x32-10 keyed by seed, counter (element block, batch_index, rank) (fs_synth_uniform)."""
         self._sync_stream()

@@ -69,7 +69,18 @@ nothing changes.
 what frame i - 1 left, frame 0 what the previous pass left.  Slot parity, the three tail graphs, ``reset()`` and the frame counter then go by
 pass; the lane has one work buffer more for the frames inside a pass, ``stabilised_output()`` is [N, Ho, Wo, 3] and ``motion_vectors()`` /
 ``motion_vectors_subpel()`` have a leading axis of N.  A pass always takes N frames: the caller pads a stream's end by repeating its last
-frame.  Without the key a batch other than 1 is refused (a batch could as well be N independent streams); with it at batch 1 nothing changes.
+frame.  Without this key or ``streams`` a batch other than 1 is refused (the stage must be told which of the two a batch is); with it at
+batch 1 nothing changes.
+``streams=True`` on a lane with ``batch=S`` is that other reading: the batch's images are one frame of each of S independent streams
+(fs_temporal_streams_f32), every one stabilised against its own previous frame.  Nothing is recursive inside such a pass, so every launch of
+the stage, the blend included, runs once over all streams: the stage has the launches of one stream whatever S is.  The lane holds one state
+buffer (per stream two slots), and what differs per stream -- whether it has a previous frame, which slot it writes, whether it takes part --
+is a device control word, written from a pinned host array by an asynchronous copy on the lane's stream ahead of the tail and advanced on the
+host only behind the pass; so there is one tail graph whatever the passes were.  ``set_streams(active)`` names the streams of the passes that
+follow (S booleans; an inactive stream keeps its state and parity, and its row of the results is whatever the lane held), ``reset(stream=)``
+forgets one stream's previous frame (None: every stream's).  ``stabilised_output()`` is [S, Ho, Wo, 3], ``motion_vectors()`` /
+``motion_vectors_subpel()`` have a leading axis of S.  Mutually exclusive with ``sequence=True``; at batch 1 the frames are, byte for byte, those
+of the lane without the key.
 
 Delivery at another size: with ``deliver=dict(height=, width=, filter='bicubic')`` one launch ahead of the output conversions (fs_resample_f32,
 csrc/fs_resample.hip) resamples the top-left H x W of the tensor they would read -- the net's output, the composed or the stabilised tensor --
@@ -200,7 +211,10 @@ class FrameStylizer(object):
         self._tn = 0                     # ... frames since construction or reset(): frame n reads slot (n - 1) & 1 and writes slot n & 1
         self._twork = None               # ... with sequence=True and a batch: the work buffer of the frames inside a pass (then _tn counts passes)
         self._cur = None                 # ... the head's result: the net's output or the composed tensor
-        self._tail_graphs = {}           # ... captured tails by the parity written (None: a first frame's)
+        self._tail_graphs = {}           # ... captured tails by the parity written (None: a first frame's); a streams lane has one
+        self._sctl = None                # ... with streams=True: the device control words (one per stream) and their pinned staging words,
+        self._sctl_stage = None          #     the lane's own; _tslots is then the one state buffer of all streams, shared by the lanes
+        self._sh = None                  #     and the host's view of the streams (prev, parity, active, last), shared by the lanes too
         if temporal is not None:
             self._temporal_setup(dict(temporal), _temporal_slots)
 
@@ -286,7 +300,7 @@ class FrameStylizer(object):
             raise L.FaststyleError("deliver guided= needs a source that is resized to the net's size (interpolation=, or resample= for 9 to 16 bits)")
         self._guided_work = self.eng.guided_workspace(H, W, B)
 
-    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels", "subpel", "overlap", "sequence")
+    TEMPORAL_KEYS = ("strength", "sensitivity", "radius", "matrix", "source_bgr", "levels", "subpel", "overlap", "sequence", "streams")
 
     def _temporal_setup(self, opt, slots):
         """The temporal stage's fixed parts: the quantised strength, the checked parameters, the state slots and the stabilised tensor."""
@@ -296,7 +310,14 @@ class FrameStylizer(object):
         sequence = kw.get("sequence", False)
         if not isinstance(sequence, (bool, np.bool_)):
             raise L.FaststyleError("temporal sequence is True or False, got %r" % (sequence,))
-        if self.shape[0] != 1 and not sequence:
+        streams = kw.get("streams", False)
+        if not isinstance(streams, (bool, np.bool_)):
+            raise L.FaststyleError("temporal streams is True or False, got %r" % (streams,))
+        if streams and sequence:
+            raise L.FaststyleError("temporal streams and sequence are mutually exclusive: a batch is independent streams or consecutive frames of one")
+        if streams and self.shape[0] > 64:
+            raise L.FaststyleError("temporal streams takes at most 64 streams per pass, this stylizer has a batch of %d" % self.shape[0])
+        if self.shape[0] != 1 and not sequence and not streams:
             raise L.FaststyleError("temporal takes one frame per pass, this stylizer has a batch of %d" % self.shape[0])
 
         def number(name, default, lo, hi, whole):
@@ -324,6 +345,15 @@ class FrameStylizer(object):
         if overlap > 0:                                      # (likewise; the slots are those of (levels, subpel))
             self.temporal["overlap"] = overlap
         Ho, Wo = self.out_shape[1:3]
+        if streams:                                          # one state buffer and one control word per stream instead of two slots and a parity
+            S = self.shape[0]
+            self.temporal["streams"] = True
+            self._tslots = self.eng.temporal_streams_state(Ho, Wo, S, levels, subpel) if slots is None else slots
+            self._sctl = self.eng.i32_buffer([0] * S)
+            self._sctl_stage = self.eng.i32_staging(S)
+            self._sh = dict(prev=[False] * S, parity=[0] * S, active=[True] * S, last=None)
+            self._stab = self.eng.mem.empty(self.out_shape)
+            return
         if slots is None:
             slots = [self.eng.temporal_state(Ho, Wo, levels, subpel) if subpel > 0 else self.eng.temporal_state(Ho, Wo, levels) for _ in range(2)]
         self._tslots = slots
@@ -677,6 +707,12 @@ class FrameStylizer(object):
         """The temporal stage of frame n since construction or reset(), and the output conversions of the stabilised tensor.  It writes
         slot n & 1 and reads slot (n - 1) & 1, so running it twice on one frame (the warm-up of a capture, then the replay) changes nothing."""
         t = self.temporal
+        if self._sh is not None:                             # independent streams: which slot and whether there is a previous frame are device words
+            self.eng.temporal_streams_f32(self._in_f32, self.eng.mem.view(self._cur, 0, self.out_shape), self._stab, self._sctl, self._tslots,
+                                          strength_q8=t["strength_q8"], sensitivity=t["sensitivity"], radius=t["radius"], matrix=t["matrix"],
+                                          src_bgr=t["source_bgr"], levels=t.get("levels", 1), subpel=t.get("subpel", 0), overlap=t.get("overlap", 0))
+            self._outputs(self._stab)
+            return
         kw = dict(prev=None if n == 0 else self._tslots[(n - 1) & 1], strength_q8=t["strength_q8"], sensitivity=t["sensitivity"], radius=t["radius"],
                   matrix=t["matrix"], src_bgr=t["source_bgr"], levels=t.get("levels", 1), **{k: t[k] for k in ("subpel", "overlap") if k in t})
         if self._twork is not None:                          # a pass of consecutive frames: n counts passes
@@ -720,6 +756,8 @@ class FrameStylizer(object):
         self._hi_jpeg = jpeg_in
         if self.mix is not None:
             self._mix_prepare()                            # (the weights go up ahead of the launches that read them)
+        if self._sh is not None:
+            self._streams_prepare()                        # (likewise the streams' control words, ahead of the tail)
         if not self._use_graph:
             self._device_pass(jpeg_in)
         elif self.mix is not None:
@@ -740,19 +778,70 @@ class FrameStylizer(object):
         if not self._use_graph:
             self._tail(n)
         else:
-            kind = None if n == 0 else n & 1
+            kind = "streams" if self._sh is not None else None if n == 0 else n & 1
             if self._guided is not None and jpeg_in:             # (a JPEG frame's guide is another buffer than a pixel frame's)
                 kind = (kind, True)
             if kind not in self._tail_graphs:
                 self._tail_graphs[kind] = self._captured(lambda: self._tail(n))
             self._tail_graphs[kind].replay()
         self._tn = n + 1
+        if self._sh is not None:
+            self._streams_advance()
 
-    def reset(self):
-        """Forget the previous frame: the next one is stabilised as a first frame (temporal= only)."""
+    def reset(self, stream=None):
+        """Forget the previous frame: the next one is stabilised as a first frame (temporal= only).  On a streams lane: of one stream
+        (its index) or of all (None); the next pass in which that stream is active is its first frame."""
         if self.temporal is None:
             raise L.FaststyleError("reset: this stylizer was built without temporal=")
-        self._tn = 0
+        if self._sh is None:
+            if stream is not None:
+                raise L.FaststyleError("reset: stream= names a stream of a lane built with temporal streams=True")
+            self._tn = 0
+            return
+        S = self.shape[0]
+        if stream is None:
+            self._sh["prev"][:] = [False] * S
+            return
+        if isinstance(stream, (bool, np.bool_)) or not isinstance(stream, (int, np.integer)) or not 0 <= stream < S:
+            raise L.FaststyleError("reset: stream must be a whole number in [0, %d), got %r" % (S, stream))
+        self._sh["prev"][int(stream)] = False
+
+    def set_streams(self, active=None):
+        """Which streams take part in the passes that follow: ``batch`` booleans, None for all (temporal streams=True only).  An inactive
+        stream is skipped by the temporal stage: its state and its slot parity stay, and its row of the stabilised tensor, and so of
+        the results, is whatever this lane held there.  Nothing is enqueued here; the next pass uploads the control words ahead of its tail."""
+        if self._sh is None:
+            raise L.FaststyleError("set_streams: this stylizer was built without temporal streams=True")
+        S = self.shape[0]
+        if active is None:
+            active = [True] * S
+        try:
+            active = list(active)
+        except TypeError:
+            raise L.FaststyleError("set_streams: active is %d booleans (the batch), got %r" % (S, active))
+        if len(active) != S or not all(isinstance(a, (bool, np.bool_)) for a in active):
+            raise L.FaststyleError("set_streams: active is %d booleans (the batch), got %r" % (S, active))
+        self._sh["active"][:] = [bool(a) for a in active]
+
+    def _streams_words(self):
+        """The control words of the pass under way from the host's view of the streams"""
+        h = self._sh
+        return [(L.FS_TS_SLOT if p else 0) | ((L.FS_TS_PREV if v else 0) if a else L.FS_TS_SKIP) for v, p, a in zip(h["prev"], h["parity"], h["active"])]
+
+    def _streams_prepare(self):
+        """Ahead of a pass (and of the capture of its tail): the control words into the lane's device buffer -- an asynchronous copy on
+        the current stream, the lane's, from the lane's staging words, which the previous pass's download has long left behind."""
+        self.eng.i32_upload(self._sctl, self._streams_words(), self._sctl_stage)
+
+    def _streams_advance(self):
+        """Behind a pass, on the host only (so that the warm-up of a capture and the replay see the same words): every active stream has a
+        previous frame now and writes its other slot next; `last` names, per stream, the slot it wrote last."""
+        h = self._sh
+        for s, a in enumerate(h["active"]):
+            if a:
+                h["prev"][s] = True
+                h["parity"][s] ^= 1
+        h["last"] = [L.FS_TS_SLOT * (p ^ 1) for p in h["parity"]]
 
     def _upload_jpeg(self, staging):
         """Decoded coefficients (decode_frames' staging) -> the device coefficient buffer, on the current stream."""
@@ -828,7 +917,7 @@ class FrameStylizer(object):
 
     def stabilised_output(self):
         """For tests and inspection: a host float32 copy [B,Ho,Wo,3] of the stabilised tensor of the last pass (synchronises; B is 1 but on a
-        sequence lane); a stylizer built without temporal= has none."""
+        sequence or streams lane, where an inactive stream's row is whatever the lane held); a stylizer built without temporal= has none."""
         if self._stab is None:
             raise L.FaststyleError("stabilised_output: this stylizer was built without temporal=")
         if self._y is None:
@@ -846,18 +935,21 @@ class FrameStylizer(object):
 
     def motion_vectors(self):
         """For tests and inspection: the block vectors (dy, dx) of the last pass, host int8 [ceil(Ho / 16), ceil(Wo / 16), 2], on a sequence
-        lane of batch N [N, ...] (synchronises)."""
+        lane of batch N [N, ...], on a streams lane of batch S [S, ...], every stream's from the pass it last took part in (synchronises)."""
         if self._tslots is None:
             raise L.FaststyleError("motion_vectors: this stylizer was built without temporal=")
         if self._tn == 0:
             raise L.FaststyleError("motion_vectors: this stylizer has not run a frame since it was built or reset")
-        if self._twork is not None:
+        if self._twork is not None or self._sh is not None:
             return self._batch_vectors()[0]
         return np.array(self.eng.mem.to_numpy(self._tslots[(self._tn - 1) & 1][2]), dtype=np.uint8, copy=True).view(np.int8)
 
     def _batch_vectors(self):
         """(mv, mvf or None) of the N frames of a sequence lane's last pass"""
         t = self.temporal
+        if self._sh is not None:                                 # every stream's from the slot it wrote last
+            return self.eng.temporal_streams_vectors(self._tslots, self._sh["last"], self.out_shape[1], self.out_shape[2], t.get("levels", 1),
+                                                     t.get("subpel", 0))
         return self.eng.temporal_batch_vectors(self._twork, self._tslots[(self._tn - 1) & 1], self.out_shape[1], self.out_shape[2], self.shape[0],
                                                t.get("levels", 1), t.get("subpel", 0))
 
@@ -867,7 +959,7 @@ class FrameStylizer(object):
         if self._tslots is None or "subpel" not in self.temporal:
             raise L.FaststyleError("motion_vectors_subpel: this stylizer was built without temporal subpel=")
         mv = self.motion_vectors()                               # (refuses a lane that has not run a frame)
-        if self._twork is not None:
+        if self._twork is not None or self._sh is not None:
             return 4 * mv.astype(np.int16) + self._batch_vectors()[1].astype(np.int16)
         mvf = np.array(self.eng.mem.to_numpy(self._tslots[(self._tn - 1) & 1][-1]), dtype=np.uint8, copy=True).view(np.int8)
         return 4 * mv.astype(np.int16) + mvf.astype(np.int16)
@@ -947,7 +1039,9 @@ class PipelinedStylizer(object):
     right behind frame n - 1's tail on the other lane's stream; the forward passes of two frames still overlap, and frame n + 1 overwrites
     the slot frame n reads only behind that chain.  Results equal the one-lane results, in order, for any depth.  reset() forgets the
     previous frame and is allowed with nothing in flight.  With temporal sequence=True and batch=N all of this goes by pass of N frames; every
-    lane has its own work buffer.
+    lane has its own work buffer.  With temporal streams=True the lanes share the one state buffer and the host's view of the streams, each
+    has its own control words, and the tails are chained by events per pass in the same way; set_streams() and reset(stream=) apply to the
+    passes submitted after them, also with passes in flight.
 
     mix= is handed to every lane: each has its own second workspace, output tensors, mixed tensor, weight buffer and pinned staging words.
     set_mix(weight) applies to the frames submitted after it: submit() hands the weights to the frame's lane, which uploads them on its own
@@ -964,6 +1058,7 @@ class PipelinedStylizer(object):
         for _ in range(self.depth):                              # (temporal=: the first lane allocates the state slots, the others share them)
             more = dict(kw, _temporal_slots=self.lanes[0]._tslots) if self.lanes and kw.get("temporal") is not None else kw
             self.lanes.append(FrameStylizer(eng, variables, height, width, **more))
+            self.lanes[-1]._sh = self.lanes[0]._sh               # (temporal streams=True: one host view of the streams; each lane has its own control words)
         self.streams = [torch.cuda.Stream() for _ in self.lanes]
         self.events = [torch.cuda.Event() for _ in self.lanes]
         self.temporal = self.lanes[0].temporal
@@ -1055,13 +1150,22 @@ class PipelinedStylizer(object):
         """Frames submitted and not yet fetched (at most `depth`)."""
         return len(self._pending)
 
-    def reset(self):
-        """Forget the previous frame (temporal= only); with nothing in flight."""
+    def reset(self, stream=None):
+        """Forget the previous frame (temporal= only); with nothing in flight.  With temporal streams=True: of one stream (its index) or of
+        all (None), for the passes submitted after this call -- passes in flight keep the control words they were submitted with."""
         if self.temporal is None:
             raise L.FaststyleError("reset: this stylizer was built without temporal=")
+        if self.lanes[0]._sh is not None or stream is not None:  # (the chain of tails goes on: _tframe stays)
+            self.lanes[0].reset(stream)
+            return
         if self._pending:
             raise L.FaststyleError("reset: %d frames in flight -- fetch() them first" % len(self._pending))
         self._tframe = 0
+
+    def set_streams(self, active=None):
+        """Which streams take part in the passes submitted after this call (temporal streams=True only): ``batch`` booleans, None for all.
+        Passes in flight keep the control words they were submitted with."""
+        self.lanes[0].set_streams(active)
 
     def set_mix(self, weight):
         """The share of the second model in the frames submitted after this call (mix= only): a number in [0, 1], or ``batch`` numbers for

@@ -684,6 +684,48 @@ int fs_temporal_batch_f32(fs_ctx* ctx, const float* src, int H, int W, const flo
                           unsigned short* out88, unsigned char* pyr, signed char* mv, signed char* mvf, void* work, size_t work_bytes,
                           float* dst);
 
+/* ---- Batches of independent streams for the temporal stage (csrc/fs_temporal.hip): `streams` S in [1, 64] streams, one frame of each, in
+ * one call.  The arithmetic is that of the blocks above and is not restated: for every stream s without FS_TS_SKIP the call writes bit for
+ * bit what fs_temporal_obmc_f32 writes for image s of src and cur with the same parameters, its prev_* being the slot of stream s that this
+ * pass does not write where FS_TS_PREV is set and all null where it is clear (no previous frame: zero vectors and F = B), its luma / out88 /
+ * pyr / mv / mvf the slot written, its dst image s of dst; dst may be cur.  For a stream with FS_TS_SKIP nothing is read or written: neither
+ * of its slots nor image s of dst.  Nothing is recursive inside such a pass, so luma, pyramid, every search level, the refinement and the
+ * blend each run once over all streams (the stream is one more grid dimension): the launches are those of one single-frame call whatever S
+ * is, 3 at L = 1, S = 0 and 7 at L = 3, S = 2.
+ *
+ * What differs per stream is a device word: ctl is int32 [S] in device memory, read by every launch of the call (so it is written ahead of
+ * the call on the same stream, or otherwise ordered before it, and left alone until the call has completed); bits above 2 are ignored.
+ * The state of all streams is one device buffer, 16-byte aligned: stream s has its two slots at s stream_stride and s stream_stride +
+ * slot_stride, each [luma | out88 | pyr | mv | mvf] at the reported offsets, laid out inside as the single-frame buffers are (pyr as
+ * fs_temporal_pyr_layout says; pyr_bytes is 0 at one level and mvf has no bytes at subpel 0).  A stream alternates FS_TS_SLOT from one of
+ * its passes to the next; a skipped pass does not count. */
+#define FS_TS_PREV 1 /* the stream has a previous frame, in the slot not written; clear: a first frame */
+#define FS_TS_SLOT 2 /* the slot this pass writes is the second one; it reads the other */
+#define FS_TS_SKIP 4 /* the stream does not take part: its workgroups return before their first access and before any barrier */
+
+/* What fs_temporal_streams_layout reports; every offset and stride is a multiple of 16, stream_stride = 2 slot_stride, state_bytes = streams
+ * stream_stride.  No implicit padding: 4 int32, then uint64. */
+typedef struct fs_temporal_streams_info {
+    int32_t streams, levels, subpel, reserved;
+    uint64_t luma_offset, out88_offset, pyr_offset, mv_offset, mvf_offset;
+    uint64_t slot_stride, stream_stride, state_bytes;
+} fs_temporal_streams_info;
+
+/* Host only: no HIP call, no global state, no allocation.  Errors: -1 null info, Ho or Wo below 1, streams outside [1, 64]; -2 levels outside
+ * [1, 3], subpel outside [0, 2]. */
+int fs_temporal_streams_layout(int Ho, int Wo, int levels, int subpel, int streams, fs_temporal_streams_info* info);
+
+/* src [streams, H, W, 3], cur and dst [streams, Ho, Wo, 3] fp32.  The stream index comes from the grid and is bounded by `streams`.  No value
+ * read from a tensor reaches an address except through the held vectors, as in the single-frame calls, and through the slot index
+ * (ctl[s] >> 1) & 1, the only value from the control buffer that does, which the mask bounds: whatever ctl holds, every access lies inside
+ * stream s's two slots.  Asynchronous on the ctx stream, allocates nothing, can be captured into a hipGraph (one graph serves every control
+ * pattern: first frames, parities and skips are data).  A refused call launches nothing.  Errors: those of fs_temporal_obmc_f32 that do not
+ * concern its state pointers; -1 streams outside [1, 64], null ctl or state, state_bytes below the layout's; -5 state not 16-byte aligned,
+ * ctl not 4-byte aligned. */
+int fs_temporal_streams_f32(fs_ctx* ctx, const float* src, int H, int W, const float* cur, int Ho, int Wo, int streams, int strength_q8,
+                            int sensitivity, int radius, int levels, int subpel, int overlap, int matrix, int src_bgr, const int* ctl,
+                            void* state, size_t state_bytes, float* dst);
+
 /* ---- Resampling between fp32 tensors (csrc/fs_resample.hip): the net's (or composed, or stabilised) output at a delivery size, a deep
  * source's fp32 planes at the net's size; no u8 stage on either path.  The arithmetic below is the contract: it is Pillow's Image.resize on
  * mode-F images (double coefficients, double accumulation, a float32 result), and tests/test_resample.py restates it in numpy, holds the

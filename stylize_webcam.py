@@ -63,6 +63,14 @@ are written.  Latency grows by N frames, so live pipes keep 1.  ``--precision bf
 only: not with --upsample_method deconv) with --frames_dir, --video_in and the camera.  Without the flags, or with ``--video_batch 1`` /
 ``--precision fp32``, nothing changes.
 
+Several streams: ``--video_also IN OUT`` (repeatable, up to 63 times, with --video_in and --video_out) names one more YUV4MPEG2 stream of the
+first one's size and format; every pass takes one frame of every open stream, so the net runs a batch without a frame of latency: eight
+cameras or eight files in one process.  With ``--temporal_strength`` every stream is stabilised on its own, against its own previous frame
+(faststyle_amd/stream.py, temporal streams=), in the launches of one stream.  A stream that ends or breaks off leaves the passes, its file
+is closed complete and the others go on; the run ends with the last stream, and a stream that broke off is reported then.  Every other flag
+applies to all streams alike (one mask, one --mix_fade weight per pass).  A pass waits for every open stream: live sources are not paced
+against each other.  Not with --video_batch, --frames_dir or the camera; without the flag nothing changes.
+
 Two styles: ``--model_path2 CKPT`` names a second model of the same --upsample_method; every frame goes through both nets and their fp32
 outputs are mixed on the device, one launch ahead of every stage above (faststyle_amd/stream.py, mix=).  ``--style_mix T`` (0..1, default 1)
 is the share of the second model, ``--mix_mask FILE`` (a grey image of the net's input size: 0 shows --model_path, 255 the mix) puts one style
@@ -164,6 +172,30 @@ def batch_options(args):
     if bf16 and args.upsample_method == 'deconv':
         raise SystemExit('--precision bf16 does not take --upsample_method deconv: the mixed-precision path is for resize-conv models')
     return batch or 1, bf16
+
+
+def also_options(args):
+    """--video_also IN OUT, repeatable -> [(IN, OUT), ...] of the further streams, [] without the flag (absent from the namespace unless
+    given).  Without both --video_in and --video_out, with --video_batch, more than 63 pairs, '-' for more than one input or more than one
+    output, or a file named twice: a SystemExit here, before anything is loaded."""
+    also = getattr(args, 'video_also', None)
+    if also is None:
+        return []
+    if args.video_in is None or args.video_out is None:
+        raise SystemExit('--video_also needs --video_in and --video_out: it names further streams beside that one')
+    if getattr(args, 'video_batch', None) is not None:
+        raise SystemExit('--video_also and --video_batch are mutually exclusive: a batch is one frame of every stream or consecutive frames of one')
+    if len(also) > 63:
+        raise SystemExit('--video_also was given %d times: at most 63 (64 streams per pass)' % len(also))
+    ins, outs = [args.video_in] + [a for a, _ in also], [args.video_out] + [b for _, b in also]
+    for flag, names in (('input', ins), ('output', outs)):
+        if names.count('-') > 1:
+            raise SystemExit('--video_also: - names more than one %s: the standard %s serves one stream' % (flag, flag))
+    files = [os.path.abspath(n) for n in ins + outs if n != '-']
+    for n in files:
+        if files.count(n) > 1:
+            raise SystemExit('--video_also: %s is named more than once: every stream has its own input and output' % n)
+    return [(a, b) for a, b in also]
 
 
 def delivery_options(args):
@@ -455,6 +487,7 @@ def check_video_flags(args):
             raise SystemExit('--frame_filter resamples the fp32 frames of a deep stream: it needs --video_in and --video_depth stream')
         if args.frame_size is None:
             raise SystemExit('--frame_filter needs --frame_size W H: it is the filter of that resize')
+    also_options(args)
 
 
 def run_video(args):
@@ -468,10 +501,11 @@ def run_video(args):
     delivery = delivery_options(args)
     guided = guided_options(args, args.video_matrix)
     batch, bf16 = batch_options(args)
+    also = also_options(args)
     mix = mix_options(args)
     frame_filter = getattr(args, 'frame_filter', None)
     to_stdout = args.video_out == '-'
-    log = sys.stderr if to_stdout else sys.stdout
+    log = sys.stderr if to_stdout or any(b == '-' for _, b in also) else sys.stdout
 
     def say(text):
         print(text, file=log)
@@ -479,12 +513,26 @@ def run_video(args):
 
     fin = sys.stdin.buffer if args.video_in == '-' else open(args.video_in, 'rb')
     fout = None
+    more_in, more_out = [], []                                               # --video_also: the further streams' files
     try:
         try:
             reader = y4m.Reader(fin, deep=args.video_depth == 'stream')
         except y4m.Y4MError as e:
             raise SystemExit('--video_in %s: %s' % (args.video_in, e))
         fmt = reader.format
+        readers = [reader]
+        for name, _ in also:                                                 # every further stream has the first one's frames
+            more_in.append(sys.stdin.buffer if name == '-' else open(name, 'rb'))
+            try:
+                readers.append(y4m.Reader(more_in[-1], deep=args.video_depth == 'stream'))
+            except y4m.Y4MError as e:
+                raise SystemExit('--video_also %s: %s' % (name, e))
+            other = readers[-1].format
+            for field, what in (('width', 'width'), ('height', 'height'), ('components', 'components'), ('sampling', 'sampling'),
+                                ('siting', 'siting'), ('full_range', 'range'), ('bits', 'bits')):
+                if getattr(other, field) != getattr(fmt, field):
+                    raise SystemExit('--video_also %s: its %s %r is not that of --video_in %s, %r: the streams of a pass have one size and '
+                                     'format' % (name, what, getattr(other, field), args.video_in, getattr(fmt, field)))
         Ws, Hs = fmt.width, fmt.height
         colour = dict(sampling=fmt.sampling, siting=fmt.siting, matrix=args.video_matrix, full_range=fmt.full_range, components=fmt.components)
         colour_in = dict(colour, bits=fmt.bits) if fmt.bits != 8 else colour       # (an 8-bit stream runs exactly as without --video_depth)
@@ -547,6 +595,10 @@ def run_video(args):
             kw.update(batch=batch)
             if temporal is not None:
                 kw.update(temporal=dict(temporal, sequence=True))
+        if also:                                                             # (the batch's images are one frame of every stream: likewise)
+            kw.update(batch=len(readers))
+            if temporal is not None:
+                kw.update(temporal=dict(temporal, streams=True))
         if mix is not None:
             kw.update(mix=mix_dict(eng, args, mix))
         fading = mix is not None and mix['fade'] is not None
@@ -555,7 +607,7 @@ def run_video(args):
         def set_weights(n):
             """The weights of the next pass of n consecutive frames (a last pass's padding counts on: it is never written)"""
             ws = [fade_weight(mix, sent[0] + i) / 256.0 for i in range(n)]
-            st.set_mix(ws if batch > 1 else ws[0])
+            st.set_mix(ws if batch > 1 else ws[0])                           # (--video_also: one pass is one frame number, one weight for all)
             sent[0] += n
         depth = int(os.environ.get('FS_FRAMES_IN_FLIGHT', '2')) if hasattr(eng.mem, 'torch') else 1
         if depth > 1:
@@ -566,6 +618,10 @@ def run_video(args):
         if args.video_out is not None:
             fout = sys.stdout.buffer if to_stdout else open(args.video_out, 'wb')
             writer = y4m.Writer(fout, st.yuv_out_desc, rate=fmt.rate, aspect=fmt.aspect)
+            writers = [writer]
+            for (_, name), r in zip(also, readers[1:]):
+                more_out.append(sys.stdout.buffer if name == '-' else open(name, 'wb'))
+                writers.append(y4m.Writer(more_out[-1], st.yuv_out_desc, rate=r.format.rate, aspect=r.format.aspect))
         elif not os.path.isdir(args.output_dir):
             os.makedirs(args.output_dir)
         say('Begin filtering...')
@@ -584,7 +640,60 @@ def run_video(args):
 
         failed = None                                                        # a stream that breaks off: what was read is still written
         try:
-            if batch > 1:
+            if also:
+                # one frame of every open stream per pass: the readers fill their rows of the [S, frame_bytes] buffer; a stream that has ended
+                # or broken off is inactive from then on, its row stays as it is and is not written
+                S = len(readers)
+                names = [args.video_in] + [a for a, _ in also]
+                outs_of = [args.video_out] + [b for _, b in also]
+                is_open, broke = [True] * S, []
+                took = collections.deque()
+
+                def close_out(s):
+                    writers[s].flush()
+                    if s > 0 and outs_of[s] != '-':
+                        more_out[s - 1].close()
+
+                def emit_rows(outs):
+                    for s in took.popleft():
+                        writers[s].write_frame(outs[s])
+                        done[0] += 1
+
+                buf = None if depth > 1 else np.zeros((S, fmt.frame_bytes), np.uint8)
+                while any(is_open):
+                    if depth > 1:
+                        if st.in_flight >= depth:
+                            emit_rows(st.fetch())
+                        buf = st.next_input()                                # [S, frame_bytes], pinned
+                    ended = []
+                    for s in range(S):
+                        if not is_open[s]:
+                            continue
+                        try:
+                            is_open[s] = bool(readers[s].read_frame_into(buf[s]))
+                        except y4m.Y4MError as e:
+                            is_open[s] = False
+                            broke.append('%s %s: %s' % ('--video_in' if s == 0 else '--video_also', names[s], e))
+                        if not is_open[s]:
+                            ended.append(s)
+                    if any(is_open):
+                        if temporal is not None:
+                            st.set_streams(list(is_open))
+                        took.append([s for s in range(S) if is_open[s]])
+                        if fading:
+                            set_weights(1)
+                        if depth > 1:
+                            st.submit(buf)
+                        else:
+                            emit_rows(st(buf))
+                    if ended:                                                # (their last frames may still be in flight: written first)
+                        while depth > 1 and st.in_flight:
+                            emit_rows(st.fetch())
+                        for s in ended:
+                            close_out(s)
+                if broke:
+                    failed = '; '.join(broke)
+            elif batch > 1:
                 # N frames per pass: the reader fills the [N, frame_bytes] buffer row by row; a last pass is padded with the last frame read
                 # and only its real frames are written
                 real = collections.deque()
@@ -653,12 +762,16 @@ def run_video(args):
             writer.flush()
         say('%d frames' % done[0])
         if failed is not None:
-            raise SystemExit('--video_in %s: %s' % (args.video_in, failed))
+            raise SystemExit(str(failed) if also else '--video_in %s: %s' % (args.video_in, failed))
     finally:
         if args.video_in != '-':
             fin.close()
         if fout is not None and not to_stdout:
             fout.close()
+        for (a, b), fa, fb in zip(also, more_in, more_out + [None] * len(also)):
+            for name, f in ((a, fa), (b, fb)):
+                if f is not None and name != '-' and not f.closed:
+                    f.close()
 
 
 def run_webcam(args):

@@ -58,6 +58,14 @@ device time of one 720p forward pass of one model and of two models alternating 
 per pass), whose difference is the second forward's.  (b) the 720p raw-video loop with one model and with --model_path2 ... --style_mix 0.5,
 and (c) with --mix_fade over the middle tenth of the frames: three legs that alternate in the one run, rates from the difference between n
 and n / 4 frames; written to profiles/video_mix.json with the digest of the kernel sources.  "mix_kernels" as the third argument runs (a) alone.
+"video" with "streams" as the fifth argument (pipe_bench.py 1280 4 video profiles/video_streams.json streams): independent streams per pass.
+(a) the device time per frame of one fs_temporal_streams_f32 call over 8 streams against 8 single-frame calls on the same data
+(Engine.temporal_f32: what eight batch-1 lanes run), at 720p and 1080p for (levels, subpel, overlap) = (1, 0, 0) and (3, 2, 1): the
+graph-of-200 scheme with the data resident, the two alternating over three repeats.  (b) the raw-video loop over 1080p 4:2:0 files: 8 inputs
+of n / 8 frames through --video_also against one input of n frames at --video_batch 8, --precision fp32 and bf16, without and with
+--temporal_strength 0.6: eight legs that alternate in the one run, rates from the difference between n and n / 4 frames; written to
+profiles/video_streams.json with the digest of the kernel sources.  "video_streams_kernels" as the third argument runs the 720p (3, 2, 1)
+graphs of (a) alone: under a kernel trace that run gives the kernels' shares.
 "host_encode": the host half of the native JPEG OUTPUT path (fs_jpeg_write: Huffman coding of ready coefficient buffers) against PIL's
 Image.save(JPEG) of the same 1280x720 frames (quality 95, 4:2:0) at the same thread count, host only; the coefficient buffers are those of PIL's
 files, read back with fs_jpeg_parse + fs_jpeg_decode (the buffer fs_jpeg_forward_many leaves on the GPU: tests/test_jpeg_encode.py).
@@ -510,6 +518,150 @@ def temporal_batch_kernel_times(sizes=((720, 1280), (1080, 1920)), modes=((1, 0,
     return res
 
 
+def temporal_streams_kernel_times(sizes=((720, 1280), (1080, 1920)), modes=((1, 0, 0), (3, 2, 1)), S=8, launches=200, repeats=3):
+    """-> dict of device microseconds per frame of the temporal stage over one frame of each of S independent streams at radius 7 by (size,
+    levels, subpel, overlap): 'single' S single-frame calls, every stream on two slots of its own (what S batch-1 lanes run), 'streams' one
+    fs_temporal_streams_f32 call on the one state buffer, both reading the state a previous frame of every stream left; timed as kernel_times
+    does (a graph of `launches` repetitions of the S frames), `repeats` times with the two alternating.  Stream k's picture is the batch
+    measurement's, drifting by (1, -2) pixels per frame, k frames further."""
+    from faststyle_amd import _lib
+    eng = engine.Engine()
+    mem = eng.mem
+    res = {}
+    for H, W in sizes:
+        rng = np.random.default_rng(3)
+        small = rng.uniform(0, 255, (H // 8, W // 8, 3)).astype(np.float32)
+        a = np.ascontiguousarray(np.kron(small, np.ones((8, 8, 1), np.float32)) + rng.uniform(-4, 4, (H, W, 3)).astype(np.float32))
+        before = mem.from_numpy(np.stack([np.roll(a, (k, -2 * k), axis=(0, 1)) for k in range(S)]))
+        src = mem.from_numpy(np.stack([np.roll(a, (k, -2 * k), axis=(0, 1)) for k in range(1, S + 1)]))
+        cur = mem.from_numpy(rng.uniform(0, 255, (S, H, W, 3)).astype(np.float32))
+        dst = mem.empty((S, H, W, 3))
+        one = lambda t, i: mem.view(t, i * H * W * 3, (1, H, W, 3))
+        for levels, subpel, overlap in modes:
+            more = dict(dict(levels=levels), **dict(dict(subpel=subpel) if subpel else {}, **(dict(overlap=overlap) if overlap else {})))
+            kw = dict(more, strength_q8=154, sensitivity=16, src_bgr=True, radius=7)
+            slots = [[eng.temporal_state(H, W, levels, subpel) for _ in range(2)] for _ in range(S)]
+            state = eng.temporal_streams_state(H, W, S, levels, subpel)
+            first, then = eng.i32_buffer([_lib.FS_TS_SLOT] * S), eng.i32_buffer([_lib.FS_TS_PREV] * S)
+            for i in range(S):                                                              # the state in front of every stream's frame: slot 1
+                eng.temporal_f32(one(before, i), one(cur, i), one(dst, i), slots[i][1], **kw)
+            eng.temporal_streams_f32(before, cur, dst, first, state, **kw)
+
+            def single():
+                for i in range(S):
+                    eng.temporal_f32(one(src, i), one(cur, i), one(dst, i), slots[i][0], prev=slots[i][1], **kw)
+
+            def streams():
+                eng.temporal_streams_f32(src, cur, dst, then, state, **kw)
+
+            name = "%dp_levels_%d_subpel_%d_overlap_%d" % (H, levels, subpel, overlap)
+            per_call = (2 + levels + (levels > 1) + (subpel > 0))
+            r = res[name] = {"streams": S, "launches": {"single": S * per_call, "streams": per_call},
+                             "single_us_per_frame_repeats": [], "streams_us_per_frame_repeats": []}
+            for _ in range(repeats):
+                r["single_us_per_frame_repeats"].append(kernel_timed(single, launches) / S)
+                r["streams_us_per_frame_repeats"].append(kernel_timed(streams, launches) / S)
+            for k in ("single", "streams"):
+                r[k + "_us_per_frame"] = sorted(r[k + "_us_per_frame_repeats"])[repeats // 2]
+            print("video_streams: %7.1f us per frame single (%s), %7.1f streams (%s): %s" %
+                  (r["single_us_per_frame"], ", ".join("%.1f" % u for u in r["single_us_per_frame_repeats"]), r["streams_us_per_frame"],
+                   ", ".join("%.1f" % u for u in r["streams_us_per_frame_repeats"]), name), flush=True)
+    return res
+
+
+def video_streams(n, repeats=3, out_json=None):
+    """-> dict: temporal_streams_kernel_times and the eight legs of the 1080p raw-video loop; prints them and writes
+    profiles/video_streams.json (after the kernel times and after every repeat, so that a run that is cut short leaves what it measured)."""
+    import contextlib
+    import json
+    import shutil
+    from PIL import Image
+    from faststyle_amd import build as fsbuild
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import stylize_webcam
+    n = max(32, n // 32 * 32)
+    w, h, S = 1920, 1080, 8
+    dst = out_json or os.path.join(root, "profiles", "video_streams.json")
+    res = {"frames": n, "streams": S, "frames_in_flight": 2, "host_threads": "1 driver", "host_cores": os.cpu_count(),
+           "omp_num_threads": os.environ.get("OMP_NUM_THREADS"),
+           "video": "1080p 4:2:0 YUV4MPEG2 (full range, BT.601), file to file of 8-bit 4:2:0; --video_also: 8 inputs of n / 8 frames, 8 outputs",
+           "method": "rate = (n - n/4) / (t(n) - t(n/4)) over all streams' frames, median of %d alternating repeats" % repeats,
+           "source_digest": fsbuild.source_digest(),
+           "launch_count_estimate": {"streams": S, "levels": 3, "subpel": 2, "single": 56, "streams_call": 7,
+                                     "note": "arithmetic of the launch counts, not a measurement: see stage_us_per_frame for the measurement"}}
+
+    def save():
+        with open(dst, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+    res["stage_us_per_frame"] = temporal_streams_kernel_times()
+    save()
+    d = tempfile.mkdtemp()
+    rng = np.random.default_rng(0)
+    base = rng.integers(0, 256, (135, 240, 3), dtype=np.uint8)
+    planes = []
+    for k in range(16):      # 16 distinct natural-ish frames (upsampled noise), reused; PIL's matrix, box-averaged chroma
+        ycc = np.asarray(Image.fromarray(np.roll(base, 5 * k, axis=1)).resize((w, h), Image.BICUBIC).convert("YCbCr"), np.uint16)
+        sub = (ycc[0::2, 0::2, 1:] + ycc[0::2, 1::2, 1:] + ycc[1::2, 0::2, 1:] + ycc[1::2, 1::2, 1:] + 2) >> 2
+        planes.append(b"FRAME\n" + ycc[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 0].astype(np.uint8).tobytes() + sub[:, :, 1].astype(np.uint8).tobytes())
+
+    def write(name, count, start=0):
+        with open(os.path.join(d, name), "wb") as f:
+            f.write(b"YUV4MPEG2 W%d H%d F30:1 Ip A1:1 C420jpeg XCOLORRANGE=FULL\n" % (w, h))
+            for k in range(count):
+                f.write(planes[(start + k) % 16])
+
+    for count in (n, n // 4):
+        write("1080p_%d.y4m" % count, count)
+        for s in range(S):                                        # (stream s starts s frames into the same pictures)
+            write("1080p_%d_of_%d.y4m" % (s, count), count // S, s)
+    parser = stylize_webcam.setup_parser()
+    outs = [os.path.join(d, "out%d.y4m" % s) for s in range(S)]
+    legs = [("video_y4m_1080p_%s_%s%s" % (kind, p, "_temporal_strength_0.6" if t else ""), kind, ["--precision", p] + (["--temporal_strength", "0.6"] if t else []))
+            for t in (False, True) for p in ("fp32", "bf16") for kind in ("batch_8", "also_8")]
+
+    def run(count, kind, flags):
+        model = ["--model_path", os.path.join(root, "models", "starry_final.ckpt")]
+        if kind == "also_8":
+            io_ = ["--video_in", os.path.join(d, "1080p_0_of_%d.y4m" % count), "--video_out", outs[0]]
+            for s in range(1, S):
+                io_ += ["--video_also", os.path.join(d, "1080p_%d_of_%d.y4m" % (s, count)), outs[s]]
+            written = outs
+        else:
+            io_ = ["--video_in", os.path.join(d, "1080p_%d.y4m" % count), "--video_out", outs[0], "--video_batch", "8"]
+            written = outs[:1]
+        args = parser.parse_args(model + io_ + flags)
+        with contextlib.redirect_stdout(io.StringIO()):
+            t0 = time.time()
+            stylize_webcam.run_video(args)
+            dt = time.time() - t0
+        assert sum(os.path.getsize(o) for o in written) > count * w * h * 3 // 2
+        for o in written:
+            os.remove(o)
+        return dt
+
+    run(n // 4, "batch_8", [])                                    # warm-up: library load, first kernels
+    times = {name: [] for name, _, _ in legs}
+    res["legs"] = {}
+    try:
+        for _ in range(repeats):                                  # legs alternate: a drifting clock touches all of them alike
+            for name, kind, flags in legs:
+                times[name].append((run(n, kind, flags), run(n // 4, kind, flags)))
+                print("video_streams: %s: %.2f s for %d frames, %.2f s for %d" % ((name,) + (times[name][-1][0], n, times[name][-1][1], n // 4)), flush=True)
+            for name, _, _ in legs:
+                rates = sorted((n - n // 4) / (a - b) for a, b in times[name])
+                res["legs"][name] = {"frames_per_s": rates[len(rates) // 2], "all_repeats": rates, "seconds_n_and_quarter": times[name]}
+            save()
+    finally:
+        shutil.rmtree(d)
+    for name, _, _ in legs:
+        r = res["legs"][name]
+        print("video_streams: %7.0f frames/s %s (repeats: %s)" % (r["frames_per_s"], name, ", ".join("%.0f" % v for v in r["all_repeats"])))
+    return res
+
+
 def video_batch(n, repeats=3, out_json=None):
     """-> dict: temporal_batch_kernel_times and the eight legs of the 1080p raw-video loop; prints them and writes profiles/video_batch.json
     (after the kernel times and after every repeat, so that a run that is cut short leaves what it measured)."""
@@ -867,6 +1019,12 @@ def main():
     threads = int(sys.argv[2]) if len(sys.argv) > 2 else None
     if len(sys.argv) > 5 and sys.argv[3] == "video" and sys.argv[5] == "batch":
         video_batch(n, out_json=sys.argv[4])
+        return
+    if len(sys.argv) > 5 and sys.argv[3] == "video" and sys.argv[5] == "streams":
+        video_streams(n, out_json=sys.argv[4])
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "video_streams_kernels":
+        temporal_streams_kernel_times(sizes=((720, 1280),), modes=((3, 2, 1),), repeats=1)
         return
     if len(sys.argv) > 5 and sys.argv[3] == "video" and sys.argv[5] == "mix":
         video_mix(n, out_json=sys.argv[4])
