@@ -537,7 +537,11 @@ int wino6_launch(const ConvArgs& a, hipStream_t s) {
     // their waves fit on a SIMD beside a GEMM wave --   s:    K1a | K2a        | K2b        | K3b
     //                                                   side:      | K1b        | K3a        |          (joined before returning)
     const long Ta = ((Tall / 2) + 127) & ~127L;
-    if (a.w6_side && a.w6_ev && !Profiler::current() && knob(K_WINO6_PIPE) && Tall - Ta >= 128 && cap >= Ta + (((Tall - Ta) + 127) & ~127L)) {
+    const bool pipe = a.w6_side && a.w6_ev && !Profiler::current() && knob(K_WINO6_PIPE) && Tall - Ta >= 128 && cap >= Ta + (((Tall - Ta) + 127) & ~127L);
+    if (knob(K_CONV_DEBUG))  // tuning aid, behind conv_launch's line: how the launch's tiles go out
+        fprintf(stderr, "wino6 N%d %dx%dx%d -> %dx%dx%d: %ld tiles in %ld chunks over %s\n", a.N, a.H, a.W, a.Cin, a.Ho, a.Wo, a.Cout, Tall,
+                pipe ? 2L : (Tall + cap - 1) / cap, pipe ? "two streams" : "one stream");
+    if (pipe) {
         const W6Args ca = chunk(0, Ta, a.w6_ws);
         const W6Args cb = chunk(Ta, Tall - Ta, a.w6_ws + (size_t)36 * ca.Tpad * ((size_t)a.Cin + a.Cout));
         hipStream_t t = a.w6_side;
